@@ -37,18 +37,14 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
 # The step runs on three HIP streams (student, teacher one step ahead, weight
-# gradients) and RCCL adds its own.  The ROCm runtime multiplexes streams onto 4
-# hardware queues by default: once a process group exists two of the step's
-# streams land on ONE queue and the teacher overlap is gone (measured with the
-# collectives forced in a 1-rank group: 36.8 ms per step at the default, 35.1-35.5
-# with 5 / 6 / 8 queues = the figure without a process group).  hipGraph replays
-# need DEBUG_HIP_FORCE_GRAPH_QUEUES=2 next to it (the graph executor's internal
-# streams must not each get a hardware queue of their own: bf16 replay 28 ms vs
-# 15.2, profiles/r05_graph_queues_s1.jsonl; ld_amd/__init__.py, DESIGN.md section
-# 6).  The runtime reads both when it initialises, at the first HIP call.
+# gradients) and RCCL adds its own, multiplexed by the ROCm runtime onto its
+# default hardware queues; the hardware-queue count is left to the runtime.  A
+# hipGraph launch spreads the captured branches over DEBUG_HIP_FORCE_GRAPH_QUEUES
+# internal streams; the step has two lanes, so a multi-process job holds it to 2
+# (profiles/r05_graph_queues_s1.jsonl; ld_amd/__init__.py).
+# The runtime reads it when it initialises, at the first HIP call.
 if int(os.environ.get('WORLD_SIZE', '1')) > 1 or \
         os.environ.get('LD_FORCE_COLLECTIVES') == '1':
-    os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
     os.environ.setdefault('DEBUG_HIP_FORCE_GRAPH_QUEUES', '2')
 
 import torch  # noqa: E402
@@ -83,7 +79,14 @@ def parse():
                     'headline R50<-R101 fp32 step (default); 4 = R101 <- '
                     'R101-DCN (ld_r101_gflv1_r101dcn_fpn_coco_2x); 5 = LDv2 '
                     'R50 <- X101 \'finegrained\'')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the headline step '
+                    'computed in its last timed step to DIR/<name>.npy (see '
+                    'dump_outputs)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 # per-config workload: detector builder, name, analytic conv GFLOP per image
@@ -488,6 +491,38 @@ def cpu_baseline(batch, sdepth=50, tdepth=101, reps=3):
                 f'{model} ({phys} physical / {logical} logical)')
 
 
+DUMP_SAMPLE = 1 << 20  # elements drawn from each flat buffer by dump_outputs
+
+
+def dump_outputs(dirname, out, trainer, seed=0):
+    """--dump-outputs: what the headline step (SGDTrainer.step) computed in its
+    last timed step, for comparing two builds output for output.  One file per
+    loss key the step returned (log_vars, float64), and the same fixed, seeded
+    sample of DUMP_SAMPLE elements of the updated student parameters, of the
+    gradient that update applied and of the momentum buffer (float32; the full
+    buffers are ~130 MB each), with the sampled flat indices (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    log_vars = out['log_vars']  # the copies to the host below synchronise
+    for k in log_vars.keys():
+        np.save(os.path.join(dirname, f'{k}.npy'),
+                np.asarray(log_vars[k], dtype=np.float64))
+    flat = dict(params=trainer.arena.flat_param, grads=trainer.arena.flat_grad,
+                momentum=trainer.flat_momentum)
+    n = flat['params'].numel()
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        g = torch.Generator(device='cpu').manual_seed(seed)
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+    np.save(os.path.join(dirname, 'sample_index.npy'),
+            idx.numpy().astype(np.float64))
+    dev_idx = idx.to(flat['params'].device)
+    for name, t in flat.items():
+        np.save(os.path.join(dirname, f'{name}_sample.npy'),
+                t.index_select(0, dev_idx).float().cpu().numpy())
+
+
 def _device_count():
     # LD_BENCH_FAKE_DEVICES: test hook of tests/test_bench_launcher.py (the
     # launcher logic runs on a box without GPUs); never set it for a measurement
@@ -628,13 +663,17 @@ def main():
     _, dbatch_b = make_batch(args.batch_per_gpu, args.num_gt, 5678 + rank, dev)
     ring = [dbatch, dbatch_b]
     counter = [0]
+    last_out = [None]
 
     def one_step():
         i = counter[0]
         counter[0] = i + 1
         if prefetch:
-            return trainer.step(ring[i % 2], next_data=ring[(i + 1) % 2])
-        return trainer.step(ring[i % 2])
+            out = trainer.step(ring[i % 2], next_data=ring[(i + 1) % 2])
+        else:
+            out = trainer.step(ring[i % 2])
+        last_out[0] = out
+        return out
 
     def timed(n_warm, n_steps):
         # one priming step outside the W warm-up steps: first-call work of a
@@ -707,7 +746,9 @@ def main():
             med = float(tt)
         return med
 
-    ms_sync_median = synced_median(min(max(args.steps, 3), 21))
+    ms_sync_median = synced_median(args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out[0], trainer)
     dt_plain = None
     if prefetch:  # the same K steps with the teacher inside each step, for the record
         prefetch = False
@@ -741,7 +782,7 @@ def main():
                 'between two device synchronisations (SURVEY.md 8(d)); the K steps '
                 'of the driver contract, enqueued back to back inside one barrier + '
                 'synchronize bracket, are images_per_sec_k_step_bracket / '
-                'ms_per_step_k_step_bracket below' % min(max(args.steps, 3), 21)),
+                'ms_per_step_k_step_bracket below' % args.steps),
             'images_per_sec_k_step_bracket': imgs,
             'ms_per_step_k_step_bracket': ms,
             'config': {
@@ -816,7 +857,7 @@ def main():
         from ld_amd import layers as Y
         Y.set_precision('bf16')
         dtb, tenqb, lossb = timed(args.warmup, args.steps)
-        ms_sync_b = synced_median(min(max(args.steps, 3), 21))
+        ms_sync_b = synced_median(args.steps)
         roofb = None
         if not args.no_kernel_roofline:
             roofb = kernel_roofline(trainer, dbatch, args.profile_steps,

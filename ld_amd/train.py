@@ -269,28 +269,7 @@ class GradArena:
         self._works = []
 
 
-_HWQ_CHECKED = [False]
-
-
-def _check_hw_queues():
-    """With a process group the step's three streams + RCCL's need more than the
-    runtime's default of 4 hardware queues (ld_amd/__init__.py sets 8 at import;
-    an application that initialised HIP before importing ld_amd, or exported a
-    smaller value, loses the teacher / weight-gradient overlap: -4.6 % measured)."""
-    if _HWQ_CHECKED[0] or not collectives_on():
-        return
-    _HWQ_CHECKED[0] = True
-    try:
-        q = int(os.environ.get('GPU_MAX_HW_QUEUES', '4'))
-    except ValueError:
-        q = 4
-    if q < 8:
-        import warnings
-        warnings.warn(
-            f'GPU_MAX_HW_QUEUES={q}: with a process group the train step\'s '
-            'streams share hardware queues and stop overlapping; export '
-            'GPU_MAX_HW_QUEUES=8 before the first HIP call (importing ld_amd '
-            'first does it)')
+_RUNTIME_DEFAULT_QUEUES = 4  # the ROCm runtime's hardware and graph-stream defaults
 
 
 def graph_queues_ok():
@@ -306,8 +285,8 @@ def graph_queues_ok():
             return int(os.environ.get(name, default))
         except ValueError:
             return default
-    return _int('GPU_MAX_HW_QUEUES', 4) <= 4 or \
-        _int('DEBUG_HIP_FORCE_GRAPH_QUEUES', 4) == 2
+    return _int('GPU_MAX_HW_QUEUES', _RUNTIME_DEFAULT_QUEUES) <= 4 or \
+        _int('DEBUG_HIP_FORCE_GRAPH_QUEUES', _RUNTIME_DEFAULT_QUEUES) == 2
 
 
 def _warn_graph_queues(what):
@@ -328,7 +307,6 @@ class SGDTrainer:
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4,
                  bucket_bytes=32 << 20, tail_bytes=8 << 20):
-        _check_hw_queues()
         self.model = model
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         frozen = [p for p in model.parameters() if not p.requires_grad]

@@ -4,8 +4,8 @@ with every collective forced (LD_FORCE_COLLECTIVES=1): what importing ld_amd set
 up in a multi-process job, which stepper AutoStepper picks there, that its steps
 equal plain SGDTrainer.step bit for bit over a batch sequence with two padded shapes
 and changing GT counts, that capturing collectives is refused, and -- without
-collectives in the capture -- that a hipGraph replay keeps its speed with the 8
-hardware queues a process group needs.  Prints one JSON line."""
+collectives in the capture -- that a hipGraph replay keeps its speed under a
+process group.  Prints one JSON line."""
 import json
 import os
 import sys
@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
-import ld_amd  # noqa: E402,F401  (sets GPU_MAX_HW_QUEUES / DEBUG_HIP_FORCE_GRAPH_QUEUES)
+import ld_amd  # noqa: E402,F401  (sets DEBUG_HIP_FORCE_GRAPH_QUEUES)
 from ld_amd import layers as Y  # noqa: E402
 from ld_amd import model_zoo, synthetic  # noqa: E402
 from ld_amd import train as T  # noqa: E402
@@ -86,7 +86,7 @@ def main():
         res['capture_refused'] = False
     except RuntimeError as e:
         res['capture_refused'] = 'refused' in str(e)
-    # a capture WITHOUT collectives (suspended): replay speed under 8 hardware queues
+    # a capture WITHOUT collectives (suspended): replay speed under the process group
     d = seq[0]
     with T.suspend_collectives():
         g = T.GraphedStep(tr1, d, warmup=2, warmup_collectives=False)

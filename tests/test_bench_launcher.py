@@ -52,3 +52,54 @@ def test_bench_spawns_the_ranks_itself():
                        env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0
     assert 'only 1 GPU' in r.stderr
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: one float64 file per loss key, and the same seeded sample
+    of the parameter / gradient / momentum buffers (float32) from run to run."""
+    import numpy as np
+    import torch
+
+    import bench
+    from ld_amd.heads import LazyScalars
+
+    class _Arena:
+        flat_param = torch.arange(3 << 20, dtype=torch.float32)
+        flat_grad = -flat_param
+
+    class _Trainer:
+        arena = _Arena()
+        flat_momentum = _Arena.flat_param * 2
+
+    out = dict(log_vars=LazyScalars(['loss_cls', 'loss'],
+                                    torch.tensor([0.5, 1.25])))
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), out, _Trainer())
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['grads_sample.npy', 'loss.npy', 'loss_cls.npy',
+                     'momentum_sample.npy', 'params_sample.npy',
+                     'sample_index.npy']
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.dtype in (np.float32, np.float64)
+        np.testing.assert_array_equal(a, b)
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / 'a' / 'loss.npy')) == 1.25
+    idx = np.load(tmp_path / 'a' / 'sample_index.npy').astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'params_sample.npy'), idx)
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'momentum_sample.npy'),
+                                  2 * idx)
+
+
+def test_steps_must_be_positive(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '0'])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '4',
+                                      '--dump-outputs', 'out'])
+    args = bench.parse()
+    assert args.steps == 4 and args.dump_outputs == 'out'

@@ -2,9 +2,9 @@
 Round 4 left the bf16 step of a multi-process job on a host-bound eager path because
 hipGraph replays collapsed with the 8 hardware queues a process group needs (15 ->
 28 ms).  Round 5: (i) the collapse is the graph executor's internal streams each
-getting a hardware queue -- DEBUG_HIP_FORCE_GRAPH_QUEUES=2, set at import beside
-GPU_MAX_HW_QUEUES=8, removes it (profiles/r05_graph_queues_s1.jsonl: 28.0 -> 15.2 ms;
-set and checked for here); (ii) capturing RCCL collectives races with
+getting a hardware queue -- DEBUG_HIP_FORCE_GRAPH_QUEUES=2, set at import, removes
+it (profiles/r05_graph_queues_s1.jsonl: 28.0 -> 15.2 ms; set and checked for here,
+while the hardware-queue count stays the runtime's own); (ii) capturing RCCL collectives races with
 ProcessGroupNCCL's watchdog thread, so it is refused loudly; (iii) the eager step is
 no longer host-bound, so that is what AutoStepper picks under a process group --
 checked here against plain steps bit for bit, collectives counted."""
@@ -39,7 +39,7 @@ def test_auto_stepper_under_process_group(precision):
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
     print(res)
-    assert res['collectives_on'] and res['hwq'] == '8' and res['graph_queues'] == '2'
+    assert res['collectives_on'] and res['hwq'] is None and res['graph_queues'] == '2'
     assert res['graph_queues_ok']
     assert res['mode'] == 'eager'
     assert res['params_equal'] and res['momentum_equal'] and res['losses_equal'], res

@@ -35,6 +35,24 @@ def test_graph_queues_ok(monkeypatch, hwq, gq, ok):
     assert train.graph_queues_ok() is ok
 
 
+@pytest.mark.parametrize('preset,expect', [(None, '2'), ('4', '4')])
+def test_import_holds_graph_streams_to_two(preset, expect):
+    """`import ld_amd` holds the hipGraph executor to the step's two lanes in
+    every process (before the runtime initialises), unless the application chose
+    a value itself."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ('DEBUG_HIP_FORCE_GRAPH_QUEUES', 'WORLD_SIZE',
+                        'LD_FORCE_COLLECTIVES')}
+    if preset is not None:
+        env['DEBUG_HIP_FORCE_GRAPH_QUEUES'] = preset
+    out = subprocess.run(
+        [sys.executable, '-c', 'import os, ld_amd; '
+         'print(os.environ["DEBUG_HIP_FORCE_GRAPH_QUEUES"])'],
+        cwd=REPO, env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stdout.split()[-1] == expect
+
+
 def test_capture_with_collectives_is_refused(tmp_path, monkeypatch):
     """A one-rank gloo group with the collectives forced stands in for the
     multi-process job: a step capture must raise, LD_GRAPH_COLLECTIVES=1 is the

@@ -1,5 +1,5 @@
 """hipGraph replay time of the train step under a given runtime configuration
-(why does a replay collapse with GPU_MAX_HW_QUEUES > 4?).
+(why does a replay collapse with more hardware queues?).
 The runtime knobs are read from the ENVIRONMENT before the first HIP call:
 GPU_MAX_HW_QUEUES, DEBUG_HIP_FORCE_GRAPH_QUEUES (how many internal streams a
 graph launch spreads its branches over), LD_WGRAD_STREAM (0 = weight gradients
