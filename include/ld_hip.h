@@ -1092,6 +1092,47 @@ int ld_get_bboxes_pre_nms(const ld_geom_t* g, const ld_maps_t* cls,
                           float* factors, void* workspace, size_t workspace_bytes,
                           ld_stream_t stream);
 
+/* Test-time augmentation (BBoxTestMixin.aug_test_bboxes,
+ * dense_test_mixins.py:38-100): one image seen through V views, each view's
+ * get_bboxes(rescale=False, with_nms=False) rows (ld_get_bboxes_pre_nms) are
+ * mapped back to the original image -- bbox_flip (transforms.py:5-30) in fp32,
+ * then a true division by the view's scale_factor -- concatenated view-major
+ * (merge_aug_bboxes) and passed through multiclass_nms with the concatenated
+ * score factors (the factor multiplies a score AFTER its score_thr test).  The
+ * merged set is not materialised; the candidate / NMS / voting stages are those
+ * of ld_get_bboxes_ex.
+ *   boxes         device (K, 4) in the view's image coordinates
+ *   scores        device (K, score_stride) rows, the first num_classes used
+ *                 (no background column)
+ *   factors       device (K,) or NULL -- for every view or for none
+ *   flip          LD_FLIP_*; img_h / img_w = the view's img_shape
+ * flags: LD_INFER_VOTING (not with factors: LD_EUNSUPPORTED), LD_AUG_RESCALE =
+ * rescale=True; without it the result is multiplied by view 0's scale_factor
+ * (dense_test_mixins.py:94-98).  Outputs dets (max_per_img, 5), labels
+ * (max_per_img) int64, count (1) int32, as ld_get_bboxes for one image.
+ * max_per_img <= 1024 and iou_thr >= 0 as there.  Synchronises the stream once
+ * (without LD_INFER_VOTING). */
+#define LD_MAX_AUG_VIEWS 16
+#define LD_FLIP_NONE 0
+#define LD_FLIP_HORIZONTAL 1
+#define LD_FLIP_VERTICAL 2
+#define LD_FLIP_DIAGONAL 3
+#define LD_AUG_RESCALE 8
+typedef struct {
+  const float* boxes;
+  const float* scores;
+  const float* factors;
+  int32_t K, score_stride, flip, reserved;
+  float img_h, img_w;
+  float scale_factor[4];
+} ld_aug_view_t;
+size_t ld_aug_merge_nms_workspace_bytes(const ld_aug_view_t* views, int num_views,
+                                        int num_classes);
+int ld_aug_merge_nms(const ld_aug_view_t* views, int num_views, int num_classes,
+                     float score_thr, float iou_thr, int max_per_img, int flags,
+                     float* dets, int64_t* labels, int32_t* count, void* workspace,
+                     size_t workspace_bytes, ld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

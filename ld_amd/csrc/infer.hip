@@ -74,6 +74,20 @@ __device__ __forceinline__ unsigned long long make_key(float score, unsigned idx
          (unsigned long long)(0xFFFFFFFFu - idx);
 }
 
+// Where the NMS / voting stages read candidate boxes: a candidate key carries
+// the pair index slot * C + class, `box` returns the slot's box of image n.
+// MapBoxes = the decoded (N, Ktot, 4) boxes of get_bboxes; AugBoxes (below,
+// ld_aug_merge_nms) = the views' boxes mapped back on the fly.
+struct MapBoxes {
+  int C, cand_cap, Ktot;
+  const float* boxes;
+  __device__ __forceinline__ void box(int n, int slot, float (&ob)[4]) const {
+    const float* bo = boxes + ((size_t)n * Ktot + slot) * 4;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ob[k] = bo[k];
+  }
+};
+
 // ---- 1. keys ---------------------------------------------------------------
 __global__ __launch_bounds__(256) void infer_keys_kernel(Plan p, ld_maps_t cls,
                                                         ld_maps_t ctr,
@@ -214,12 +228,12 @@ __global__ __launch_bounds__(kSortThreads) void infer_topk_select_kernel(
 // the kSelN best candidates of an image, sorted, into their own buffer (the
 // full list stays intact for the rare fallback)
 __global__ __launch_bounds__(kSortThreads) void infer_cand_select_kernel(
-    Plan p, const unsigned long long* cand, const int* cand_count,
+    int cand_cap, const unsigned long long* cand, const int* cand_count,
     unsigned long long* cand_top) {
   __shared__ SelectLds s;
   const int n = blockIdx.x;
-  const int M = min(cand_count[n], p.cand_cap);
-  select_sort_desc(cand + (size_t)n * p.cand_cap, M, kSelN,
+  const int M = min(cand_count[n], cand_cap);
+  select_sort_desc(cand + (size_t)n * cand_cap, M, kSelN,
                    cand_top + (size_t)n * kSelN, s);
 }
 
@@ -319,12 +333,12 @@ __global__ __launch_bounds__(256) void infer_decode_kernel(
 
 // ---- 4. candidate sort ----------------------------------------------------------
 __global__ __launch_bounds__(kSortThreads) void infer_cand_sort_kernel(
-    Plan p, unsigned long long* cand, const int* cand_count) {
+    int cand_cap, unsigned long long* cand, const int* cand_count) {
   const int n = blockIdx.x;
-  const int M = min(cand_count[n], p.cand_cap);
+  const int M = min(cand_count[n], cand_cap);
   int len = 2;
   while (len < M) len <<= 1;
-  unsigned long long* a = cand + (size_t)n * p.cand_cap;
+  unsigned long long* a = cand + (size_t)n * cand_cap;
   for (int i = M + threadIdx.x; i < len; i += blockDim.x) a[i] = 0ull;
   __syncthreads();
   bitonic_desc(a, len);
@@ -355,11 +369,10 @@ __device__ __forceinline__ float diou_measure(const float (&a)[4], float area_a,
   return inter / uni - powf(D, 0.8f);
 }
 
-template <bool DIOU>
+template <bool DIOU, class Src>
 __global__ __launch_bounds__(kNmsThreads) void infer_nms_kernel(
-    Plan p, const unsigned long long* cand, size_t cand_stride, int limit,
-    const int* cand_count, const unsigned* max_coord, const float* boxes,
-    float iou_thr, int max_keep, float* dets, long long* labels, int* counts,
+    Src p, const unsigned long long* cand, size_t cand_stride, int limit,
+    const int* cand_count, const unsigned* max_coord, float iou_thr, int max_keep, float* dets, long long* labels, int* counts,
     int* exhausted, int* keep_rank) {
   __shared__ float k_box[kMaxKeep][4];  // class-shifted coordinates
   __shared__ float k_area[kMaxKeep];
@@ -386,13 +399,10 @@ __global__ __launch_bounds__(kNmsThreads) void infer_nms_kernel(
       const unsigned pidx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
       const int slot = (int)(pidx / (unsigned)p.C);
       label = (int)(pidx - (unsigned)slot * (unsigned)p.C);
-      const float* bo = boxes + ((size_t)n * p.Ktot + slot) * 4;
+      p.box(n, slot, ob);
       const float off = (float)label * shift_unit;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        ob[k] = bo[k];
-        sb[k] = ob[k] + off;
-      }
+      for (int k = 0; k < 4; ++k) sb[k] = ob[k] + off;
       area = (sb[2] - sb[0]) * (sb[3] - sb[1]);
       // against everything kept so far
       const int nk = s_nkept;
@@ -468,9 +478,9 @@ __global__ __launch_bounds__(kNmsThreads) void infer_nms_kernel(
 //          candidate still enters with the factor exp(-40), as in the
 //          reference's dense matrix product.
 // One workgroup per (kept box, image); fp32 sums like torch.mm / sum.
+template <class Src>
 __global__ __launch_bounds__(256) void infer_vote_kernel(
-    Plan p, const unsigned long long* cand, const int* cand_count, const float* boxes,
-    int max_keep, const int* counts, const int* keep_rank, float* dets) {
+    Src p, const unsigned long long* cand, const int* cand_count, int max_keep, const int* counts, const int* keep_rank, float* dets) {
   __shared__ float red[5][256];
   const int n = blockIdx.y, q = blockIdx.x, t = threadIdx.x;
   if (q >= counts[n]) return;
@@ -482,13 +492,10 @@ __global__ __launch_bounds__(256) void infer_vote_kernel(
     const unsigned pidx = 0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull);
     const int slot = (int)(pidx / (unsigned)p.C);
     label = (int)(pidx - (unsigned)slot * (unsigned)p.C);
-    const float* bo = boxes + ((size_t)n * p.Ktot + slot) * 4;
+    p.box(n, slot, ob);
     const float off = (float)label * 4000.0f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      ob[k] = bo[k];
-      sb[k] = ob[k] + off;
-    }
+    for (int k = 0; k < 4; ++k) sb[k] = ob[k] + off;
   };
   const int ri = keep_rank[(size_t)n * max_keep + q];
   float iob[4], isb[4], isc;
@@ -605,6 +612,65 @@ extern "C" size_t ld_get_bboxes_ex_workspace_bytes(const ld_geom_t* g, int num_c
   return layout(p).total;
 }
 
+// Stages 4-6 over a filled candidate list (keys slot * C + class, count and
+// boxes.max() per image): the fast path over the kSelN best candidates, the
+// full sort when it runs out (or for voting), greedy NMS, score voting.
+template <class Src>
+static int nms_tail(const Src& src, int N, unsigned long long* cand,
+                    unsigned long long* cand_top, const int* count,
+                    const unsigned* maxc, int* flags, int* rank, float iou_thr,
+                    int max_per_img, bool voting, bool force_global, float* dets,
+                    int64_t* labels, int32_t* counts, hipStream_t stream) {
+  hipError_t err;
+  bool need_global = force_global;
+  if (!force_global) {
+    // fast path: NMS over the kSelN best candidates of every image
+    LD_LAUNCH(infer_cand_select_kernel, dim3(N), dim3(kSortThreads), 0,
+                       stream, src.cand_cap, cand, count, cand_top);
+    int limit = kSelN;  // LD_INFER_LIMIT: test hook to provoke the fallback
+    if (const char* lim = getenv("LD_INFER_LIMIT")) {
+      const int v = atoi(lim);
+      if (v >= 1 && v <= kSelN) limit = v;
+    }
+    LD_LAUNCH(infer_nms_kernel<false, Src>, dim3(N), dim3(kNmsThreads), 0, stream,
+                       src, cand_top, (size_t)kSelN, limit, count, maxc, iou_thr,
+                       max_per_img, dets, (long long*)labels, counts, flags,
+                       (int*)nullptr);
+    // rare: the best kSelN ran out before max_per_img detections -> redo the
+    // NMS over the fully sorted list (the caller reads `counts` next anyway)
+    int host_flags[64];
+    if (N > 64) {
+      need_global = true;
+    } else {
+      if ((err = hipMemcpyAsync(host_flags, flags, (size_t)N * sizeof(int),
+                                hipMemcpyDeviceToHost, stream)))
+        return (int)err;
+      if ((err = hipStreamSynchronize(stream))) return (int)err;
+      for (int n = 0; n < N; ++n)
+        if (host_flags[n]) need_global = true;
+    }
+  }
+  if (need_global) {
+    LD_LAUNCH(infer_cand_sort_kernel, dim3(N), dim3(kSortThreads), 0, stream,
+                       src.cand_cap, cand, count);
+    if (voting) {
+      LD_LAUNCH(infer_nms_kernel<true, Src>, dim3(N), dim3(kNmsThreads), 0, stream,
+                         src, cand, (size_t)src.cand_cap, src.cand_cap, count, maxc,
+                         iou_thr, max_per_img, dets, (long long*)labels, counts,
+                         (int*)nullptr, rank);
+      LD_LAUNCH(infer_vote_kernel<Src>, dim3(max_per_img, N), dim3(256), 0, stream,
+                         src, cand, count, max_per_img, counts, rank, dets);
+    } else {
+      LD_LAUNCH(infer_nms_kernel<false, Src>, dim3(N), dim3(kNmsThreads), 0,
+                         stream, src, cand, (size_t)src.cand_cap, src.cand_cap, count,
+                         maxc, iou_thr, max_per_img, dets, (long long*)labels, counts,
+                         (int*)nullptr, (int*)nullptr);
+    }
+  }
+  return (int)hipGetLastError();
+}
+
+
 static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
                            const ld_maps_t* reg, int num_classes, int reg_max,
                            const float* img_hw, const float* scale_factors,
@@ -682,53 +748,10 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
       return (int)err;
     return (int)hipGetLastError();
   }
-  bool need_global = force_global;
-  if (!force_global) {
-    // fast path: NMS over the kSelN best candidates of every image
-    LD_LAUNCH(infer_cand_select_kernel, dim3(p.N), dim3(kSortThreads), 0,
-                       stream, p, cand, count, cand_top);
-    int limit = kSelN;  // LD_INFER_LIMIT: test hook to provoke the fallback
-    if (const char* lim = getenv("LD_INFER_LIMIT")) {
-      const int v = atoi(lim);
-      if (v >= 1 && v <= kSelN) limit = v;
-    }
-    LD_LAUNCH(infer_nms_kernel<false>, dim3(p.N), dim3(kNmsThreads), 0, stream,
-                       p, cand_top, (size_t)kSelN, limit, count, maxc, boxes, iou_thr,
-                       max_per_img, dets, (long long*)labels, counts, flags,
-                       (int*)nullptr);
-    // rare: the best kSelN ran out before max_per_img detections -> redo the
-    // NMS over the fully sorted list (the caller reads `counts` next anyway)
-    int host_flags[64];
-    if (p.N > 64) {
-      need_global = true;
-    } else {
-      if ((err = hipMemcpyAsync(host_flags, flags, (size_t)p.N * sizeof(int),
-                                hipMemcpyDeviceToHost, stream)))
-        return (int)err;
-      if ((err = hipStreamSynchronize(stream))) return (int)err;
-      for (int n = 0; n < p.N; ++n)
-        if (host_flags[n]) need_global = true;
-    }
-  }
-  if (need_global) {
-    LD_LAUNCH(infer_cand_sort_kernel, dim3(p.N), dim3(kSortThreads), 0, stream,
-                       p, cand, count);
-    if (voting) {
-      int* rank = (int*)(ws + o.rank);
-      LD_LAUNCH(infer_nms_kernel<true>, dim3(p.N), dim3(kNmsThreads), 0, stream,
-                         p, cand, (size_t)p.cand_cap, p.cand_cap, count, maxc, boxes,
-                         iou_thr, max_per_img, dets, (long long*)labels, counts,
-                         (int*)nullptr, rank);
-      LD_LAUNCH(infer_vote_kernel, dim3(max_per_img, p.N), dim3(256), 0, stream,
-                         p, cand, count, boxes, max_per_img, counts, rank, dets);
-    } else {
-      LD_LAUNCH(infer_nms_kernel<false>, dim3(p.N), dim3(kNmsThreads), 0,
-                         stream, p, cand, (size_t)p.cand_cap, p.cand_cap, count, maxc,
-                         boxes, iou_thr, max_per_img, dets, (long long*)labels, counts,
-                         (int*)nullptr, (int*)nullptr);
-    }
-  }
-  return (int)hipGetLastError();
+  MapBoxes src{p.C, p.cand_cap, p.Ktot, boxes};
+  return nms_tail(src, p.N, cand, cand_top, count, maxc, flags, (int*)(ws + o.rank),
+                  iou_thr, max_per_img, voting, force_global, dets, labels, counts,
+                  stream);
 }
 
 extern "C" int ld_get_bboxes(const ld_geom_t* g, const ld_maps_t* cls,
@@ -791,4 +814,212 @@ extern "C" int ld_get_bboxes_pre_nms(const ld_geom_t* g, const ld_maps_t* cls,
                          nms_pre, 0.0f, 0.5f, 1, nullptr, nullptr, nullptr, workspace,
                          workspace_bytes, stream, false, (flags & LD_INFER_PROB) != 0, ctr,
                          (flags & LD_INFER_POINTS) != 0, num_base, boxes, scores, factors);
+}
+
+// ---- test-time augmentation: merge the views, then multiclass_nms ----------------
+// BBoxTestMixin.aug_test_bboxes (dense_test_mixins.py:38-100): every view's
+// get_bboxes(rescale=False, with_nms=False) rows are mapped back to the original
+// image (bbox_mapping_back, transforms.py:40-55: bbox_flip in fp32, then a true
+// division by the view's scale_factor), concatenated view-major
+// (merge_aug_bboxes) and handed to multiclass_nms with the concatenated score
+// factors.  The merged (M, C) set is never materialised: one pass builds the
+// candidate keys (row * C + class, row = view offset + view row) straight from
+// the views, and the NMS / voting stages map a candidate's box back again when
+// they read it (the same fp32 operations, so the same bits).
+namespace {
+
+struct AugBoxes {
+  int C, cand_cap, V;
+  int off[LD_MAX_AUG_VIEWS + 1];  // first merged row of each view; off[V] = M
+  const float* boxes[LD_MAX_AUG_VIEWS];
+  const float* scores[LD_MAX_AUG_VIEWS];
+  const float* factors[LD_MAX_AUG_VIEWS];
+  int score_stride[LD_MAX_AUG_VIEWS];
+  int flip[LD_MAX_AUG_VIEWS];
+  float h[LD_MAX_AUG_VIEWS], w[LD_MAX_AUG_VIEWS];
+  float sf[LD_MAX_AUG_VIEWS][4];
+
+  __device__ __forceinline__ int view_of(int row) const {
+    int v = 0;
+    for (int i = 1; i < V; ++i)
+      if (row >= off[i]) v = i;
+    return v;
+  }
+  // bbox_flip (transforms.py:5-30): horizontal x1' = w - x2, x2' = w - x1;
+  // vertical the same on y with h; diagonal both
+  __device__ __forceinline__ void box(int /*n*/, int row, float (&ob)[4]) const {
+    const int v = view_of(row);
+    const float* b = boxes[v] + (size_t)(row - off[v]) * 4;
+    float x1 = b[0], y1 = b[1], x2 = b[2], y2 = b[3];
+    if (flip[v] & LD_FLIP_HORIZONTAL) {
+      const float a = w[v] - x2, c = w[v] - x1;
+      x1 = a;
+      x2 = c;
+    }
+    if (flip[v] & LD_FLIP_VERTICAL) {
+      const float a = h[v] - y2, c = h[v] - y1;
+      y1 = a;
+      y2 = c;
+    }
+    ob[0] = x1 / sf[v][0];
+    ob[1] = y1 / sf[v][1];
+    ob[2] = x2 / sf[v][2];
+    ob[3] = y2 / sf[v][3];
+  }
+};
+
+// one thread per merged row: map the box back, test every class score against
+// score_thr BEFORE the factor multiplies it (bbox_nms.py:114-126), append the
+// candidates, fold the row's box into boxes.max() (batched_nms' class shift)
+__global__ __launch_bounds__(256) void aug_keys_kernel(AugBoxes s, float score_thr,
+                                                      unsigned long long* cand,
+                                                      int* cand_count,
+                                                      unsigned* max_coord) {
+  const int row = blockIdx.x * 256 + threadIdx.x;
+  if (row >= s.off[s.V]) return;
+  const int v = s.view_of(row), r = row - s.off[v];
+  const float* so = s.scores[v] + (size_t)r * s.score_stride[v];
+  const float* fp = s.factors[v];
+  const float fac = fp ? fp[r] : 1.0f;
+  bool any = false;
+  for (int c = 0; c < s.C; ++c) {
+    const float sc = so[c];
+    if (sc > score_thr) {
+      any = true;
+      const int pos = atomicAdd(cand_count, 1);
+      if (pos < s.cand_cap)
+        cand[pos] = make_key(fp ? sc * fac : sc, (unsigned)(row * s.C + c));
+    }
+  }
+  if (any) {
+    float bx[4];
+    s.box(0, row, bx);
+    const float m = fmaxf(fmaxf(bx[0], bx[1]), fmaxf(bx[2], bx[3]));
+    atomicMax(max_coord, __float_as_uint(fmaxf(m, 0.0f)));
+  }
+}
+
+// rescale=False: det_bboxes[:, :4] *= view 0's scale_factor
+// (dense_test_mixins.py:94-98)
+__global__ __launch_bounds__(256) void aug_scale_dets_kernel(const int* counts,
+                                                            float s0, float s1,
+                                                            float s2, float s3,
+                                                            float* dets) {
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= counts[0]) return;
+  float* d = dets + (size_t)q * 5;
+  d[0] *= s0;
+  d[1] *= s1;
+  d[2] *= s2;
+  d[3] *= s3;
+}
+
+struct AugOffsets {
+  size_t cand, cand_top, count, maxc, flags, rank, total;
+};
+
+int aug_plan(const ld_aug_view_t* views, int num_views, int num_classes,
+             AugBoxes* s, AugOffsets* o) {
+  if (!views || num_views < 1 || num_views > LD_MAX_AUG_VIEWS || num_classes < 1)
+    return LD_EINVAL;
+  s->C = num_classes;
+  s->V = num_views;
+  long long M = 0;
+  const bool has_fac = views[0].factors != nullptr;
+  for (int v = 0; v < num_views; ++v) {
+    const ld_aug_view_t& a = views[v];
+    if (a.K < 0 || (a.K > 0 && (!a.boxes || !a.scores))) return LD_EINVAL;
+    if (a.score_stride < num_classes) return LD_EINVAL;
+    if (a.flip < 0 || a.flip > LD_FLIP_DIAGONAL) return LD_EINVAL;
+    // merge_aug_bboxes concatenates the factors of every view or of none
+    if ((a.factors != nullptr) != has_fac) return LD_EINVAL;
+    s->off[v] = (int)M;
+    s->boxes[v] = a.boxes;
+    s->scores[v] = a.scores;
+    s->factors[v] = a.factors;
+    s->score_stride[v] = a.score_stride;
+    s->flip[v] = a.flip;
+    s->h[v] = a.img_h;
+    s->w[v] = a.img_w;
+    for (int k = 0; k < 4; ++k) s->sf[v][k] = a.scale_factor[k];
+    M += a.K;
+  }
+  for (int v = num_views; v < LD_MAX_AUG_VIEWS; ++v) {
+    s->off[v] = (int)M;
+    s->boxes[v] = s->scores[v] = s->factors[v] = nullptr;
+    s->score_stride[v] = s->flip[v] = 0;
+    s->h[v] = s->w[v] = 0.f;
+    for (int k = 0; k < 4; ++k) s->sf[v][k] = 1.f;
+  }
+  s->off[LD_MAX_AUG_VIEWS] = (int)M;
+  s->off[num_views] = (int)M;
+  const long long cap = M * num_classes;
+  if (cap > (1LL << 30)) return LD_EUNSUPPORTED;  // pair index fits 32 bits
+  s->cand_cap = next_pow2((int)(cap < 2 ? 2 : cap));
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    const size_t r = at;
+    at += (bytes + 255) / 256 * 256;
+    return r;
+  };
+  o->cand = take((size_t)s->cand_cap * 8);
+  o->cand_top = take((size_t)kSelN * 8);
+  o->count = take(sizeof(int));
+  o->maxc = take(sizeof(unsigned));
+  o->flags = take(sizeof(int));
+  o->rank = take((size_t)kMaxKeep * sizeof(int));
+  o->total = at;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t ld_aug_merge_nms_workspace_bytes(const ld_aug_view_t* views,
+                                                   int num_views, int num_classes) {
+  AugBoxes s;
+  AugOffsets o;
+  if (aug_plan(views, num_views, num_classes, &s, &o) != 0) return 0;
+  return o.total;
+}
+
+extern "C" int ld_aug_merge_nms(const ld_aug_view_t* views, int num_views,
+                                int num_classes, float score_thr, float iou_thr,
+                                int max_per_img, int flags, float* dets,
+                                int64_t* labels, int32_t* count, void* workspace,
+                                size_t workspace_bytes, ld_stream_t stream_) {
+  if (flags & ~(LD_INFER_VOTING | LD_AUG_RESCALE)) return LD_EINVAL;
+  AugBoxes s;
+  AugOffsets o;
+  if (int e = aug_plan(views, num_views, num_classes, &s, &o)) return e;
+  const bool voting = (flags & LD_INFER_VOTING) != 0;
+  // the restrictions of ld_get_bboxes_ex, refused the same way
+  if (voting && views[0].factors) return LD_EUNSUPPORTED;
+  if (max_per_img < 1 || max_per_img > kMaxKeep) return LD_EUNSUPPORTED;
+  if (!(iou_thr >= 0.0f)) return LD_EINVAL;
+  if (!dets || !labels || !count) return LD_EINVAL;
+  if (!workspace || workspace_bytes < o.total) return LD_ENOSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  char* ws = (char*)workspace;
+  unsigned long long* cand = (unsigned long long*)(ws + o.cand);
+  int* cnt = (int*)(ws + o.count);
+  unsigned* maxc = (unsigned*)(ws + o.maxc);
+  hipError_t err;
+  if ((err = ldrec::memset_async(cnt, 0, sizeof(int), stream))) return (int)err;
+  if ((err = ldrec::memset_async(maxc, 0, sizeof(unsigned), stream))) return (int)err;
+  const int M = s.off[s.V];
+  if (M > 0)
+    LD_LAUNCH(aug_keys_kernel, dim3((M + 255) / 256), dim3(256), 0, stream, s,
+              score_thr, cand, cnt, maxc);
+  const char* env = getenv("LD_INFER_SORT");
+  const bool force_global = voting || (env && env[0] == 'g');
+  if (int e = nms_tail(s, 1, cand, (unsigned long long*)(ws + o.cand_top), cnt, maxc,
+                       (int*)(ws + o.flags), (int*)(ws + o.rank), iou_thr, max_per_img,
+                       voting, force_global, dets, labels, count, stream))
+    return e;
+  if (!(flags & LD_AUG_RESCALE)) {
+    const float* f = views[0].scale_factor;
+    LD_LAUNCH(aug_scale_dets_kernel, dim3((max_per_img + 255) / 256), dim3(256), 0,
+              stream, (const int*)count, f[0], f[1], f[2], f[3], dets);
+  }
+  return (int)hipGetLastError();
 }

@@ -109,10 +109,26 @@ class SingleStageDetector(nn.Module):
         return [bbox2result(b, l, self.bbox_head.num_classes)
                 for b, l in bbox_list]
 
+    def extract_feats(self, imgs):
+        """base.py:67-71: features of every test-time view."""
+        return [self.extract_feat(img) for img in imgs]
+
     def aug_test(self, imgs, img_metas, rescale=False):
-        raise NotImplementedError('test-time augmentation (single_stage.py:'
-                                  '131-160) is not on the SURVEY.md section 8 '
-                                  'scope')
+        """single_stage.py:131-160: features of every view -> the head's
+        aug_test (per-view get_bboxes(with_nms=False) + one device merge-NMS)
+        -> ``[bbox_results]`` of the one image."""
+        if not hasattr(self.bbox_head, 'aug_test'):
+            raise NotImplementedError(
+                f'{type(self.bbox_head).__name__} does not support test-time '
+                'augmentation')
+        for img, metas in zip(imgs, img_metas):
+            if img.shape[0] != 1 or len(metas) != 1:
+                raise ValueError(
+                    'aug_test takes one image per view: the reference reads '
+                    'image 0 of each view only (dense_test_mixins.py:71), '
+                    f'got a view batch of {img.shape[0]}')
+        feats = self.extract_feats(imgs)
+        return [self.bbox_head.aug_test(feats, img_metas, rescale=rescale)]
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:120-167: outer lists = test-time augmentations."""

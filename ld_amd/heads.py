@@ -180,8 +180,56 @@ def _tower(convs, x3, levels):
     return x3
 
 
+class BBoxTestMixin:
+    """Test-time augmentation of the dense heads (anchor_head.py:729,
+    anchor_free_head.py:324 -> dense_test_mixins.py:38-100): per view the
+    head forward and get_bboxes(rescale=False, with_nms=False), then ONE
+    device call (ld_aug_merge_nms) maps every view back to the original image,
+    merges them view-major and runs multiclass_nms over the merged set."""
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        """``feats``: per view the FPN levels of ONE image; ``img_metas``: per
+        view a one-element list of metas (img_shape, scale_factor, flip,
+        flip_direction).  -> bbox2result per-class arrays of the image."""
+        from .core import bbox2result
+        cfg = self.test_cfg
+        if cfg is None:
+            raise ValueError('aug_test needs a test_cfg')
+        if len(feats) != len(img_metas):
+            raise ValueError(f'{len(feats)} views of features but '
+                             f'{len(img_metas)} of image metas')
+        get = cfg.get if hasattr(cfg, 'get') else lambda k, d=None: cfg[k]
+        nms = get('nms')
+        nms_type = nms.get('type', 'nms')
+        views = []
+        for x, metas in zip(feats, img_metas):
+            # the reference reads image 0 of every view (dense_test_mixins.py:71)
+            if len(metas) != 1:
+                raise ValueError('aug_test: one image per view (the reference '
+                                 'reads only image 0 of each view, '
+                                 'dense_test_mixins.py:71)')
+            outs = self(x)
+            res = self.get_bboxes(*outs, metas, rescale=False,
+                                  with_nms=False)[0]
+            m = metas[0]
+            views.append(dict(
+                boxes=res[0], scores=res[1],
+                factors=res[2] if len(res) > 2 else None,
+                img_shape=m['img_shape'], scale_factor=m['scale_factor'],
+                flip=m.get('flip', False),
+                flip_direction=m.get('flip_direction')))
+        voting = nms_type == 'voting_cluster_diounms'
+        if voting and views[0]['factors'] is not None:
+            raise NotImplementedError('score voting with centerness factors')
+        dets, labels = LB.aug_merge_nms(
+            views, score_thr=get('score_thr'), iou_thr=nms['iou_threshold'],
+            max_per_img=get('max_per_img'), voting=voting, rescale=rescale,
+            num_classes=self.cls_out_channels)
+        return bbox2result(dets, labels, self.num_classes)
+
+
 @HEADS.register_module()
-class GFLHead(nn.Module):
+class GFLHead(BBoxTestMixin, nn.Module):
     """Constructor = AnchorHead.__init__ (anchor_head.py:31-96) +
     GFLHead.__init__ (gfl_head.py:76-100)."""
 
@@ -757,7 +805,7 @@ INF = 1e8
 
 
 @HEADS.register_module()
-class FCOSGFLHead(nn.Module):
+class FCOSGFLHead(BBoxTestMixin, nn.Module):
     """fcos_gfl_head.py:52-346 over anchor_free_head.py:15-130: the anchor-free
     FCOS head with a general-distribution box branch.  Parameters
     ``cls_convs / reg_convs / conv_cls / conv_reg / conv_centerness / scales``
@@ -983,7 +1031,7 @@ _RETINA_ROWS = [0, 1, 3, 4, 5]
 
 
 @HEADS.register_module()
-class RetinaGFLHead(nn.Module):
+class RetinaGFLHead(BBoxTestMixin, nn.Module):
     """retina_gfl_head.py:50-330 over anchor_head.py:14-173: the RetinaNet head
     (ratios x scales anchors per cell, conv + ReLU towers without a norm
     layer) with a general-distribution box branch.  ``atss_cls`` /

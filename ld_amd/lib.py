@@ -59,6 +59,17 @@ LD_LOSS_RETINA = 16
 LD_INFER_VOTING = 1
 LD_INFER_PROB = 2
 LD_INFER_POINTS = 4
+LD_AUG_RESCALE = 8
+LD_MAX_AUG_VIEWS = 16
+LD_FLIP = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
+
+
+class AugViewT(C.Structure):
+    _fields_ = [('boxes', C.c_void_p), ('scores', C.c_void_p),
+                ('factors', C.c_void_p), ('K', C.c_int32),
+                ('score_stride', C.c_int32), ('flip', C.c_int32),
+                ('reserved', C.c_int32), ('img_h', C.c_float),
+                ('img_w', C.c_float), ('scale_factor', C.c_float * 4)]
 
 
 class ConvLevelT(C.Structure):
@@ -185,6 +196,7 @@ ABI_VERSION = 10
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
+_AV = C.POINTER(AugViewT)
 
 # name -> (restype, argtypes); kept in one table so the CPU test-suite can
 # check that every symbol include/ld_hip.h declares is exported.
@@ -274,6 +286,9 @@ SIGNATURES = {
     'ld_get_bboxes_ex': (C.c_int, [_G, _M, _M, _M, _i32, _i32, _i32, _vp, _vp, _i32, _f32,
                                    _f32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                    _vp]),
+    'ld_aug_merge_nms_workspace_bytes': (_sz, [_AV, _i32, _i32]),
+    'ld_aug_merge_nms': (C.c_int, [_AV, _i32, _i32, _f32, _f32, _i32, _i32,
+                                   _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_conv_weight_transform_batch': (C.c_int, [_vp, _vp, _i32, _vp]),
     'ld_conv_weight_transform_tiles': (C.c_int, [_i32, _i32, _i32, _i32]),
     'ld_conv_weight_transform_batch_tiled': (C.c_int, [_vp, _vp, _i32, _i32,

@@ -676,3 +676,73 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
         L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_get_bboxes_ex')
     ks = counts.cpu().tolist()  # the one sync of the call
     return [(dets[n, :k], labels[n, :k]) for n, k in enumerate(ks)]
+
+
+def aug_merge_nms(views, score_thr=0.05, iou_thr=0.6, max_per_img=100,
+                  voting=False, rescale=False, num_classes=None):
+    """BBoxTestMixin.aug_test_bboxes after the per-view get_bboxes: map every
+    view's rows back to the original image, merge them view-major and run
+    multiclass_nms over the merged set, on the device (ld_aug_merge_nms).
+
+    ``views``: one dict per view with ``boxes`` (K, 4), ``scores`` (K, >= C)
+    (a padded background column is ignored when ``num_classes`` says so),
+    optional ``factors`` (K,), ``img_shape`` (h, w[, c]), ``scale_factor`` (4
+    values), ``flip`` and ``flip_direction`` as the image metas carry them.
+    ``rescale=False`` multiplies the result by view 0's scale_factor.
+    -> (dets (k, 5), labels (k,)) device tensors."""
+    lib = L.get_lib()
+    V = len(views)
+    if not 1 <= V <= L.LD_MAX_AUG_VIEWS:
+        raise L.LdError(f'aug_merge_nms: {V} views (1..{L.LD_MAX_AUG_VIEWS})')
+    dev = views[0]['boxes'].device
+    C_ = int(num_classes or views[0]['scores'].shape[1])
+    arr = (L.AugViewT * V)()
+    keep = []  # the tensors the descriptors point at
+    for v, view in enumerate(views):
+        boxes, scores = view['boxes'], view['scores']
+        fac = view.get('factors')
+        L.require_device(boxes, torch.float32)
+        L.require_device(scores, torch.float32)
+        boxes = boxes.contiguous()
+        if scores.stride(1) != 1 or scores.shape[1] < C_:
+            scores = scores.contiguous()
+        if scores.shape[1] < C_ or boxes.shape[0] != scores.shape[0]:
+            raise L.LdError('aug_merge_nms: boxes (K, 4) / scores (K, C) '
+                            'do not match')
+        if fac is not None:
+            L.require_device(fac, torch.float32)
+            fac = fac.contiguous()
+        flip = L.LD_FLIP[view.get('flip_direction')] if view.get('flip') \
+            else 0
+        if view.get('flip') and flip == 0:
+            raise L.LdError('aug_merge_nms: flip=True needs a flip_direction')
+        a = arr[v]
+        a.boxes, a.scores = L.ptr(boxes).value, L.ptr(scores).value
+        a.factors = L.ptr(fac).value if fac is not None else None
+        a.K, a.flip = int(boxes.shape[0]), flip
+        a.score_stride = int(scores.stride(0)) if scores.shape[0] > 1 \
+            else int(scores.shape[1])
+        a.img_h, a.img_w = float(view['img_shape'][0]), \
+            float(view['img_shape'][1])
+        sf = [float(x) for x in torch.as_tensor(
+            view['scale_factor'], dtype=torch.float32).reshape(-1).tolist()]
+        if len(sf) == 1:
+            sf = sf * 4
+        for k in range(4):
+            a.scale_factor[k] = sf[k]
+        keep += [boxes, scores, fac]
+    need = lib.ld_aug_merge_nms_workspace_bytes(arr, V, C_)
+    if need == 0:
+        raise L.LdError('aug_merge_nms: bad view descriptors')
+    ws = workspace(dev, need, 'aug_nms')
+    dets = torch.empty((max_per_img, 5), dtype=torch.float32, device=dev)
+    labels = torch.empty((max_per_img, ), dtype=torch.int64, device=dev)
+    count = torch.empty((1, ), dtype=torch.int32, device=dev)
+    flags = (L.LD_INFER_VOTING if voting else 0) | \
+        (L.LD_AUG_RESCALE if rescale else 0)
+    L.check(lib.ld_aug_merge_nms(
+        arr, V, C_, float(score_thr), float(iou_thr), int(max_per_img), flags,
+        L.ptr(dets), L.ptr(labels), L.ptr(count), L.ptr(ws), ws.numel(),
+        L.stream_ptr(dev)), 'ld_aug_merge_nms')
+    k = int(count.item())
+    return dets[:k], labels[:k]

@@ -159,6 +159,96 @@ class DevicePipeline:
                 raise NotImplementedError(f'pipeline step {t}')
         return cls(device=device, **kw)
 
+    @classmethod
+    def from_test_cfg(cls, test_pipeline, device=None):
+        """Build from a reference config's ``test_pipeline``: the
+        MultiScaleFlipAug entry (test_time_aug.py:9-112) and its inner Resize /
+        RandomFlip / Normalize / Pad.  The views ``aug_views`` expands an image
+        into are its img_scale list x [(no flip)] + the flip directions.  The
+        device pixel path flips horizontally only."""
+        aug = None
+        for step in test_pipeline:
+            t = step['type']
+            if t == 'MultiScaleFlipAug':
+                aug = step
+            elif t != 'LoadImageFromFile':
+                raise NotImplementedError(f'test pipeline step {t}')
+        if aug is None:
+            raise NotImplementedError('test_pipeline without MultiScaleFlipAug')
+        if aug.get('img_scale') is None:
+            raise NotImplementedError('MultiScaleFlipAug(scale_factor=...): '
+                                      'no configs/ld test pipeline uses it')
+        scales = aug['img_scale']
+        scales = [tuple(x) for x in (scales if isinstance(scales, list)
+                                     else [scales])]
+        flip = bool(aug.get('flip', False))
+        dirs = aug.get('flip_direction', 'horizontal')
+        dirs = list(dirs) if isinstance(dirs, list) else [dirs]
+        if flip and any(d != 'horizontal' for d in dirs):
+            raise NotImplementedError(
+                f'flip_direction {dirs}: the device pipeline flips '
+                'horizontally only')
+        kw = {}
+        for step in aug.get('transforms', []):
+            t = step['type']
+            if t == 'Resize':
+                kw['keep_ratio'] = step.get('keep_ratio', True)
+            elif t == 'Normalize':
+                kw['mean'], kw['std'] = step['mean'], step['std']
+                kw['to_rgb'] = step.get('to_rgb', True)
+            elif t == 'Pad':
+                kw['size_divisor'] = step.get('size_divisor')
+            elif t not in ('RandomFlip', 'ImageToTensor', 'DefaultFormatBundle',
+                           'Collect'):
+                raise NotImplementedError(f'test pipeline step {t}')
+        self = cls(img_scale=scales[0], flip_ratio=0.0, device=device, **kw)
+        self.aug_scales = scales
+        self.aug_flips = [(False, None)] + \
+            ([(True, d) for d in dirs] if flip else [])
+        return self
+
+    def view_plans(self, shape):
+        """MultiScaleFlipAug.__call__ order (test_time_aug.py:96-106): scale
+        major, then (no flip), then each flip direction; one plan per view of
+        an image of ``shape`` (h, w)."""
+        h, w = shape
+        scales = getattr(self, 'aug_scales', [tuple(self.img_scale)])
+        flips = getattr(self, 'aug_flips', [(False, None)])
+        plans = []
+        for scale in scales:
+            new_w, new_h = rescale_size((w, h), tuple(scale))
+            sf = np.array([new_w / w, new_h / h, new_w / w, new_h / h],
+                          np.float32)
+            for flip, direction in flips:
+                if flip and direction != 'horizontal':
+                    raise NotImplementedError(
+                        f'flip_direction {direction!r}: the device pipeline '
+                        'flips horizontally only')
+                plans.append(dict(ori_shape=(h, w, 3),
+                                  img_shape=(new_h, new_w, 3),
+                                  scale_factor=sf, flip=flip,
+                                  flip_direction=direction,
+                                  scale=tuple(scale)))
+        return plans
+
+    def aug_views(self, image, stream=None):
+        """One decoded image -> the test-time views, in ONE ld_preprocess_batch
+        launch (one descriptor per view).  Returns ``(imgs, img_metas)`` as
+        ``forward_test`` takes them: per view a (1, 3, Hpad_v, Wpad_v) tensor
+        padded to its own size_divisor multiple, and a one-element meta list
+        (ori_shape, img_shape, pad_shape, scale_factor, flip,
+        flip_direction)."""
+        plans = self.view_plans(tuple(image.shape[:2]))
+        res = self([image] * len(plans), plans=plans, stream=stream)
+        imgs, metas = [], []
+        for v, (p, m) in enumerate(zip(plans, res['img_metas'])):
+            ph, pw = m['pad_shape'][:2]
+            imgs.append(res['img'][v:v + 1, :, :ph, :pw].contiguous())
+            m['flip_direction'] = p['flip_direction']
+            m['scale'] = p['scale']
+            metas.append([m])
+        return imgs, metas
+
     # -- per-image host decisions -------------------------------------------
     def plan(self, shapes, rng=np.random):
         """For each (h, w): the scale, the resized size, scale_factor and the

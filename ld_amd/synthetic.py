@@ -373,3 +373,71 @@ def infer_inputs_retina(case, device='cpu'):
                   scale_factor=np.array(f, dtype=np.float32))
              for s_, f in zip(img_shapes, sfs)]
     return cls, reg, metas
+
+
+# ---------------------------------------------------------------------------
+# test-time augmentation (BBoxTestMixin.aug_test_bboxes, tests/golden/augtest.npz)
+# ---------------------------------------------------------------------------
+# name, head kind, views, seed, nms_pre, cls_scale, cls_shift, nms type, store.
+# A view is (pad, img_shape, scale factor, flip, flip_direction): the image is
+# one original picture seen at the view's scale, so that img_shape = round(
+# original * scale_factor).  Every view gets its own seeded head maps.
+_HFLIP = [((128, 160), (128, 160, 3), 1.0, False, None),
+          ((128, 160), (128, 160, 3), 1.0, True, 'horizontal')]
+AUG_CASES = [
+    ('gfl_small', 'gfl', _HFLIP, 71, 1000, 1.25, -1.0, 'nms', True),
+    ('gfl_split', 'gfl',
+     [((640, 1024), (600, 1000, 3), 1.25, False, None),
+      ((640, 1024), (600, 1000, 3), 1.25, True, 'horizontal'),
+      ((320, 512), (300, 500, 3), 0.625, False, None),
+      ((320, 512), (300, 500, 3), 0.625, True, 'horizontal')],
+     72, 1000, 1.0, 0.0, 'nms', False),
+    ('gfl_flips', 'gfl',
+     [((128, 160), (120, 150, 3), 1.25, False, None),
+      ((128, 160), (120, 150, 3), 1.25, True, 'horizontal'),
+      ((128, 160), (120, 150, 3), 1.25, True, 'vertical'),
+      ((128, 160), (120, 150, 3), 1.25, True, 'diagonal')],
+     73, 50, 1.25, -1.0, 'nms', True),
+    ('gfl_voting', 'gfl_clustered', _HFLIP, 74, 1000, 1.0, 0.0,
+     'voting_cluster_diounms', True),
+    ('atss_small', 'atss', _HFLIP, 75, 1000, 1.25, -1.0, 'nms', True),
+    ('fcos_small', 'fcos', _HFLIP, 76, 1000, 1.25, -1.0, 'nms', True),
+    ('v2_small', 'v2', _HFLIP, 77, 1000, 1.25, -1.0, 'nms', True),
+    ('retina_small', 'retina', _HFLIP, 78, 1000, 1.25, -1.0, 'nms', True),
+]
+
+
+def aug_view_outs(case, v, device='cpu'):
+    """The head outputs (the tuple the head's forward returns) of view ``v`` of
+    an AUG_CASES row, for one image."""
+    name, kind, views, seed, nms_pre, cs, sh, nms_type, store = case
+    pad = views[v][0]
+    sizes = level_shapes(pad)
+    vs = seed * 100 + v
+    if kind == 'gfl_clustered':
+        cls, reg = infer_inputs_clustered(pad, 1, vs, device)
+        return cls, reg
+    hi = synthetic_head_inputs(1, sizes, seed=vs,
+                               num_classes=81 if kind == 'v2' else 80,
+                               num_anchors=9 if kind == 'retina' else 1)
+    cls = [c * cs + sh for c in hi['cls']]
+    if kind == 'v2':
+        cls = [torch.sigmoid(c) for c in cls]
+    out = ([c.to(device) for c in cls], [r.to(device) for r in hi['reg']])
+    if kind in ('atss', 'fcos'):
+        out += (synthetic_centerness(1, sizes, seed=vs, device=device), )
+    if kind == 'v2':
+        out += (None, )  # GFocalHead's cls_feat slot
+    return out
+
+
+def aug_view_metas(case):
+    """img_metas (outer list = views, inner = the one image) of an AUG_CASES
+    row, with the keys bbox_mapping_back reads."""
+    import numpy as np
+    metas = []
+    for pad, shape, sf, flip, direction in case[2]:
+        metas.append([dict(img_shape=shape, pad_shape=tuple(pad) + (3, ),
+                           scale_factor=np.array([sf] * 4, dtype=np.float32),
+                           flip=flip, flip_direction=direction)])
+    return metas
