@@ -1133,6 +1133,55 @@ int ld_aug_merge_nms(const ld_aug_view_t* views, int num_views, int num_classes,
                      float* dets, int64_t* labels, int32_t* count, void* workspace,
                      size_t workspace_bytes, ld_stream_t stream);
 
+/* ---- detection mAP evaluation (eval.hip) ----------------------------------
+ * eval_map of the reference (core/evaluation/mean_ap.py) on the device.  One
+ * batch of images: detections (n, 5) [x1 y1 x2 y2 score] with int64 labels, GTs
+ * (g, 4) and ignored GTs (k, 4) with int64 labels, packed image after image;
+ * *_off are DEVICE int32 arrays of num_imgs + 1 offsets.  All boxes fp32. */
+#define LD_EVAL_MAX_SCALES 16
+#define LD_EVAL_MAX_THRS 16
+#define LD_EVAL_11POINTS 1 /* ld_eval_ap flags: average_precision '11points' */
+typedef struct {
+  const float* dets;
+  const int64_t* det_labels;
+  const int32_t* det_off;
+  const float* gts;
+  const int64_t* gt_labels;
+  const int32_t* gt_off;
+  const float* ign;
+  const int64_t* ign_labels;
+  const int32_t* ign_off;
+  int32_t num_imgs, num_dets, num_gts, num_ign;
+} ld_eval_batch_t;
+
+/* tpfp_default for every (image, class), IoU threshold and area range of the
+ * batch.  area_ranges: HOST fp32 [lo0, hi0, lo1, hi1, ...] (areas, i.e. the
+ * squared scale bounds) or NULL for no range (num_scales must then be 1);
+ * iou_thrs: HOST fp32, num_thrs <= LD_EVAL_MAX_THRS.  Writes num_dets * num_thrs
+ * records, record d * num_thrs + t for detection d: the score, the segment
+ * t * num_classes + label (num_thrs * num_classes for a label outside
+ * [0, num_classes)), and bits: TP of scale k = bit k, FP = bit 16 + k.  Adds
+ * the counted GTs of each (class, scale) to num_gts[class * num_scales + k]
+ * (device int32, atomics: accumulate batches into one buffer). */
+size_t ld_eval_tpfp_workspace_bytes(int num_dets);
+int ld_eval_tpfp(const ld_eval_batch_t* batch, int num_classes, int num_scales,
+                 const float* area_ranges, int num_thrs, const float* iou_thrs,
+                 float* rec_score, int32_t* rec_seg, uint32_t* rec_bits, int32_t* num_gts,
+                 void* workspace, size_t workspace_bytes, ld_stream_t stream);
+
+/* Finalize every (threshold, class) segment of the records of all batches, in
+ * the order they were written: stable sort by descending score, cumulative TP /
+ * FP, recall (float64) and precision (fp32) into recall / precision
+ * [num_scales][num_records] in sorted order, segment s = records
+ * [seg_start[s], seg_start[s + 1]) (num_thrs * num_classes + 1 entries), and
+ * ap[s * num_scales + k] ('area', or '11points' with LD_EVAL_11POINTS). */
+size_t ld_eval_ap_workspace_bytes(int num_records, int num_scales);
+int ld_eval_ap(int num_records, const float* rec_score, const int32_t* rec_seg,
+               const uint32_t* rec_bits, int num_classes, int num_thrs, int num_scales,
+               const int32_t* num_gts, int flags, int32_t* seg_start, double* recall,
+               float* precision, float* ap, void* workspace, size_t workspace_bytes,
+               ld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,5 +26,6 @@ from .lib import LdError  # noqa: F401
 from . import core, losses, resnet, fpn, heads, detectors  # noqa: F401,E402
 from .registry import (build_backbone, build_detector, build_head,  # noqa
                        build_loss, build_neck)
+from .evaluation import MapAccumulator, eval_map  # noqa: F401,E402
 
 __version__ = '0.1.0'

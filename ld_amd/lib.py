@@ -72,6 +72,21 @@ class AugViewT(C.Structure):
                 ('img_w', C.c_float), ('scale_factor', C.c_float * 4)]
 
 
+LD_EVAL_MAX_SCALES = 16
+LD_EVAL_MAX_THRS = 16
+LD_EVAL_11POINTS = 1
+
+
+class EvalBatchT(C.Structure):
+    _fields_ = [('dets', C.c_void_p), ('det_labels', C.c_void_p),
+                ('det_off', C.c_void_p), ('gts', C.c_void_p),
+                ('gt_labels', C.c_void_p), ('gt_off', C.c_void_p),
+                ('ign', C.c_void_p), ('ign_labels', C.c_void_p),
+                ('ign_off', C.c_void_p), ('num_imgs', C.c_int32),
+                ('num_dets', C.c_int32), ('num_gts', C.c_int32),
+                ('num_ign', C.c_int32)]
+
+
 class ConvLevelT(C.Structure):
     _fields_ = [('Hin', C.c_int32), ('Win', C.c_int32), ('Hout', C.c_int32),
                 ('Wout', C.c_int32), ('off_in', C.c_int32),
@@ -289,6 +304,12 @@ SIGNATURES = {
     'ld_aug_merge_nms_workspace_bytes': (_sz, [_AV, _i32, _i32]),
     'ld_aug_merge_nms': (C.c_int, [_AV, _i32, _i32, _f32, _f32, _i32, _i32,
                                    _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ld_eval_tpfp_workspace_bytes': (_sz, [_i32]),
+    'ld_eval_tpfp': (C.c_int, [C.POINTER(EvalBatchT), _i32, _i32, _vp, _i32,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ld_eval_ap_workspace_bytes': (_sz, [_i32, _i32]),
+    'ld_eval_ap': (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32,
+                             _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_conv_weight_transform_batch': (C.c_int, [_vp, _vp, _i32, _vp]),
     'ld_conv_weight_transform_tiles': (C.c_int, [_i32, _i32, _i32, _i32]),
     'ld_conv_weight_transform_batch_tiled': (C.c_int, [_vp, _vp, _i32, _i32,

@@ -22,6 +22,7 @@ import math
 import zlib
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 __all__ = ['synthetic_batch', 'seeded_state_dict', 'synthetic_head_inputs']
@@ -441,3 +442,120 @@ def aug_view_metas(case):
                            scale_factor=np.array([sf] * 4, dtype=np.float32),
                            flip=flip, flip_direction=direction)])
     return metas
+
+
+# ---------------------------------------------------------------- eval_map ----
+# (name, seed, num_imgs, num_classes, scale_ranges, ignored GTs, empty cases,
+#  hand-made boundary image).  Scores are a permutation of distinct fp32
+#  values: tie-free inside every class, so the reference's unstable argsort
+#  has one answer (tests/golden/eval_map.npz, tools/gen_golden_evalmap.py).
+EVAL_CASES = [
+    ('base', 11, 60, 20, None, False, False, False),
+    ('scales', 12, 40, 6, [(0, 32), (32, 96), (96, 1e5)], False, False, False),
+    ('ignore', 13, 40, 5, None, True, False, False),
+    ('ignore_scales', 13, 40, 5, [(0, 48), (48, 1e5)], True, False, False),
+    ('empty', 14, 30, 8, None, False, True, False),
+    ('exact', 15, 12, 3, [(0, 32), (32, 64), (64, 1e5)], True, False, True),
+]
+# which (dataset, iou_thr) runs of eval_map each case is scored with
+EVAL_RUNS = {
+    'base': [(None, 0.5), ('voc07', 0.5), (None, 0.75), ('voc07', 0.75)],
+    'scales': [(None, 0.5), ('voc07', 0.5)],
+    'ignore': [(None, 0.5), (None, 0.75)],
+    'ignore_scales': [(None, 0.5), ('voc07', 0.5)],
+    'empty': [(None, 0.5), ('voc07', 0.5)],
+    'exact': [(None, 0.5), ('voc07', 0.5)],
+}
+
+
+def _eval_boxes(rng, n, lo=4.0, hi=150.0):
+    xy = rng.uniform(0, 400, size=(n, 2))
+    wh = rng.uniform(lo, hi, size=(n, 2))
+    return np.concatenate([xy, xy + wh], 1).astype(np.float32)
+
+
+def eval_map_inputs(case):
+    """An EVAL_CASES row -> (det_results, annotations) in the reference's form:
+    ``det_results[i][c]`` (k, 5) float32, ``annotations[i]`` with ``bboxes``
+    (n, 4) float32 / ``labels`` int64 (+ ``bboxes_ignore`` / ``labels_ignore``
+    when the case has ignored GTs)."""
+    name, seed, num_imgs, C, _, ign, empty, special = case
+    rng = np.random.RandomState(seed)
+    gt_classes = C - 3 if empty else C  # 'empty': the last 3 classes lack GTs
+    imgs = []
+    for i in range(num_imgs):
+        ngt = 0 if empty and i % 5 == 0 else rng.randint(0, 7)
+        gts = _eval_boxes(rng, ngt)
+        gl = rng.randint(0, gt_classes, size=ngt).astype(np.int64)
+        nig = rng.randint(0, 3) if ign else 0
+        igs = _eval_boxes(rng, nig)
+        il = rng.randint(0, C, size=nig).astype(np.int64)
+        rows, labs = [], []
+        for box, lab in zip(np.concatenate([gts, igs]),
+                            np.concatenate([gl, il])):
+            w, h = box[2] - box[0], box[3] - box[1]
+            for _ in range(rng.randint(0, 4)):
+                jit = rng.normal(0, 0.12, size=4) * np.array([w, h, w, h])
+                rows.append(box + jit.astype(np.float32))
+                labs.append(lab if rng.uniform() < 0.85 else
+                            rng.randint(0, C))
+        nfp = rng.randint(0, 5)
+        rows += list(_eval_boxes(rng, nfp))
+        labs += list(rng.randint(0, C, size=nfp))
+        if empty and i == 0:  # an image with neither GTs nor detections
+            gts, gl, rows, labs = gts[:0], gl[:0], [], []
+        dets = np.array(rows, dtype=np.float32).reshape(-1, 4)
+        labs = np.array(labs, dtype=np.int64)
+        if empty:  # the last class has no detections at all
+            labs[labs == C - 1] = 0
+        imgs.append([dets, labs, gts, gl, igs, il])
+    if special:
+        # fp32 IoU exactly 0.5 ([0,0,10,5] in [0,0,10,10]), and areas on the
+        # range bounds: a GT of area 32**2 and a detection of area 64**2
+        imgs.insert(0, [
+            np.array([[0, 0, 10, 5], [100, 100, 132, 132],
+                      [200, 200, 264, 264], [0, 0, 10, 5]], np.float32),
+            np.array([0, 1, 2, 1], np.int64),
+            np.array([[0, 0, 10, 10], [100, 100, 132, 132],
+                      [0, 0, 10, 10]], np.float32),
+            np.array([0, 1, 1], np.int64),
+            np.zeros((0, 4), np.float32), np.zeros((0, ), np.int64)])
+    total = sum(len(x[1]) for x in imgs)
+    scores = ((rng.permutation(total) + 1) / (total + 1)).astype(np.float32)
+    assert len(np.unique(scores)) == total
+    det_results, annotations, k = [], [], 0
+    for dets, labs, gts, gl, igs, il in imgs:
+        n = len(labs)
+        d5 = np.concatenate([dets, scores[k:k + n, None]], 1)
+        k += n
+        det_results.append([d5[labs == c] for c in range(C)])
+        ann = {'bboxes': gts, 'labels': gl}
+        if ign:
+            ann['bboxes_ignore'], ann['labels_ignore'] = igs, il
+        annotations.append(ann)
+    return det_results, annotations
+
+
+def eval_map_scale_inputs(num_imgs=4952, num_classes=20, dets_per_img=100,
+                          seed=21):
+    """VOC07-test sized input in packed form: per image (100, 5) detections
+    with labels and a few GTs.  Scores are quantised to 1/512 so that equal
+    scores are common inside a class (the stable tie rule decides)."""
+    rng = np.random.RandomState(seed)
+    ngt = rng.randint(1, 8, size=num_imgs)
+    gts = _eval_boxes(rng, int(ngt.sum()))
+    gl = rng.randint(0, num_classes, size=len(gts)).astype(np.int64)
+    goff = np.concatenate([[0], np.cumsum(ngt)])
+    N = num_imgs * dets_per_img
+    src = goff[:-1].repeat(dets_per_img) + (
+        rng.randint(0, 1 << 30, size=N) % ngt.repeat(dets_per_img))
+    box = gts[src]
+    wh = np.concatenate([box[:, 2:] - box[:, :2]] * 2, 1)
+    dets = box + (rng.normal(0, 0.2, size=(N, 4)) * wh).astype(np.float32)
+    lab = np.where(rng.uniform(size=N) < 0.7, gl[src],
+                   rng.randint(0, num_classes, size=N)).astype(np.int64)
+    score = (rng.randint(0, 512, size=N) / np.float32(512)).astype(np.float32)
+    dets = np.concatenate([dets, score[:, None]], 1).astype(np.float32)
+    return dict(dets=dets.reshape(num_imgs, dets_per_img, 5),
+                labels=lab.reshape(num_imgs, dets_per_img), gts=gts,
+                gt_labels=gl, gt_off=goff)
