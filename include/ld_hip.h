@@ -1182,6 +1182,72 @@ int ld_eval_ap(int num_records, const float* rec_score, const int32_t* rec_seg,
                float* precision, float* ap, void* workspace, size_t workspace_bytes,
                ld_stream_t stream);
 
+/* ---- COCO-style bbox evaluation (coco_eval.hip) ----------------------------
+ * pycocotools' COCOeval(iouType='bbox') evaluate() + accumulate() as mmdet's
+ * CocoDataset.evaluate runs them, float64 throughout.  Categories are indexed
+ * in sorted category-id order (the K axis), images by their position in sorted
+ * image-id order ("image rank").  One batch of images per ld_coco_match call:
+ * detections (n, 5) fp32 [x1 y1 x2 y2 score] with int64 labels, packed image
+ * after image (det_off: DEVICE int32, num_imgs + 1); img_rank: DEVICE int32 per
+ * batch image; label_cat: DEVICE int32 label -> category index or -1 (not
+ * scored).  The GTs of the whole dataset (num_all_imgs images), grouped by
+ * (image rank, category index) in annotation order: cell c = rank * num_cats
+ * + k holds GTs [gt_cell_off[c], gt_cell_off[c + 1]); xywh boxes and the json
+ * area in float64, iscrowd 0/1, annotation ids.  max_img_dets / max_cell_gts
+ * are host bounds: the most detections of one batch image, the most GTs of one
+ * cell (<= LD_COCO_MAX_CELL_GTS). */
+#define LD_COCO_MAX_THRS 16
+#define LD_COCO_MAX_AREAS 4
+#define LD_COCO_MAX_MAXDETS 4
+#define LD_COCO_MAX_REC_THRS 128
+#define LD_COCO_MAX_CELL_GTS 1024
+typedef struct {
+  const float* dets;
+  const int64_t* labels;
+  const int32_t* det_off;
+  const int32_t* img_rank;
+  const int32_t* label_cat;
+  const double* gt_box;
+  const double* gt_area;
+  const int32_t* gt_crowd;
+  const int64_t* gt_id;
+  const int32_t* gt_cell_off;
+  int32_t num_imgs, num_dets, num_labels, max_img_dets;
+  int32_t num_all_imgs, num_cats, num_gts, max_cell_gts;
+} ld_coco_batch_t;
+
+/* evaluateImg for every (batch image, category) cell, every IoU threshold and
+ * area range.  iou_thrs: HOST float64 (num_thrs), area_rng: HOST float64
+ * [lo0, hi0, lo1, hi1, ...] (num_areas), num_thrs * num_areas <= 64; max_det:
+ * maxDets[-1].  Writes one record per detection: score, category index
+ * (num_cats when the label is not scored or its rank in its cell is
+ * >= max_det), pos = image rank * max_det + rank in cell, and the 64-bit
+ * matched (dtm != 0) / ignored (dtIg) masks, bit t * num_areas + a.  Adds the
+ * non-ignored GTs of the batch images to npig[k * num_areas + a] (DEVICE int32,
+ * atomics). */
+size_t ld_coco_match_workspace_bytes(int num_dets, int max_img_dets, int max_det,
+                                     int max_cell_gts);
+int ld_coco_match(const ld_coco_batch_t* batch, int num_thrs, const double* iou_thrs,
+                  int num_areas, const double* area_rng, int max_det, float* rec_score,
+                  int32_t* rec_cat, uint32_t* rec_pos, uint64_t* rec_match,
+                  uint64_t* rec_ign, int32_t* npig, void* workspace,
+                  size_t workspace_bytes, ld_stream_t stream);
+
+/* accumulate() over the records of all batches: max_dets (HOST int32, sorted,
+ * >= 1) and rec_thrs (HOST float64, ascending).  Writes precision and scores
+ * [T][R][K][A][M] and recall [T][K][A][M] (DEVICE float64), -1 where npig is
+ * 0. */
+size_t ld_coco_accumulate_workspace_bytes(int num_records, int num_cats, int num_thrs,
+                                          int num_areas, int num_max_dets);
+int ld_coco_accumulate(int num_records, const float* rec_score, const int32_t* rec_cat,
+                       const uint32_t* rec_pos, const uint64_t* rec_match,
+                       const uint64_t* rec_ign, int num_cats, int num_all_imgs,
+                       int num_thrs, int num_areas, int num_max_dets,
+                       const int32_t* max_dets, int num_rec_thrs, const double* rec_thrs,
+                       const int32_t* npig, double* precision, double* recall,
+                       double* scores, void* workspace, size_t workspace_bytes,
+                       ld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

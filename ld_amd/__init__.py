@@ -27,5 +27,7 @@ from . import core, losses, resnet, fpn, heads, detectors  # noqa: F401,E402
 from .registry import (build_backbone, build_detector, build_head,  # noqa
                        build_loss, build_neck)
 from .evaluation import MapAccumulator, eval_map  # noqa: F401,E402
+from .coco_eval import (CocoEvaluator, CocoGroundTruth,  # noqa: F401,E402
+                        coco_evaluate)
 
 __version__ = '0.1.0'

@@ -87,6 +87,25 @@ class EvalBatchT(C.Structure):
                 ('num_ign', C.c_int32)]
 
 
+LD_COCO_MAX_THRS = 16
+LD_COCO_MAX_AREAS = 4
+LD_COCO_MAX_MAXDETS = 4
+LD_COCO_MAX_REC_THRS = 128
+LD_COCO_MAX_CELL_GTS = 1024
+
+
+class CocoBatchT(C.Structure):
+    _fields_ = [('dets', C.c_void_p), ('labels', C.c_void_p),
+                ('det_off', C.c_void_p), ('img_rank', C.c_void_p),
+                ('label_cat', C.c_void_p), ('gt_box', C.c_void_p),
+                ('gt_area', C.c_void_p), ('gt_crowd', C.c_void_p),
+                ('gt_id', C.c_void_p), ('gt_cell_off', C.c_void_p),
+                ('num_imgs', C.c_int32), ('num_dets', C.c_int32),
+                ('num_labels', C.c_int32), ('max_img_dets', C.c_int32),
+                ('num_all_imgs', C.c_int32), ('num_cats', C.c_int32),
+                ('num_gts', C.c_int32), ('max_cell_gts', C.c_int32)]
+
+
 class ConvLevelT(C.Structure):
     _fields_ = [('Hin', C.c_int32), ('Win', C.c_int32), ('Hout', C.c_int32),
                 ('Wout', C.c_int32), ('off_in', C.c_int32),
@@ -310,6 +329,15 @@ SIGNATURES = {
     'ld_eval_ap_workspace_bytes': (_sz, [_i32, _i32]),
     'ld_eval_ap': (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32,
                              _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ld_coco_match_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'ld_coco_match': (C.c_int, [C.POINTER(CocoBatchT), _i32, _vp, _i32, _vp,
+                                _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                _vp]),
+    'ld_coco_accumulate_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32,
+                                                 _i32]),
+    'ld_coco_accumulate': (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32,
+                                     _i32, _i32, _i32, _i32, _vp, _i32, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_conv_weight_transform_batch': (C.c_int, [_vp, _vp, _i32, _vp]),
     'ld_conv_weight_transform_tiles': (C.c_int, [_i32, _i32, _i32, _i32]),
     'ld_conv_weight_transform_batch_tiled': (C.c_int, [_vp, _vp, _i32, _i32,

@@ -559,3 +559,76 @@ def eval_map_scale_inputs(num_imgs=4952, num_classes=20, dets_per_img=100,
     return dict(dets=dets.reshape(num_imgs, dets_per_img, 5),
                 labels=lab.reshape(num_imgs, dets_per_img), gts=gts,
                 gt_labels=gl, gt_off=goff)
+
+
+# --------------------------------------------------------------- coco eval ----
+# (name, seed, num_imgs, category ids in file order, GTs / image, dets / GT,
+#  false positives / image, score grid (0: distinct scores), evaluate kwargs).
+#  Image and category ids are deliberately unsorted and non-contiguous; json
+#  areas differ from the box areas (segment areas); ~6% crowds
+#  (tests/golden/coco_eval.npz, tools/gen_golden_coco.py).
+COCO_CASES = [
+    ('base', 31, 40, [3, 7, 1, 12, 5], 6, 3, 4, 0, {}),
+    ('ties', 32, 30, [2, 9, 4], 5, 4, 6, 16, {}),
+    ('maxdet', 33, 12, [1, 2], 14, 4, 10, 0,
+     dict(proposal_nums=(12, 3, 8))),
+    ('thrs', 34, 25, [8, 6, 4, 0], 5, 3, 3, 0,
+     dict(iou_thrs=[0.5, 0.75, 0.6])),
+]
+
+
+def coco_eval_inputs(case):
+    """A COCO_CASES row -> (dataset, results, classes, kwargs): ``dataset`` a
+    COCO annotation dict (json-ready), ``results[i][c]`` (k, 5) float32 per
+    image (file order) and class (label c = the c-th category of the file)."""
+    name, seed, num_imgs, cat_ids, gpi, dpg, fpi, grid, kw = case
+    rng = np.random.RandomState(seed)
+    K = len(cat_ids)
+    img_ids = [int(x) for x in rng.choice(10 * num_imgs, num_imgs,
+                                          replace=False)]
+    cats = [dict(id=c, name=f'cls{c}', supercategory='x') for c in cat_ids]
+    images = [dict(id=i, width=640, height=480, file_name=f'{i}.jpg')
+              for i in img_ids]
+    anns, results, next_id = [], [], 1
+    for n, img in enumerate(img_ids):
+        ng = rng.randint(0, gpi + 1)
+        xy = rng.uniform(0, 400, size=(ng, 2))
+        wh = np.exp(rng.uniform(np.log(6), np.log(200), size=(ng, 2)))
+        labs = rng.randint(0, K, size=ng)
+        crowd = rng.uniform(size=ng) < 0.06
+        rows = [[] for _ in range(K)]
+        for g in range(ng):
+            box = [float(xy[g, 0]), float(xy[g, 1]), float(wh[g, 0]),
+                   float(wh[g, 1])]
+            anns.append(dict(id=next_id, image_id=img,
+                             category_id=cat_ids[labs[g]], bbox=box,
+                             area=float(box[2] * box[3] *
+                                        rng.uniform(0.45, 1.0)),
+                             iscrowd=int(crowd[g])))
+            next_id += 1
+            x1, y1, x2, y2 = box[0], box[1], box[0] + box[2], box[1] + box[3]
+            for _ in range(rng.randint(0, dpg + 1)):
+                j = rng.normal(0, 0.1, size=4) * [box[2], box[3], box[2],
+                                                   box[3]]
+                lab = labs[g] if rng.uniform() < 0.85 else rng.randint(0, K)
+                rows[lab].append([x1 + j[0], y1 + j[1], x2 + j[2], y2 + j[3]])
+        for _ in range(rng.randint(0, fpi + 1)):
+            x, y = rng.uniform(0, 450, size=2)
+            w, h = np.exp(rng.uniform(np.log(4), np.log(150), size=2))
+            rows[rng.randint(0, K)].append([x, y, x + w, y + h])
+        res = []
+        for c in range(K):
+            r = np.array(rows[c], np.float32).reshape(-1, 4)
+            s = rng.uniform(0.05, 1.0, size=len(r))
+            if grid:
+                s = np.round(s * grid) / grid
+            res.append(np.concatenate([r, s[:, None]], 1).astype(np.float32))
+        results.append(res)
+    if name == 'ties':
+        # annotation id 0 (a custom dataset's first id), an image without
+        # detections, a category without GTs
+        anns[0]['id'] = 0
+        results[1] = [np.zeros((0, 5), np.float32) for _ in range(K)]
+        anns = [a for a in anns if a['category_id'] != cat_ids[-1]]
+    dataset = dict(images=images, annotations=anns, categories=cats)
+    return dataset, results, [c['name'] for c in cats], dict(kw)
