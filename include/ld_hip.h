@@ -519,6 +519,11 @@ int ld_conv_tune_dgrad(const ld_conv_t* c, const float* dy, const float* wt_bwd,
 int ld_conv_tune_load(const char* path);
 int ld_conv_tune_save(const char* path);
 int ld_conv_tune_clear(void);
+/* Lookups that found the record with this 18-int key since the last
+ * ld_conv_tune_reset_hits (any launch or tune call that consulted the table);
+ * -1 if the key is not in the table, LD_EINVAL for a null key.  Host paths. */
+long long ld_conv_tune_hits(const int* key);
+int ld_conv_tune_reset_hits(void);
 /* Workspace of the plan a launch of this geometry actually follows (one size for
  * ld_conv_wgrad / ld_conv_bf16_wgrad / ld_conv_bf16_wgrad_c8).
  * ld_conv_tune_wgrad_workspace_bytes: the worst case over every candidate

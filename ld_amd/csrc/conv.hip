@@ -2133,6 +2133,9 @@ struct TuneKeyEq {
 };
 std::mutex g_tune_mu;
 std::unordered_map<LdTuneKey, LdTuneCfg, TuneKeyHash, TuneKeyEq> g_tune;
+// lookups that found each record since the last ld_conv_tune_reset_hits (read
+// by the tests that check every shipped record is reached)
+std::unordered_map<LdTuneKey, long long, TuneKeyHash, TuneKeyEq> g_tune_hits;
 }  // namespace
 
 bool ld_tune_lookup(const LdTuneKey& key, LdTuneCfg* out) {
@@ -2140,7 +2143,24 @@ bool ld_tune_lookup(const LdTuneKey& key, LdTuneCfg* out) {
   auto it = g_tune.find(key);
   if (it == g_tune.end()) return false;
   *out = it->second;
+  ++g_tune_hits[key];
   return true;
+}
+
+extern "C" long long ld_conv_tune_hits(const int* key) {
+  if (!key) return LD_EINVAL;
+  LdTuneKey k;
+  for (int i = 0; i < 18; ++i) k.v[i] = key[i];
+  std::lock_guard<std::mutex> lock(g_tune_mu);
+  if (g_tune.find(k) == g_tune.end()) return -1;
+  auto it = g_tune_hits.find(k);
+  return it == g_tune_hits.end() ? 0 : it->second;
+}
+
+extern "C" int ld_conv_tune_reset_hits(void) {
+  std::lock_guard<std::mutex> lock(g_tune_mu);
+  g_tune_hits.clear();
+  return 0;
 }
 
 void ld_tune_store(const LdTuneKey& key, const LdTuneCfg& cfg) {

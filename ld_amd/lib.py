@@ -387,6 +387,8 @@ SIGNATURES = {
     'ld_conv_tune_load': (C.c_int, [C.c_char_p]),
     'ld_conv_tune_save': (C.c_int, [C.c_char_p]),
     'ld_conv_tune_clear': (C.c_int, []),
+    'ld_conv_tune_hits': (C.c_longlong, [C.POINTER(C.c_int32)]),
+    'ld_conv_tune_reset_hits': (C.c_int, []),
     'ld_conv_wgrad_workspace_bytes': (_sz, [_CV]),
     'ld_conv_wgrad_partial': (C.c_int, [_CV, _i32, _vp, _vp, _vp, _sz,
                                         C.POINTER(WgradJobT), _vp]),
