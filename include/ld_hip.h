@@ -1238,6 +1238,48 @@ int ld_coco_match(const ld_coco_batch_t* batch, int num_thrs, const double* iou_
                   uint64_t* rec_ign, int32_t* npig, void* workspace,
                   size_t workspace_bytes, ld_stream_t stream);
 
+/* The matching of the reference's tools/analysis_tools/coco_error_analysis.py
+ * (C75 / C50 / Loc rows plus the Sim and Oth passes of
+ * analyze_individual_category).  The detection half is as ld_coco_batch_t's.
+ * The GTs are grouped by image only: image rank r holds GTs
+ * [gt_img_off[r], gt_img_off[r + 1]) in annotation order (DEVICE int32,
+ * num_all_imgs + 1), at most max_img_gts (<= LD_COCO_MAX_CELL_GTS) per image;
+ * gt_cat is each GT's category index, or -1 for a category outside the set;
+ * cat_sup (DEVICE int32, num_cats) each category's supercategory index. */
+typedef struct {
+  const float* dets;
+  const int64_t* labels;
+  const int32_t* det_off;
+  const int32_t* img_rank;
+  const int32_t* label_cat;
+  const double* gt_box;
+  const double* gt_area;
+  const int32_t* gt_crowd;
+  const int64_t* gt_id;
+  const int32_t* gt_cat;
+  const int32_t* gt_img_off;
+  const int32_t* cat_sup;
+  int32_t num_imgs, num_dets, num_labels, max_img_dets;
+  int32_t num_all_imgs, num_cats, num_gts, max_img_gts;
+} ld_coco_err_batch_t;
+
+/* ld_coco_match's records with num_thrs + 2 rows: row t < num_thrs is
+ * evaluateImg at iou_thrs[t] (HOST float64); rows num_thrs ("Sim") and
+ * num_thrs + 1 ("Oth") match at err_thr against the cell's own GTs plus the
+ * image's GTs of the other categories of the same supercategory (Sim) or of
+ * every other category (Oth), each taken as an ignored crowd GT of the cell's
+ * category.  (num_thrs + 2) * num_areas <= 64.  npig counts the own GTs only,
+ * as for ld_coco_match; ld_coco_accumulate with num_thrs + 2 thresholds then
+ * gives every row. */
+size_t ld_coco_match_errors_workspace_bytes(int num_dets, int max_img_dets, int max_det,
+                                            int max_img_gts);
+int ld_coco_match_errors(const ld_coco_err_batch_t* batch, int num_thrs,
+                         const double* iou_thrs, double err_thr, int num_areas,
+                         const double* area_rng, int max_det, float* rec_score,
+                         int32_t* rec_cat, uint32_t* rec_pos, uint64_t* rec_match,
+                         uint64_t* rec_ign, int32_t* npig, void* workspace,
+                         size_t workspace_bytes, ld_stream_t stream);
+
 /* accumulate() over the records of all batches: max_dets (HOST int32, sorted,
  * >= 1) and rec_thrs (HOST float64, ascending).  Writes precision and scores
  * [T][R][K][A][M] and recall [T][K][A][M] (DEVICE float64), -1 where npig is

@@ -29,5 +29,7 @@ from .registry import (build_backbone, build_detector, build_head,  # noqa
 from .evaluation import MapAccumulator, eval_map  # noqa: F401,E402
 from .coco_eval import (CocoEvaluator, CocoGroundTruth,  # noqa: F401,E402
                         coco_evaluate)
+from .coco_analysis import (CocoErrorAnalysis,  # noqa: F401,E402
+                            coco_error_analysis)
 
 __version__ = '0.1.0'

@@ -69,10 +69,16 @@ class CocoGroundTruth:
     cell."""
 
     def __init__(self, img_ids, cat_ids, cat_names, gt_img_ids, gt_cat_ids,
-                 boxes, areas, iscrowd, ids):
+                 boxes, areas, iscrowd, ids, supercategories=None):
         self.img_ids = [int(i) for i in img_ids]
         self.cat_ids = [int(c) for c in cat_ids]
         self.cat_names = list(cat_names)
+        # one per category (cat_ids order) or None; read by the error analysis
+        self.supercategories = None if supercategories is None else \
+            list(supercategories)
+        if self.supercategories is not None and \
+                len(self.supercategories) != len(self.cat_ids):
+            raise ValueError('CocoGroundTruth: one supercategory per category')
         if len(set(self.img_ids)) != len(self.img_ids):
             raise ValueError('CocoGroundTruth: duplicate image ids')
         self.gt_img_ids = np.asarray(gt_img_ids, np.int64).reshape(-1)
@@ -94,7 +100,8 @@ class CocoGroundTruth:
     def from_json(cls, ann_file, classes=None):
         """A COCO annotation json.  ``img_ids`` in file order (get_img_ids);
         ``cat_ids`` the categories whose name is in ``classes`` (all when
-        None), in the order of ``categories`` (get_cat_ids(cat_names=...))."""
+        None), in the order of ``categories`` (get_cat_ids(cat_names=...)).
+        ``supercategories`` when every category has one."""
         if isinstance(ann_file, dict):
             data = ann_file
         else:
@@ -107,6 +114,8 @@ class CocoGroundTruth:
             cats = [c for c in cats if c['name'] in names]
         cat_ids = [c['id'] for c in cats]
         anns = data.get('annotations', [])
+        sup = [c['supercategory'] for c in cats] \
+            if all('supercategory' in c for c in cats) else None
         return cls(img_ids, cat_ids, [c['name'] for c in cats],
                    [a['image_id'] for a in anns],
                    [a['category_id'] for a in anns],
@@ -114,14 +123,16 @@ class CocoGroundTruth:
                             np.float64).reshape(-1, 4),
                    [a['area'] for a in anns],
                    [a.get('iscrowd', 0) for a in anns],
-                   [a['id'] for a in anns])
+                   [a['id'] for a in anns], sup)
 
     @classmethod
-    def from_annotations(cls, annotations, num_classes=None, classes=None):
+    def from_annotations(cls, annotations, num_classes=None, classes=None,
+                         supercategories=None):
         """mmdet-style ``annotations[i]``: xyxy ``bboxes`` / ``labels``, and
         ``bboxes_ignore`` / ``labels_ignore`` taken as crowd GTs.  Image ids
         are 0..N-1, category ids 0..C-1, areas w * h, annotation ids from 1
-        (each image's GTs, then its crowd GTs)."""
+        (each image's GTs, then its crowd GTs).  ``supercategories``: one
+        name per class, for the error analysis."""
         if classes is not None:
             num_classes = len(classes)
         if num_classes is None:
@@ -149,7 +160,7 @@ class CocoGroundTruth:
         boxes = np.concatenate(boxes) if boxes else np.zeros((0, 4))
         return cls(range(len(annotations)), range(num_classes), names, gi, gc,
                    boxes, boxes[:, 2] * boxes[:, 3], crowd,
-                   np.arange(1, len(gi) + 1))
+                   np.arange(1, len(gi) + 1), supercategories)
 
     def _cells(self):
         """GT order grouped by (image rank, category index), stable; cell
@@ -205,7 +216,170 @@ def _f32(x, dev, last):
     return t.to(device=dev, dtype=torch.float32).reshape(-1, last)
 
 
-class CocoEvaluator:
+class _CocoStream:
+    """The streaming half that CocoEvaluator and CocoErrorAnalysis share:
+    the label map, one record per detection kept on the device, ``add`` and
+    the images never added.  A subclass sets ``gt``, ``iou_thrs``,
+    ``max_dets``, ``rec_thrs`` and ``area_rng``, calls ``_setup`` and provides
+    ``_match`` (its matching kernel over one batch)."""
+
+    def _setup(self, gt, device):
+        name = type(self).__name__
+        if len(gt.img_ids) == 0 or len(gt.cat_ids) == 0:
+            raise ValueError(f'{name}: the ground truth has no images '
+                             'or no categories')
+        self.device = torch.device(device) if device is not None else \
+            torch.device('cuda', torch.cuda.current_device())
+        if self.device.type != 'cuda':
+            raise L.LdError(f'{name}: device {self.device} is not a HIP '
+                            'device (there is no CPU path)')
+        self.num_imgs = len(gt.img_ids)
+        self.K = len(gt.sorted_cat_ids)
+        self._img_rank = np.searchsorted(gt.sorted_img_ids,
+                                         np.asarray(gt.img_ids, np.int64))
+        lut = np.searchsorted(gt.sorted_cat_ids,
+                              np.asarray(gt.cat_ids, np.int64)).astype(np.int32)
+        self._label_cat = torch.from_numpy(lut).to(self.device)
+        self.npig = torch.zeros(self.K * len(self.area_rng), dtype=torch.int32,
+                                device=self.device)
+        self._seen = np.zeros(self.num_imgs, bool)
+        self.num_dets = 0  # detection rows added (scored or not)
+        self._n = 0
+        self._buf = {}
+        for name, dt in (('score', torch.float32), ('cat', torch.int32),
+                         ('pos', torch.int32), ('match', torch.int64),
+                         ('ign', torch.int64)):
+            self._buf[name] = torch.empty(0, dtype=dt, device=self.device)
+
+    def _reserve(self, extra):
+        need = self._n + extra
+        cap = self._buf['score'].numel()
+        if need <= cap:
+            return
+        cap = max(need, 2 * cap, 1 << 12)
+        for name, old in self._buf.items():
+            new = torch.empty(cap, dtype=old.dtype, device=self.device)
+            new[:self._n] = old[:self._n]
+            self._buf[name] = new
+
+    def _pack(self, indices, dets, labels):
+        """One batch as the match kernels read it -> (dets (N, 5), labels,
+        det_off, image ranks (device), per-image counts, N)."""
+        dev = self.device
+        counts = [d.shape[0] for d in dets]
+        off = np.zeros(len(indices) + 1, np.int32)
+        off[1:] = np.cumsum(counts)
+        N = int(off[-1])
+        if N:
+            d = torch.cat(dets).contiguous()
+            lab = torch.cat(labels).contiguous()
+        else:
+            d = torch.zeros((0, 5), dtype=torch.float32, device=dev)
+            lab = torch.zeros(0, dtype=torch.int64, device=dev)
+        det_off = torch.from_numpy(off).to(dev)
+        ranks = torch.from_numpy(
+            self._img_rank[np.asarray(indices, np.int64)].astype(
+                np.int32)).to(dev)
+        return d, lab, det_off, ranks, counts, N
+
+    def add(self, indices, dets, labels):
+        """One batch: ``indices`` (dataset indices into ``gt.img_ids``) and,
+        per image, detections (n, 5) [x1 y1 x2 y2 score] with labels (n,) --
+        device tensors as ``get_bboxes`` / ``aug_test`` return them, no host
+        copy.  Label ``c`` is category ``gt.cat_ids[c]``; other labels are
+        not scored.  An image may be added once."""
+        name = type(self).__name__
+        indices = [int(i) for i in indices]
+        B = len(indices)
+        if not len(dets) == len(labels) == B:
+            raise ValueError(f'{name}.add: indices, dets and labels need '
+                             'one entry per image')
+        if B == 0:
+            return
+        ix = np.asarray(indices, np.int64)
+        if ix.min() < 0 or ix.max() >= self.num_imgs:
+            raise IndexError(f'{name}.add: image index out of range')
+        if len(np.unique(ix)) != B or self._seen[ix].any():
+            raise ValueError(f'{name}.add: an image was added twice')
+        dev = self.device
+        d = [_f32(x, dev, 5) for x in dets]
+        lab = [torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1)
+               for x in labels]
+        for x, y in zip(d, lab):
+            if x.shape[0] != y.shape[0]:
+                raise ValueError(f'{name}.add: detections and labels '
+                                 'differ in length')
+        N = sum(x.shape[0] for x in d)
+        self._reserve(N)
+        lo, hi = self._n, self._n + N
+        rec = {k: v[lo:hi] for k, v in self._buf.items()}
+        self._match(indices, d, lab, self.npig, rec)
+        self._seen[ix] = True
+        self._n = hi
+        self.num_dets += N
+
+    def records(self):
+        """The records written so far, in the order they were added (image
+        after image, detections in their input order) -> host dict of
+        ``cat`` (category index, K when not scored), ``pos`` (image rank *
+        maxDets[-1] + rank in its cell), ``score``, ``match`` / ``ign``
+        (uint64 masks, bit t * A + a)."""
+        out = {k: v[:self._n].cpu().numpy() for k, v in self._buf.items()}
+        out['pos'] = out['pos'].view(np.uint32)
+        out['match'] = out['match'].view(np.uint64)
+        out['ign'] = out['ign'].view(np.uint64)
+        return out
+
+    def _check_one_rank(self):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and \
+                dist.get_world_size() > 1:
+            raise NotImplementedError(
+                f'{type(self).__name__}.compute: results are not gathered '
+                f'across ranks (world size {dist.get_world_size()}); '
+                'evaluate on one rank, or gather the detections there first')
+
+    def _npig_all(self):
+        """npig with the images never added counted as images without
+        detections (their GTs still count)."""
+        dev = self.device
+        npig = self.npig.clone()
+        missing = np.nonzero(~self._seen)[0]
+        if len(missing):
+            empty = torch.zeros((0, 5), dtype=torch.float32, device=dev)
+            none = torch.zeros(0, dtype=torch.int64, device=dev)
+            self._match(missing.tolist(), [empty] * len(missing),
+                        [none] * len(missing), npig, None)
+        return npig
+
+    def _accumulate(self, npig, num_thrs):
+        """ld_coco_accumulate over every record -> device precision / scores
+        (T, R, K, A, M) and recall (T, K, A, M)."""
+        lib = L.get_lib()
+        dev = self.device
+        T, R, K = num_thrs, len(self.rec_thrs), self.K
+        A, M = len(self.area_rng), len(self.max_dets)
+        need = lib.ld_coco_accumulate_workspace_bytes(self._n, K, T, A, M)
+        if need == 0:
+            raise L.LdError('ld_coco_accumulate_workspace_bytes: bad sizes')
+        ws = workspace(dev, need, 'coco_accumulate')
+        precision = torch.empty((T, R, K, A, M), dtype=torch.float64,
+                                device=dev)
+        scores = torch.empty_like(precision)
+        recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+        md = (L.C.c_int32 * M)(*self.max_dets)
+        rt = (L.C.c_double * R)(*self.rec_thrs.tolist())
+        L.check(lib.ld_coco_accumulate(
+            self._n, L.ptr(self._buf['score']), L.ptr(self._buf['cat']),
+            L.ptr(self._buf['pos']), L.ptr(self._buf['match']),
+            L.ptr(self._buf['ign']), K, len(self.gt.sorted_img_ids), T, A, M,
+            L.C.cast(md, L.C.c_void_p), R, L.C.cast(rt, L.C.c_void_p),
+            L.ptr(npig), L.ptr(precision), L.ptr(recall), L.ptr(scores),
+            L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_coco_accumulate')
+        return precision, recall, scores
+
+
+class CocoEvaluator(_CocoStream):
     """Streaming COCO bbox evaluation against ``gt`` (a CocoGroundTruth):
     ``add`` batches of images, then ``compute`` / ``evaluate``.
 
@@ -232,63 +406,14 @@ class CocoEvaluator:
                 self.max_dets[0] < 1:
             raise ValueError('CocoEvaluator: proposal_nums needs 3 or 4 '
                              'positive values (summarize reads maxDets[2])')
-        if len(gt.img_ids) == 0 or len(gt.cat_ids) == 0:
-            raise ValueError('CocoEvaluator: the ground truth has no images '
-                             'or no categories')
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        if self.device.type != 'cuda':
-            raise L.LdError(f'CocoEvaluator: device {self.device} is not a HIP '
-                            'device (there is no CPU path)')
-        self.num_imgs = len(gt.img_ids)
-        self.K = len(gt.sorted_cat_ids)
+        self._setup(gt, device)
         self._g = gt.to(self.device)
-        self._img_rank = np.searchsorted(gt.sorted_img_ids,
-                                         np.asarray(gt.img_ids, np.int64))
-        lut = np.searchsorted(gt.sorted_cat_ids,
-                              np.asarray(gt.cat_ids, np.int64)).astype(np.int32)
-        self._label_cat = torch.from_numpy(lut).to(self.device)
-        self.npig = torch.zeros(self.K * A, dtype=torch.int32,
-                                device=self.device)
-        self._seen = np.zeros(self.num_imgs, bool)
-        self.num_dets = 0  # detection rows added (scored or not)
-        self._n = 0
-        self._buf = {}
-        for name, dt in (('score', torch.float32), ('cat', torch.int32),
-                         ('pos', torch.int32), ('match', torch.int64),
-                         ('ign', torch.int64)):
-            self._buf[name] = torch.empty(0, dtype=dt, device=self.device)
-
-    def _reserve(self, extra):
-        need = self._n + extra
-        cap = self._buf['score'].numel()
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap, 1 << 12)
-        for name, old in self._buf.items():
-            new = torch.empty(cap, dtype=old.dtype, device=self.device)
-            new[:self._n] = old[:self._n]
-            self._buf[name] = new
 
     def _match(self, indices, dets, labels, npig, records):
         """ld_coco_match over the images ``indices`` (dataset indices)."""
         lib = L.get_lib()
         dev, g = self.device, self._g
-        B = len(indices)
-        counts = [d.shape[0] for d in dets]
-        off = np.zeros(B + 1, np.int32)
-        off[1:] = np.cumsum(counts)
-        N = int(off[-1])
-        if N:
-            d = torch.cat(dets).contiguous()
-            lab = torch.cat(labels).contiguous()
-        else:
-            d = torch.zeros((0, 5), dtype=torch.float32, device=dev)
-            lab = torch.zeros(0, dtype=torch.int64, device=dev)
-        det_off = torch.from_numpy(off).to(dev)
-        ranks = torch.from_numpy(
-            self._img_rank[np.asarray(indices, np.int64)].astype(
-                np.int32)).to(dev)
+        d, lab, det_off, ranks, counts, N = self._pack(indices, dets, labels)
         b = L.CocoBatchT()
         b.dets, b.labels, b.det_off = L.ptr(d).value, L.ptr(lab).value, \
             L.ptr(det_off).value
@@ -297,7 +422,7 @@ class CocoEvaluator:
         b.gt_box, b.gt_area = L.ptr(g['box']).value, L.ptr(g['area']).value
         b.gt_crowd, b.gt_id = L.ptr(g['crowd']).value, L.ptr(g['id']).value
         b.gt_cell_off = L.ptr(g['cell_off']).value
-        b.num_imgs, b.num_dets = B, N
+        b.num_imgs, b.num_dets = len(indices), N
         b.num_labels = self._label_cat.numel()
         b.max_img_dets = max(counts) if counts else 0
         b.num_all_imgs, b.num_cats = len(self.gt.sorted_img_ids), self.K
@@ -319,97 +444,17 @@ class CocoEvaluator:
             L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_coco_match')
         return N
 
-    def add(self, indices, dets, labels):
-        """One batch: ``indices`` (dataset indices into ``gt.img_ids``) and,
-        per image, detections (n, 5) [x1 y1 x2 y2 score] with labels (n,) --
-        device tensors as ``get_bboxes`` / ``aug_test`` return them, no host
-        copy.  Label ``c`` is category ``gt.cat_ids[c]``; other labels are
-        not scored.  An image may be added once."""
-        indices = [int(i) for i in indices]
-        B = len(indices)
-        if not len(dets) == len(labels) == B:
-            raise ValueError('CocoEvaluator.add: indices, dets and labels need '
-                             'one entry per image')
-        if B == 0:
-            return
-        ix = np.asarray(indices, np.int64)
-        if ix.min() < 0 or ix.max() >= self.num_imgs:
-            raise IndexError('CocoEvaluator.add: image index out of range')
-        if len(np.unique(ix)) != B or self._seen[ix].any():
-            raise ValueError('CocoEvaluator.add: an image was added twice')
-        dev = self.device
-        d = [_f32(x, dev, 5) for x in dets]
-        lab = [torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1)
-               for x in labels]
-        for x, y in zip(d, lab):
-            if x.shape[0] != y.shape[0]:
-                raise ValueError('CocoEvaluator.add: detections and labels '
-                                 'differ in length')
-        N = sum(x.shape[0] for x in d)
-        self._reserve(N)
-        lo, hi = self._n, self._n + N
-        rec = {k: v[lo:hi] for k, v in self._buf.items()}
-        self._match(indices, d, lab, self.npig, rec)
-        self._seen[ix] = True
-        self._n = hi
-        self.num_dets += N
-
-    def records(self):
-        """The records written so far, in the order they were added (image
-        after image, detections in their input order) -> host dict of
-        ``cat`` (category index, K when not scored), ``pos`` (image rank *
-        maxDets[-1] + rank in its cell), ``score``, ``match`` / ``ign``
-        (uint64 masks, bit t * A + a)."""
-        out = {k: v[:self._n].cpu().numpy() for k, v in self._buf.items()}
-        out['pos'] = out['pos'].view(np.uint32)
-        out['match'] = out['match'].view(np.uint64)
-        out['ign'] = out['ign'].view(np.uint64)
-        return out
-
     def compute(self):
         """-> dict of ``precision`` / ``scores`` (T, R, K, A, M), ``recall``
         (T, K, A, M) float64 as COCOeval.accumulate leaves them in
         ``eval``, ``npig`` (K, A) and ``stats`` (12,) from summarize.  Images
         never added count as images without detections."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and \
-                dist.get_world_size() > 1:
-            raise NotImplementedError(
-                'CocoEvaluator.compute: results are not gathered across '
-                f'ranks (world size {dist.get_world_size()}); evaluate on one '
-                'rank, or gather the detections there first')
-        lib = L.get_lib()
-        dev = self.device
-        npig = self.npig.clone()
-        missing = np.nonzero(~self._seen)[0]
-        if len(missing):
-            empty = torch.zeros((0, 5), dtype=torch.float32, device=dev)
-            none = torch.zeros(0, dtype=torch.int64, device=dev)
-            self._match(missing.tolist(), [empty] * len(missing),
-                        [none] * len(missing), npig, None)
-        T, R, K = len(self.iou_thrs), len(self.rec_thrs), self.K
-        A, M = len(self.area_rng), len(self.max_dets)
-        need = lib.ld_coco_accumulate_workspace_bytes(self._n, K, T, A, M)
-        if need == 0:
-            raise L.LdError('ld_coco_accumulate_workspace_bytes: bad sizes')
-        ws = workspace(dev, need, 'coco_accumulate')
-        precision = torch.empty((T, R, K, A, M), dtype=torch.float64,
-                                device=dev)
-        scores = torch.empty_like(precision)
-        recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
-        md = (L.C.c_int32 * M)(*self.max_dets)
-        rt = (L.C.c_double * R)(*self.rec_thrs.tolist())
-        n = self._n
-        L.check(lib.ld_coco_accumulate(
-            n, L.ptr(self._buf['score']), L.ptr(self._buf['cat']),
-            L.ptr(self._buf['pos']), L.ptr(self._buf['match']),
-            L.ptr(self._buf['ign']), K, len(self.gt.sorted_img_ids), T, A, M,
-            L.C.cast(md, L.C.c_void_p), R, L.C.cast(rt, L.C.c_void_p),
-            L.ptr(npig), L.ptr(precision), L.ptr(recall), L.ptr(scores),
-            L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_coco_accumulate')
+        self._check_one_rank()
+        npig = self._npig_all()
+        precision, recall, scores = self._accumulate(npig, len(self.iou_thrs))
         out = dict(precision=precision.cpu().numpy(),
                    recall=recall.cpu().numpy(), scores=scores.cpu().numpy(),
-                   npig=npig.cpu().numpy().reshape(K, A))
+                   npig=npig.cpu().numpy().reshape(self.K, len(self.area_rng)))
         out['stats'] = summarize(out['precision'], out['recall'],
                                  self.iou_thrs, self.max_dets)
         return out

@@ -39,6 +39,23 @@
 //               precision envelope (in-tile reverse max-scan + later tiles), and
 //               the recall thresholds whose searchsorted index is this record.
 // Everything but the sort is bound by block-wide scans (one per lane and tile).
+//
+// ld_coco_match_errors (tools/analysis_tools/coco_error_analysis.py: the main
+// COCOeval pass and the two per-category passes of analyze_individual_category
+// in one match).  Same rank step, same wave64 per (image, category) cell, but
+// the GTs of a cell are the image's whole GT span in annotation order
+// (imgToAnns order, which the relabel keeps), each with its category index:
+//   rows t < T0   plain evaluateImg at iou_thrs[t]: only the cell's own GTs;
+//   row  T0       "Sim" at err_thr: own GTs + the GTs of the other categories
+//                 of the same supercategory, relabelled ignore = iscrowd = 1;
+//   row  T0 + 1   "Oth" at err_thr: own GTs + every other GT of the image,
+//                 relabelled likewise (unknown categories included).
+// A relabelled GT is a crowd (overlap = intersection / detection area, never
+// consumed) and ignored in every area range, so it leaves npig alone.  One IoU
+// tile (D x image GTs) serves every row.  Lane t * A + a writes bit t * A + a,
+// so one ld_coco_accumulate call with T0 + 2 thresholds and M = 1 gives every
+// row.  Images with more than kLdsG GTs or tiles over kLdsTile take the
+// global-tile path; more than LD_COCO_MAX_CELL_GTS GTs in an image is refused.
 #include <hip/hip_runtime.h>
 
 #include <float.h>
@@ -256,6 +273,138 @@ __global__ __launch_bounds__(kWave) void coco_match_kernel(
       }
     }
     __syncthreads();  // the next cell rewrites the tile and the flags
+  }
+}
+
+// ------------------------------------------------------ error analysis ----
+constexpr uint32_t kFlagOwn = 1u << 10;  // a GT of the cell's own category
+constexpr uint32_t kFlagSim = 1u << 11;  // another category, same supercategory
+
+// the image-major GT span of ld_coco_err_batch_t (device pointers)
+struct ErrGts {
+  const double* box;
+  const double* area;
+  const int32_t* crowd;
+  const int64_t* id;
+  const int32_t* cat;
+  const int32_t* img_off;
+  const int32_t* cat_sup;
+  int max_img_gts;
+};
+
+// As coco_match_kernel, over the image's GT span; rows t < T0 plain, T0 Sim,
+// T0 + 1 Oth (file comment).  BIG: the queued cells, one global tile per
+// workgroup.
+template <bool BIG>
+__global__ __launch_bounds__(kWave) void coco_match_errors_kernel(
+    ld_coco_batch_t b, ErrGts eg, MatchParams p, int T0, const int32_t* order,
+    int32_t* big_list, double* slots, uint64_t* rec_match, uint64_t* rec_ign,
+    int32_t* npig) {
+  constexpr int GMAX = BIG ? LD_COCO_MAX_CELL_GTS : kLdsG;
+  __shared__ double tile_s[BIG ? 1 : kLdsTile];
+  __shared__ uint32_t gfl[GMAX];
+  __shared__ uint32_t gm[GMAX / 32][kWave];
+  const int lane = threadIdx.x;
+  const int K = p.K, A = p.A;
+  const int n_cells = BIG ? big_list[0] : 1;
+  for (int e = BIG ? blockIdx.x : 0; e < n_cells; e += BIG ? gridDim.x : 1) {
+    const int cell = BIG ? big_list[1 + e] : blockIdx.x;
+    const int bi = cell / K, k = cell - bi * K;
+    const int d0 = b.det_off[bi], d1 = b.det_off[bi + 1];
+    int lt = 0, eq = 0;
+    for (int j = d0 + lane; j < d1; j += kWave) {
+      const int kj = det_cat(b, j);
+      lt += (kj >= 0 && kj < k);
+      eq += (kj == k);
+    }
+    lt = wave_sum(lt);
+    eq = wave_sum(eq);
+    const int D = min(min(eq, p.max_det), p.max_d);
+    const int ir = b.img_rank[bi];
+    const int g0 = eg.img_off[ir];
+    const int G = min(eg.img_off[ir + 1] - g0, eg.max_img_gts);
+    if (!BIG && lane < A) {
+      int c = 0;
+      for (int g = 0; g < G; ++g) {
+        if (eg.cat[g0 + g] != k) continue;
+        const double ar = eg.area[g0 + g];
+        c += !eg.crowd[g0 + g] && !(ar < p.lo[lane] || ar > p.hi[lane]);
+      }
+      if (c) atomicAdd(npig + k * A + lane, c);
+    }
+    if (D == 0) continue;
+    if (!BIG && (G > kLdsG || (long long)D * G > kLdsTile)) {
+      if (lane == 0) big_list[1 + atomicAdd(big_list, 1)] = cell;
+      continue;
+    }
+    double* tile = BIG ? slots + (size_t)blockIdx.x * p.slot_elems : tile_s;
+    const int cs = d0 + lt;
+    const int sk = eg.cat_sup[k];
+    for (int g = lane; g < G; g += kWave) {
+      const int c = eg.cat[g0 + g];
+      uint32_t f = eg.id[g0 + g] != 0 ? kFlagIdNz : 0u;
+      if (c == k) {
+        const double ar = eg.area[g0 + g];
+        const bool crowd = eg.crowd[g0 + g] != 0;
+        f |= kFlagOwn | (crowd ? kFlagCrowd : 0u);
+        for (int a = 0; a < A; ++a)
+          if (crowd || ar < p.lo[a] || ar > p.hi[a]) f |= 1u << a;
+      } else {  // relabelled: crowd, ignored in every area range
+        f |= kFlagCrowd | ((1u << A) - 1u);
+        if (c >= 0 && c < K && sk >= 0 && eg.cat_sup[c] == sk) f |= kFlagSim;
+      }
+      gfl[g] = f;
+    }
+    for (int w = 0; w < (G + 31) / 32; ++w) gm[w][lane] = 0u;
+    __syncthreads();  // gfl is read by every lane below
+    for (int idx = lane; idx < D * G; idx += kWave) {
+      const int d = idx / G, g = idx - d * G;
+      double db[4];
+      det_xywh(b.dets + (size_t)order[cs + d] * 5, db);
+      tile[idx] = bb_iou(db, eg.box + (size_t)(g0 + g) * 4, (gfl[g] & kFlagCrowd) != 0);
+    }
+    __syncthreads();
+    const bool active = lane < p.T * A;
+    const int t = active ? lane / A : 0, a = active ? lane - t * A : 0;
+    // the GTs row t sees: own only, own + Sim, or all (mem == 0)
+    const uint32_t mem = t < T0 ? kFlagOwn : (t == T0 ? (kFlagOwn | kFlagSim) : 0u);
+    const double lo = p.lo[a], hi = p.hi[a];
+    for (int d = 0; d < D; ++d) {
+      const int i = order[cs + d];
+      double db[4];
+      det_xywh(b.dets + (size_t)i * 5, db);
+      const double da = db[2] * db[3];
+      const double* row = tile + (size_t)d * G;
+      bool mbit = false, ibit = false;
+      if (active) {
+        double iou = p.iou0[t];
+        int m = -1;
+        for (int pass = 0; pass < 2 && m < 0; ++pass) {
+          for (int g = 0; g < G; ++g) {
+            const uint32_t f = gfl[g];
+            if (mem && !(f & mem)) continue;
+            if ((int)((f >> a) & 1u) != pass) continue;
+            if (((gm[g >> 5][lane] >> (g & 31)) & 1u) && !(f & kFlagCrowd)) continue;
+            const double v = row[g];
+            if (v < iou) continue;
+            iou = v;
+            m = g;
+          }
+        }
+        if (m >= 0) {
+          gm[m >> 5][lane] |= 1u << (m & 31);
+          mbit = (gfl[m] & kFlagIdNz) != 0;
+          ibit = (gfl[m] >> a) & 1u;
+        }
+        if (!mbit && (da < lo || da > hi)) ibit = true;
+      }
+      const uint64_t mb = __ballot(mbit), ib = __ballot(ibit);
+      if (lane == 0) {
+        rec_match[i] = mb;
+        rec_ign[i] = ib;
+      }
+    }
+    __syncthreads();
   }
 }
 
@@ -824,6 +973,84 @@ int ld_coco_match(const ld_coco_batch_t* b, int num_thrs, const double* iou_thrs
   if (b->num_dets > 0 && o.slots != o.total)
     LD_LAUNCH(coco_match_kernel<true>, dim3(kSlots), dim3(kWave), 0, stream, *b, p,
               (const int32_t*)order, big, slots, rec_match, rec_ign, npig);
+  return (int)hipGetLastError();
+}
+
+size_t ld_coco_match_errors_workspace_bytes(int num_dets, int max_img_dets, int max_det,
+                                            int max_img_gts) {
+  return ld_coco_match_workspace_bytes(num_dets, max_img_dets, max_det, max_img_gts);
+}
+
+int ld_coco_match_errors(const ld_coco_err_batch_t* e, int num_thrs, const double* iou_thrs,
+                         double err_thr, int num_areas, const double* area_rng, int max_det,
+                         float* rec_score, int32_t* rec_cat, uint32_t* rec_pos,
+                         uint64_t* rec_match, uint64_t* rec_ign, int32_t* npig,
+                         void* workspace, size_t workspace_bytes, ld_stream_t stream_) {
+  if (!e || !iou_thrs || !area_rng || !npig) return LD_EINVAL;
+  const int T = num_thrs + 2;  // + Sim + Oth
+  if (num_thrs < 1 || T > LD_COCO_MAX_THRS || num_areas < 1 ||
+      num_areas > LD_COCO_MAX_AREAS || T * num_areas > 64 || max_det < 1)
+    return LD_EINVAL;
+  if (e->num_imgs < 1 || e->num_dets < 0 || e->num_labels < 0 || e->max_img_dets < 0 ||
+      e->num_all_imgs < 1 || e->num_cats < 1 || e->num_gts < 0 || e->max_img_gts < 0)
+    return LD_EINVAL;
+  if (e->max_img_gts > LD_COCO_MAX_CELL_GTS) return LD_EUNSUPPORTED;
+  if ((long long)e->num_imgs * e->num_cats >= (1ll << 31) ||
+      (long long)e->num_all_imgs * max_det >= (1ll << 32))
+    return LD_EUNSUPPORTED;
+  if (!e->det_off || !e->img_rank || !e->gt_img_off || !e->cat_sup) return LD_EINVAL;
+  if (e->num_dets && (!e->dets || !e->labels || !rec_score || !rec_cat || !rec_pos ||
+                      !rec_match || !rec_ign || (e->num_labels && !e->label_cat)))
+    return LD_EINVAL;
+  if (e->num_gts && (!e->gt_box || !e->gt_area || !e->gt_crowd || !e->gt_id || !e->gt_cat))
+    return LD_EINVAL;
+  const int max_d = std::min(max_det, e->max_img_dets);
+  const MatchPlan o = match_plan(e->num_dets, max_d, e->max_img_gts);
+  if (workspace_bytes < o.total || (o.total && !workspace)) return LD_ENOSPACE;
+  MatchParams p{};
+  for (int t = 0; t < num_thrs; ++t) p.iou0[t] = std::min(iou_thrs[t], 1.0 - 1e-10);
+  p.iou0[num_thrs] = p.iou0[num_thrs + 1] = std::min(err_thr, 1.0 - 1e-10);
+  for (int a = 0; a < num_areas; ++a) {
+    p.lo[a] = area_rng[2 * a];
+    p.hi[a] = area_rng[2 * a + 1];
+  }
+  p.T = T;
+  p.A = num_areas;
+  p.K = e->num_cats;
+  p.max_det = max_det;
+  p.max_d = max_d;
+  p.slot_elems = (long long)max_d * e->max_img_gts;
+  // the detection half as ld_coco_match reads it (no cell-grouped GTs)
+  ld_coco_batch_t b{};
+  b.dets = e->dets;
+  b.labels = e->labels;
+  b.det_off = e->det_off;
+  b.img_rank = e->img_rank;
+  b.label_cat = e->label_cat;
+  b.num_imgs = e->num_imgs;
+  b.num_dets = e->num_dets;
+  b.num_labels = e->num_labels;
+  b.max_img_dets = e->max_img_dets;
+  b.num_all_imgs = e->num_all_imgs;
+  b.num_cats = e->num_cats;
+  const ErrGts eg{e->gt_box, e->gt_area, e->gt_crowd, e->gt_id, e->gt_cat,
+                  e->gt_img_off, e->cat_sup, e->max_img_gts};
+  hipStream_t stream = (hipStream_t)stream_;
+  char* ws = (char*)workspace;
+  int32_t* order = (int32_t*)(ws + o.order);
+  int32_t* big = (int32_t*)(ws + o.big);
+  double* slots = (double*)(ws + o.slots);
+  hipError_t err = ldrec::memset_async(big, 0, 4, stream);
+  if (err != hipSuccess) return (int)err;
+  if (b.num_dets > 0)
+    LD_LAUNCH(coco_rank_kernel, dim3((b.num_dets + 255) / 256), dim3(256), 0, stream, b, p,
+              order, rec_score, rec_cat, rec_pos, rec_match, rec_ign);
+  LD_LAUNCH(coco_match_errors_kernel<false>, dim3(b.num_imgs * b.num_cats), dim3(kWave), 0,
+            stream, b, eg, p, num_thrs, (const int32_t*)order, big, slots, rec_match,
+            rec_ign, npig);
+  if (b.num_dets > 0 && o.slots != o.total)
+    LD_LAUNCH(coco_match_errors_kernel<true>, dim3(kSlots), dim3(kWave), 0, stream, b, eg,
+              p, num_thrs, (const int32_t*)order, big, slots, rec_match, rec_ign, npig);
   return (int)hipGetLastError();
 }
 

@@ -106,6 +106,19 @@ class CocoBatchT(C.Structure):
                 ('num_gts', C.c_int32), ('max_cell_gts', C.c_int32)]
 
 
+class CocoErrBatchT(C.Structure):  # ld_coco_err_batch_t
+    _fields_ = [('dets', C.c_void_p), ('labels', C.c_void_p),
+                ('det_off', C.c_void_p), ('img_rank', C.c_void_p),
+                ('label_cat', C.c_void_p), ('gt_box', C.c_void_p),
+                ('gt_area', C.c_void_p), ('gt_crowd', C.c_void_p),
+                ('gt_id', C.c_void_p), ('gt_cat', C.c_void_p),
+                ('gt_img_off', C.c_void_p), ('cat_sup', C.c_void_p),
+                ('num_imgs', C.c_int32), ('num_dets', C.c_int32),
+                ('num_labels', C.c_int32), ('max_img_dets', C.c_int32),
+                ('num_all_imgs', C.c_int32), ('num_cats', C.c_int32),
+                ('num_gts', C.c_int32), ('max_img_gts', C.c_int32)]
+
+
 class ConvLevelT(C.Structure):
     _fields_ = [('Hin', C.c_int32), ('Win', C.c_int32), ('Hout', C.c_int32),
                 ('Wout', C.c_int32), ('off_in', C.c_int32),
@@ -226,7 +239,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -333,6 +346,10 @@ SIGNATURES = {
     'ld_coco_match': (C.c_int, [C.POINTER(CocoBatchT), _i32, _vp, _i32, _vp,
                                 _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                 _vp]),
+    'ld_coco_match_errors_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'ld_coco_match_errors': (C.c_int, [C.POINTER(CocoErrBatchT), _i32, _vp,
+                                       C.c_double, _i32, _vp, _i32, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_coco_accumulate_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32,
                                                  _i32]),
     'ld_coco_accumulate': (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _i32,
