@@ -16,7 +16,9 @@ per GPU, 800x1333 padded to 800x1344, 7 GT boxes each) resident in HBM.
 Workload = BASELINE.json configs[1] (ld_r50_gflv1_r101_fpn_coco_1x, bs 2 per
 GPU, fp32); weak scaling (per-GPU batch fixed).
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields.  A plain run
+does only what they need: set-up, warm-up, the timed steps, --dump-outputs and
+that line.  With --full it also runs the other legs and adds
   roofline      the dominant kernel family (fp32 MFMA implicit-GEMM conv):
                 algorithmic conv FLOPs / summed HIP-event launch durations,
                 measured in an instrumented pass right after the timed region
@@ -26,6 +28,13 @@ Prints ONE JSON line on rank 0 with the driver's contract fields plus
                 mmdet sources from the oracle/_ref archive, through the oracle
                 shim, in a child process) on the host cores; the CPU oracle
                 ("port") only when that archive is absent.
+  bf16, roofline_bf16
+                the same step with bf16 matrix operands
+  step_list     the step captured once and re-issued by the C launch loop
+  config.images_per_sec_teacher_in_step
+                the same K steps with the frozen teacher inside each step
+                instead of one step ahead
+The --no-* switches turn single legs of a --full run off.
 """
 import argparse
 import json
@@ -63,14 +72,23 @@ def parse():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch-per-gpu', type=int, default=2)
     ap.add_argument('--num-gt', type=int, default=7)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-roofline', action='store_true')
-    ap.add_argument('--profile-steps', type=int, default=2)
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline step, run every other leg: the '
+                    'teacher-in-step timing, the conv and LD-KL kernel '
+                    'rooflines, the bf16 leg, the step-list leg and the CPU '
+                    'baseline (off by default: a plain run times the headline '
+                    'step only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true',
+                    help='with --full: skip the CPU baseline leg')
+    ap.add_argument('--no-kernel-roofline', action='store_true',
+                    help='with --full: skip the conv and LD-KL roofline legs')
+    ap.add_argument('--profile-steps', type=int, default=2,
+                    help='with --full: instrumented steps of the conv roofline')
     ap.add_argument('--no-graph', action='store_true',
-                    help='skip the step-list leg (the captured step re-issued by '
-                    'the C launch loop)')
+                    help='with --full: skip the step-list leg (the captured '
+                    'step re-issued by the C launch loop)')
     ap.add_argument('--no-bf16', action='store_true',
-                    help='skip the bf16 (BASELINE config 3) leg')
+                    help='with --full: skip the bf16 (BASELINE config 3) leg')
     ap.add_argument('--no-prefetch', action='store_true',
                     help='run the frozen teacher inside each step instead of '
                     'one step ahead (see "teacher_prefetch" in the output)')
@@ -637,7 +655,7 @@ def main():
     # after ~100 steps at full power).  It is timed
     # again after them and that figure is reported beside it.
     ldkl_first = None
-    if rank == 0 and not args.no_kernel_roofline:
+    if rank == 0 and args.full and not args.no_kernel_roofline:
         try:
             ldkl_first = ldkl_roofline(dev)
         except Exception as e:  # never lose the bench line over the extra leg
@@ -750,7 +768,7 @@ def main():
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, last_out[0], trainer)
     dt_plain = None
-    if prefetch:  # the same K steps with the teacher inside each step, for the record
+    if prefetch and args.full:  # the same K steps with the teacher inside each step
         prefetch = False
         dt_plain, _, _ = timed(1, args.steps)
         prefetch = True
@@ -775,7 +793,7 @@ def main():
             'rccl_ranks': dist.get_world_size() if dist.is_initialized() else 1,
             'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': ms_sync_median, 'higher_is_better': True,
-            'scaling': 'weak',
+            'scaling': 'weak', 'full': args.full,
             'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'value_definition': (
                 'global batch / median over %d steps, each timed with HIP events '
@@ -829,7 +847,7 @@ def main():
     # them -- their gradient / normaliser all-reduces must be matched on all
     # ranks (rank 0 alone would pair them with the other ranks' barrier).
     roof = None
-    if not args.no_kernel_roofline:
+    if args.full and not args.no_kernel_roofline:
         roof = kernel_roofline(trainer, dbatch, args.profile_steps)
     if rank == 0 and roof is not None:
         res['roofline'] = roof
@@ -853,7 +871,7 @@ def main():
     # ---- bf16 leg (BASELINE config 3's arithmetic on this rank count): the
     # same step with bf16 matrix operands.  The headline `value` above stays
     # the fp32 config; this is reported beside it.
-    if not args.no_bf16:
+    if args.full and not args.no_bf16:
         from ld_amd import layers as Y
         Y.set_precision('bf16')
         dtb, tenqb, lossb = timed(args.warmup, args.steps)
@@ -897,7 +915,8 @@ def main():
     # line.  Reported beside the eager numbers; `value` stays the eager fp32 step.
     # (not with N > 1 ranks: a captured step would contain RCCL collectives, which
     # the capture refuses -- they race with ProcessGroupNCCL's watchdog)
-    if not args.no_graph and world == 1 and not os.environ.get('LD_FORCE_COLLECTIVES') == '1':
+    if args.full and not args.no_graph and world == 1 and \
+            not os.environ.get('LD_FORCE_COLLECTIVES') == '1':
         from ld_amd import layers as Y
         from ld_amd.train import PipelinedGraphedStep
         list_res = {}
@@ -941,7 +960,7 @@ def main():
             res['step_list'] = list_res
     if world > 1:
         dist.barrier()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and \
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and \
             args.config == 2:  # the CPU port restates configs[1]'s nets
         res['cpu_baseline'] = cpu_baseline(cpu_batch)
     if rank == 0:

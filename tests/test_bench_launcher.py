@@ -103,3 +103,14 @@ def test_steps_must_be_positive(monkeypatch):
                                       '--dump-outputs', 'out'])
     args = bench.parse()
     assert args.steps == 4 and args.dump_outputs == 'out'
+
+
+def test_plain_run_times_the_headline_only(monkeypatch):
+    """The legs beside the headline step run with --full only; the --no-*
+    switches still turn single legs of a --full run off."""
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '4'])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-bf16'])
+    args = bench.parse()
+    assert args.full and args.no_bf16 and not args.no_graph
