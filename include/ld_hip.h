@@ -919,6 +919,33 @@ int ld_sgd_step(float* params, const float* grads, float* momentum_buf, size_t n
 int ld_sgd_step_dev(float* params, const float* grads, float* momentum_buf, size_t n,
                     const float* hyper, ld_stream_t stream);
 
+/* ---- optimizer of a config's recipe (optim.hip, ld_amd/optim.py) ---------------
+ * hyper (DEVICE, fp32) = {momentum, grad_scale, max_norm, 0,
+ *                         lr_0, wd_0, lr_1, wd_1, ..., lr_{C-1}, wd_{C-1}}:
+ * one (lr, weight_decay) pair per parameter class of mmcv's
+ * DefaultOptimizerConstructor paramwise_cfg (bias_lr_mult, *_decay_mult,
+ * custom_keys), C <= LD_SGD_MAX_CLASSES.  Read on the device, so a captured step
+ * follows an lr schedule the host rewrites between replays. */
+#define LD_SGD_MAX_CLASSES 64
+/* torch.optim.SGD with per-class (lr, wd):
+ *   d = g*s + wd_c*p; buf = mu*buf + d; p -= lr_c*buf,   s = grad_scale * clip[1]
+ * (s = grad_scale when clip is NULL).  chunk_class: one uint8 class id per 64
+ * floats of the arena (ceil(n / 64) entries; every parameter starts on a 64-float
+ * boundary).  clip: NULL or the output of ld_grad_norm.  With one class and
+ * clip[1] == 1 the result is bit-identical to ld_sgd_step / ld_sgd_step_dev. */
+int ld_sgd_step_classes(float* params, const float* grads, float* momentum_buf,
+                        size_t n, const uint8_t* chunk_class, int num_classes,
+                        const float* hyper, const float* clip, ld_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) of grads * grad_scale
+ * (the arena holds the SUM over ranks; mmcv's OptimizerHook clips the average):
+ * out = {total_norm, clip_coef}, total_norm = grad_scale * ||grads||_2,
+ * clip_coef = min(1, max_norm / (total_norm + 1e-6)) in fp32.  fp64 partials of a
+ * fixed grid, then one fixed-order final sum: the same bits on every run.  grad_scale
+ * and max_norm come from hyper[1], hyper[2] (layout above). */
+size_t ld_grad_norm_workspace_bytes(void);
+int ld_grad_norm(const float* grads, size_t n, const float* hyper, float* out,
+                 void* workspace, size_t workspace_bytes, ld_stream_t stream);
+
 /* ---- GFLv2 distribution-guided quality branch (config 5, R-V2) ----------------
  * GFocalHead.forward_single's tail (gfocal_head.py:201-217) for all levels and
  * images in one launch, on the level-concatenated (N, C, P) tensors:

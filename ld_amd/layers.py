@@ -2398,6 +2398,51 @@ def sgd_step(params_flat, grads_flat, momentum_flat, lr, momentum,
     refresh_params(params_flat.device)
 
 
+def sgd_step_classes(params_flat, grads_flat, momentum_flat, chunk_class,
+                     num_classes, hyper, clip=None):
+    """SGD with (lr, weight decay) per parameter class (ld_sgd_step_classes):
+    ``chunk_class`` uint8, one class id per 64 floats of the arena; ``hyper``
+    the device table [momentum, grad_scale, max_norm, 0, lr_0, wd_0, ...];
+    ``clip`` None or the [total_norm, clip_coef] output of ``grad_norm``."""
+    lib = L.get_lib()
+    for t in (params_flat, grads_flat, momentum_flat):
+        _dev_f32(t, 'sgd arena')
+    _dev_f32(hyper, 'sgd class table')
+    L.require_device(chunk_class, torch.uint8, 'sgd chunk classes')
+    n = params_flat.numel()
+    if chunk_class.numel() < (n + 63) // 64:
+        raise L.LdError(f'{chunk_class.numel()} chunk class ids for an arena '
+                        f'of {n} floats (one per 64 floats needed)')
+    if hyper.numel() < 4 + 2 * int(num_classes):
+        raise L.LdError(f'class table of {hyper.numel()} floats for '
+                        f'{num_classes} classes')
+    if clip is not None:
+        _dev_f32(clip, 'clip coefficient')
+    L.check(lib.ld_sgd_step_classes(
+        L.ptr(params_flat), L.ptr(grads_flat), L.ptr(momentum_flat), n,
+        L.ptr(chunk_class), int(num_classes), L.ptr(hyper), L.ptr(clip),
+        L.stream_ptr(params_flat.device)), 'ld_sgd_step_classes')
+    bump_param_generation()
+    refresh_params(params_flat.device)
+
+
+def grad_norm(grads_flat, hyper, out, workspace):
+    """out <- [grad_scale * ||grads||_2, clip_coef] (ld_grad_norm); grad_scale
+    and max_norm from hyper[1], hyper[2]; ``workspace`` >=
+    ld_grad_norm_workspace_bytes() bytes of device memory."""
+    lib = L.get_lib()
+    _dev_f32(grads_flat, 'gradient arena')
+    _dev_f32(hyper, 'sgd class table')
+    _dev_f32(out, 'grad norm output')
+    if out.numel() < 2:
+        raise L.LdError('grad norm output needs 2 floats')
+    L.require_device(workspace, None, 'grad norm workspace')
+    nbytes = workspace.numel() * workspace.element_size()
+    L.check(lib.ld_grad_norm(L.ptr(grads_flat), grads_flat.numel(), L.ptr(hyper),
+                             L.ptr(out), L.ptr(workspace), nbytes,
+                             L.stream_ptr(grads_flat.device)), 'ld_grad_norm')
+
+
 # ---------------------------------------------------------------------------
 # level packing: the shared head towers run on ONE level-concatenated tensor
 # ---------------------------------------------------------------------------

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, '_lib', 'libldhip.so')
 
 LD_MAX_LEVELS = 8
 LD_NUM_LOSS_KEYS = 8
+LD_SGD_MAX_CLASSES = 64  # ld_sgd_step_classes: parameter classes per table
 LOSS_KEYS = ('loss_cls', 'loss_bbox', 'loss_dfl', 'loss_ld', 'loss_ld_vlr',
              'loss_kd', 'loss_kd_neg', 'loss_im')
 
@@ -239,7 +240,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -471,6 +472,10 @@ SIGNATURES = {
     'ld_sgd_step': (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32,
                               _vp]),
     'ld_sgd_step_dev': (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    'ld_sgd_step_classes': (C.c_int, [_vp, _vp, _vp, _sz, _vp, _i32, _vp, _vp,
+                                      _vp]),
+    'ld_grad_norm_workspace_bytes': (_sz, []),
+    'ld_grad_norm': (C.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -303,12 +303,25 @@ def _warn_graph_queues(what):
 
 class SGDTrainer:
     """One LD training iteration = forward_train -> _parse_losses -> backward
-    (with overlapped gradient all-reduce) -> SGD step."""
+    (with overlapped gradient all-reduce) -> SGD step.
+
+    The config's recipe (``SGDTrainer.from_config``; ld_amd.optim,
+    ld_amd.schedule) adds three optional parts:
+      * ``param_classes`` (paramwise_cfg): per-class (lr, weight decay) read by
+        ld_sgd_step_classes from a device table;
+      * ``grad_clip`` (dict(max_norm, norm_type=2)): ld_grad_norm before the
+        update, the step's result gains ``grad_norm`` (a device scalar);
+      * ``lr_schedule`` (a schedule.StepLrSchedule): applied from
+        (``epoch``, ``iter``) before every step, eager or replayed.
+    Without ``param_classes`` and ``grad_clip`` the update is the one
+    ld_sgd_step / ld_sgd_step_dev launch of the plain constructor."""
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4,
-                 bucket_bytes=32 << 20, tail_bytes=8 << 20):
+                 bucket_bytes=32 << 20, tail_bytes=8 << 20, param_classes=None,
+                 grad_clip=None, lr_schedule=None):
         self.model = model
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
+        self.base_lr = lr  # initial lr of an unscaled group (mmcv's initial_lr)
         frozen = [p for p in model.parameters() if not p.requires_grad]
         self.arena = GradArena(list(model.parameters()), bucket_bytes,
                                extra_state=frozen + list(model.buffers()),
@@ -318,6 +331,107 @@ class SGDTrainer:
         self.iter = 0
         self.epoch = 0
         self._hyper_dev = self._hyper_host = None
+        self.param_classes = param_classes
+        if grad_clip is not None:
+            from .optim import parse_grad_clip
+            grad_clip = parse_grad_clip(dict(grad_clip=grad_clip))
+        self.grad_clip = grad_clip
+        self.lr_schedule = lr_schedule
+        self._sched_epoch, self._sched_lrs = None, None
+        self._classes = None
+        if param_classes is not None or grad_clip is not None:
+            self._init_classes()
+        if lr_schedule is not None:
+            lr_schedule.before_run(self._base_lrs())
+
+    @classmethod
+    def from_config(cls, model, cfg, **kw):
+        """The trainer a config's ``optimizer``, ``optimizer_config`` and
+        ``lr_config`` describe (mmcv's build_optimizer + OptimizerHook +
+        StepLrUpdaterHook); ``kw`` goes to the constructor."""
+        from .optim import build_optimizer
+        from .schedule import build_lr_schedule
+        for key in ('momentum_config', 'fp16'):
+            # recipe keys that change the update and are not restated here:
+            # training without them would silently differ from the config
+            if cfg.get(key) is not None:
+                raise NotImplementedError(
+                    f'config key {key!r} is not supported (SGDTrainer trains '
+                    'fp32 without a momentum schedule)')
+        opt = build_optimizer(model, cfg['optimizer'],
+                              cfg.get('optimizer_config'))
+        return cls(model, lr=opt['lr'], momentum=opt['momentum'],
+                   weight_decay=opt['weight_decay'],
+                   param_classes=opt['param_classes'],
+                   grad_clip=opt['grad_clip'],
+                   lr_schedule=build_lr_schedule(cfg.get('lr_config')), **kw)
+
+    # -- per-class optimizer (paramwise_cfg / grad_clip) ------------------------
+    def _init_classes(self):
+        from .optim import ParamClasses
+        from . import lib as L
+        allp = self._all_params()
+        classes = self.param_classes
+        if classes is None:  # grad_clip alone: one class
+            classes = ParamClasses(allp, [str(i) for i in range(len(allp))],
+                                   [(1.0, 1.0)] * len(allp))
+        elif [id(p) for p in classes.params] != [id(p) for p in allp]:
+            raise ValueError('param_classes were built for another model')
+        self._classes = classes
+        dev = self.arena.flat_param.device
+        self._chunk_ids = classes.chunk_ids(self.arena)
+        n = 4 + 2 * len(classes)
+        self._hyper_host = None  # pinned staging, made at the first push
+        self._hyper_dev = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._hyper_last = None
+        self._norm_ws = None
+        if self.grad_clip is not None:
+            nbytes = L.get_lib().ld_grad_norm_workspace_bytes()
+            self._norm_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def _base_lrs(self):
+        """Base lr of the schedule's groups: [unscaled] + one per class."""
+        lrs = [self.base_lr]
+        if self._classes is not None:
+            lrs += [self.base_lr * m for m, _ in self._classes.classes]
+        return lrs
+
+    def _class_lrs(self):
+        if self.lr_schedule is not None and self._sched_lrs is not None:
+            return list(self._sched_lrs[1:])
+        return [self.lr * m for m, _ in self._classes.classes]
+
+    def _class_wds(self):
+        return [self.weight_decay * d for _, d in self._classes.classes]
+
+    # -- lr schedule ------------------------------------------------------------
+    def _set_lrs(self, lrs):
+        self._sched_lrs = list(lrs)
+        self.lr = lrs[0]
+
+    def begin_epoch(self, epoch):
+        """mmcv's before_train_epoch: the regular lr of ``epoch``."""
+        self.epoch = int(epoch)
+        if self.lr_schedule is not None:
+            lrs = self.lr_schedule.before_train_epoch(self.epoch, self.iter)
+            if lrs is not None:
+                self._set_lrs(lrs)
+            self._sched_epoch = self.epoch
+
+    def _apply_schedule(self):
+        """mmcv's before_train_iter at (epoch, iter); nothing while capturing
+        (the capture executes nothing; replays apply it themselves)."""
+        if self.lr_schedule is None or torch.cuda.is_current_stream_capturing():
+            return
+        if self._sched_epoch != self.epoch:
+            self.begin_epoch(self.epoch)
+        lrs = self.lr_schedule.before_train_iter(self.epoch, self.iter)
+        if lrs is not None:
+            self._set_lrs(lrs)
+
+    def _before_step(self):
+        self._apply_schedule()
+        self._push_hyper()
 
     def enable_device_hyper(self):
         """Route lr / momentum / weight decay / the 1/world gradient scale to the
@@ -338,10 +452,19 @@ class SGDTrainer:
         if self._hyper_dev is None or \
                 torch.cuda.is_current_stream_capturing():
             return
-        vals = (float(self.lr), float(self.momentum), float(self.weight_decay),
-                1.0 / _world())
+        if self._classes is not None:
+            max_norm = self.grad_clip['max_norm'] if self.grad_clip else 0.0
+            vals = tuple([float(self.momentum), 1.0 / _world(), float(max_norm),
+                          0.0] + self._classes.table(self._class_lrs(),
+                                                     self._class_wds()))
+        else:
+            vals = (float(self.lr), float(self.momentum),
+                    float(self.weight_decay), 1.0 / _world())
         if vals == self._hyper_last:
             return  # unchanged since the last push: the device copy is current
+        if self._hyper_host is None:
+            from .lossblock import PinnedRing
+            self._hyper_host = PinnedRing(self._hyper_dev.numel(), torch.float32)
         self._hyper_last = vals
         self._hyper_host.stage(self._hyper_dev, vals)
 
@@ -362,27 +485,95 @@ class SGDTrainer:
             for p, o in zip(self.arena.order, self.arena.offsets):
                 buf = self.flat_momentum[o:o + p.numel()].view_as(p)
                 state[index[id(p)]] = dict(momentum_buffer=buf.detach().clone())
+        if self.param_classes is not None:
+            # paramwise_cfg: mmcv's layout, one group per parameter
+            lrs, wds = self._class_lrs(), self._class_wds()
+            groups = []
+            for i, c in enumerate(self.param_classes.class_of):
+                g = dict(lr=lrs[c], momentum=self.momentum, dampening=0,
+                         weight_decay=wds[c], nesterov=False, params=[i])
+                if self.lr_schedule is not None:
+                    g['initial_lr'] = self._base_lrs()[1 + c]
+                groups.append(g)
+            return dict(state=state, param_groups=groups)
         group = dict(lr=self.lr, momentum=self.momentum, dampening=0,
                      weight_decay=self.weight_decay, nesterov=False,
                      params=list(range(len(allp))))
+        if self.lr_schedule is not None:
+            group['initial_lr'] = self.base_lr
         return dict(state=state, param_groups=[group])
+
+    def _load_paramwise_groups(self, groups):
+        """Per-parameter groups (mmcv's paramwise layout) -> base lr, lr and
+        weight decay of an unscaled group; every group must match this
+        trainer's classification."""
+        import math
+        pc = self.param_classes
+        allp = self._all_params()
+        if len(groups) != len(allp):
+            raise ValueError(
+                f'expected one param group per parameter ({len(allp)}, '
+                f'paramwise_cfg), got {len(groups)}')
+        for i, g in enumerate(groups):
+            if list(g['params']) != [i]:
+                raise ValueError(f'param group {i} holds parameters '
+                                 f"{list(g['params'])}, expected [{i}]")
+            if g.get('nesterov') or g.get('dampening', 0) != 0:
+                raise NotImplementedError('nesterov / dampening are not '
+                                          'supported (plain SGD)')
+        base = [float(g.get('initial_lr', g['lr'])) for g in groups]
+
+        def ref(k):  # a parameter whose multiplier k is 1 (else non-zero)
+            idx = [i for i, m in enumerate(pc.mults) if m == (1.0, 1.0)] or \
+                [i for i, m in enumerate(pc.mults) if m[k] != 0.0]
+            return idx[0] if idx else None
+        r = ref(0)
+        base_lr = base[r] / pc.mults[r][0] if r is not None else self.base_lr
+        lr = float(groups[r]['lr']) / pc.mults[r][0] if r is not None \
+            else self.lr
+        r = ref(1)
+        wd = float(groups[r]['weight_decay']) / pc.mults[r][1] \
+            if r is not None else self.weight_decay
+        for i, (g, (lm, dm)) in enumerate(zip(groups, pc.mults)):
+            ok = math.isclose(base[i], base_lr * lm, rel_tol=1e-9,
+                              abs_tol=1e-15) and \
+                math.isclose(float(g['weight_decay']), wd * dm, rel_tol=1e-9,
+                             abs_tol=1e-15)
+            if not ok:
+                raise ValueError(
+                    f'optimizer group of parameter {i} ({pc.names[i]}): lr '
+                    f"{base[i]} / weight_decay {g['weight_decay']} does not "
+                    f'match this trainer\'s classification (lr_mult {lm}, '
+                    f'decay_mult {dm} of lr {base_lr}, weight_decay {wd})')
+        return base_lr, lr, wd
 
     def load_state_dict(self, sd):
         groups = sd['param_groups']
-        if len(groups) != 1:
-            raise ValueError('expected the single param group of the LD '
-                             f'configs, got {len(groups)}')
-        g = groups[0]
         allp = self._all_params()
-        if len(g['params']) != len(allp):
-            raise ValueError(f"optimizer state is for {len(g['params'])} "
-                             f'parameters, the model has {len(allp)}')
-        if g.get('nesterov') or g.get('dampening', 0) != 0:
-            raise NotImplementedError('nesterov / dampening are not on the LD '
-                                      'recipe (configs/ld/*.py: plain SGD)')
-        self.lr = float(g['lr'])
-        self.momentum = float(g['momentum'])
-        self.weight_decay = float(g['weight_decay'])
+        if self.param_classes is not None:
+            self.base_lr, self.lr, self.weight_decay = \
+                self._load_paramwise_groups(groups)
+            self.momentum = float(groups[0]['momentum'])
+        else:
+            if len(groups) != 1:
+                raise ValueError('expected the single param group of the LD '
+                                 f'configs, got {len(groups)}')
+            g = groups[0]
+            if len(g['params']) != len(allp):
+                raise ValueError(f"optimizer state is for {len(g['params'])} "
+                                 f'parameters, the model has {len(allp)}')
+            if g.get('nesterov') or g.get('dampening', 0) != 0:
+                raise NotImplementedError('nesterov / dampening are not on the '
+                                          'LD recipe (configs/ld/*.py: plain '
+                                          'SGD)')
+            self.lr = float(g['lr'])
+            self.base_lr = float(g.get('initial_lr', g['lr']))
+            self.momentum = float(g['momentum'])
+            self.weight_decay = float(g['weight_decay'])
+        if self.lr_schedule is not None:
+            # mmcv's before_run after a resume: the loaded initial_lr
+            self.lr_schedule.before_run(self._base_lrs())
+            self._sched_epoch, self._sched_lrs = None, None
         offset_of = {id(p): o for p, o in zip(self.arena.order,
                                               self.arena.offsets)}
         self.flat_momentum.zero_()
@@ -405,6 +596,7 @@ class SGDTrainer:
         (KnowledgeDistillationSingleStageDetector.prefetch_teacher)."""
         if next_data is not None and hasattr(self.model, 'prefetch_teacher'):
             self.model.prefetch_teacher(next_data['img'])
+        self._apply_schedule()
         self.arena.zero_grad()
         # _parse_losses sums the loss keys with unit coefficients, so the fused
         # loss block may hand back the gradient its forward launch already
@@ -435,12 +627,29 @@ class SGDTrainer:
                     'decay them (torch.optim.SGD would not)')
         self.arena.finish()
         self._push_hyper()
-        Y.sgd_step(self.arena.flat_param, self.arena.flat_grad,
-                   self.flat_momentum, self.lr, self.momentum,
-                   self.weight_decay, 1.0 / _world(), hyper=self._hyper_dev)
-        self.iter += 1
-        return dict(loss=loss.detach(), log_vars=log_vars,
-                    num_samples=len(data['img_metas']))
+        norm = None
+        if self._classes is not None:
+            if self.grad_clip is not None:
+                # OptimizerHook: clip_grad_norm_ of the averaged gradient, then
+                # the update with the coefficient folded into its scale
+                norm = torch.empty(2, dtype=torch.float32,
+                                   device=self.arena.flat_grad.device)
+                Y.grad_norm(self.arena.flat_grad, self._hyper_dev, norm,
+                            self._norm_ws)
+            Y.sgd_step_classes(self.arena.flat_param, self.arena.flat_grad,
+                               self.flat_momentum, self._chunk_ids,
+                               len(self._classes), self._hyper_dev, clip=norm)
+        else:
+            Y.sgd_step(self.arena.flat_param, self.arena.flat_grad,
+                       self.flat_momentum, self.lr, self.momentum,
+                       self.weight_decay, 1.0 / _world(), hyper=self._hyper_dev)
+        if not torch.cuda.is_current_stream_capturing():
+            self.iter += 1  # a capture executes nothing: not an iteration
+        out = dict(loss=loss.detach(), log_vars=log_vars,
+                   num_samples=len(data['img_metas']))
+        if norm is not None:
+            out['grad_norm'] = norm[0]
+        return out
 
 
 def _refuse_collectives_in_capture(what):
@@ -610,6 +819,7 @@ class GraphedStep:
             out = trainer.step(self.data)
         self.list = _StepList(self.graph) if launcher == 'list' else None
         self._loss = out['loss']
+        self._grad_norm = out.get('grad_norm')
         lv = out['log_vars']
         self._log_keys, self._log_tensor = list(lv._keys), lv._tensor
         self.num_samples = out['num_samples']
@@ -642,15 +852,18 @@ class GraphedStep:
 
     def replay(self):
         from .heads import LazyScalars
-        self.trainer._push_hyper()
+        self.trainer._before_step()
         if self.list is not None:
             self.list.replay(self.dev)
         else:
             self.graph.replay()
         self.trainer.iter += 1
-        return dict(loss=self._loss,
-                    log_vars=LazyScalars(self._log_keys, self._log_tensor),
-                    num_samples=self.num_samples)
+        out = dict(loss=self._loss,
+                   log_vars=LazyScalars(self._log_keys, self._log_tensor),
+                   num_samples=self.num_samples)
+        if self._grad_norm is not None:
+            out['grad_norm'] = self._grad_norm
+        return out
 
 
 class PipelinedGraphedStep:
@@ -730,7 +943,7 @@ class PipelinedGraphedStep:
             self.graphs.append(g)
             self.lists.append(_StepList(g) if launcher == 'list' else None)
             self.outs.append((out['loss'], list(lv._keys), lv._tensor,
-                              out['num_samples']))
+                              out['num_samples'], out.get('grad_norm')))
         self.cur = 0
 
     def _one(self, k):
@@ -766,16 +979,19 @@ class PipelinedGraphedStep:
         nxt['data']['img'].copy_(next_data['img'], non_blocking=True)
         nxt['static'].load(next_data['img_metas'], next_data['gt_bboxes'],
                            next_data['gt_labels'])
-        self.trainer._push_hyper()
+        self.trainer._before_step()
         if self.lists[self.cur] is not None:
             self.lists[self.cur].replay(self.dev)
         else:
             self.graphs[self.cur].replay()
-        loss, keys, tensor, ns = self.outs[self.cur]
+        loss, keys, tensor, ns, gnorm = self.outs[self.cur]
         self.cur = 1 - self.cur
         self.trainer.iter += 1
-        return dict(loss=loss, log_vars=LazyScalars(keys, tensor),
-                    num_samples=ns)
+        out = dict(loss=loss, log_vars=LazyScalars(keys, tensor),
+                   num_samples=ns)
+        if gnorm is not None:
+            out['grad_norm'] = gnorm
+        return out
 
 class AutoStepper:
     """How a train step is enqueued (DESIGN.md sections 4 and 5):
