@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "conv_common.h"
+#include "conv_tune.h"
 
 namespace {
 
@@ -1918,91 +1919,61 @@ inline int stream_cfg_model(const ConvK& k) {
   return best;
 }
 
-constexpr int kTuneReps = 3;
-
-inline int stream_cfg_index(const LdTuneCfg& c) {
-  for (int i = 0; i < kNumStreamCfgs; ++i)
-    if (kStreamCfgs[i].tm == c.tm && kStreamCfgs[i].tn == c.tn &&
-        kStreamCfgs[i].wvm == c.wvm && kStreamCfgs[i].d == c.d &&
-        kStreamCfgs[i].ks == c.ks)
-      return i;
-  return -1;
+inline LdTuneCfg stream_cfg_rec(const StreamCfg& c) {
+  return LdTuneCfg{c.tm, c.tn, c.wvm, c.d, c.ks};
 }
 
-// Shape choice of a launch: forced by LD_CONV_STREAM, else the tuning table
-// (ld_conv_tune_load / ld_conv_tune_*), else the round-count model -- a pure
-// function of the geometry.  Never times anything and never synchronises: the
-// launch entry points only enqueue.  *forced gets the LD_CONV_STREAM override.
-template <int MODE>
-int pick_stream_cfg(const ConvK& k, StreamCfg* forced, int* cap) {
-  *cap = 0;
-  if (k.Cin % 8 != 0) return -1;
-  if (const char* env = getenv("LD_CONV_STREAM")) {
-    if (env[0] == '0' && env[1] == 0) return -1;
-    StreamCfg c;
-    c.ks = 1;
-    if (sscanf(env, "%dx%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.wvm, &c.d, &c.ks, cap) >= 4) {
-      while (c.d > 4 && k.Cin % (2 * c.d) != 0) c.d /= 2;
-      *forced = c;
-      return -2;
-    }
-  }
-  LdTuneCfg t;
-  if (ld_tune_lookup(make_tune_key(MODE, 0, k), &t)) {
-    const int i = stream_cfg_index(t);
-    if (i >= 0 && stream_cfg_fits(k, kStreamCfgs[i])) {
-      *cap = t.cap;
-      return i;
-    }
-  }
-  return stream_cfg_model(k);
-}
-
+// Shape choice of a launch (launch_picked): LD_CONV_STREAM, else the tuning
+// table (ld_conv_tune_load / ld_conv_tune_*), else the round-count model.
 template <int MODE>
 int launch_stream(const ConvK& k, hipStream_t stream) {
-  StreamCfg forced;
-  int cap = 0;
-  const int pick = pick_stream_cfg<MODE>(k, &forced, &cap);
-  if (pick == -1) return LD_EUNSUPPORTED;
-  if (pick == -2 && forced.ks == 2 && !stream_cfg_fits(k, forced)) {
+  if (k.Cin % 8 != 0) return LD_EUNSUPPORTED;
+  auto launch = [&](const StreamCfg& c, int cap) {
+    return launch_stream_cfg<MODE>(k, c, stream, cap);
+  };
+  auto by_model = [&] {
+    const int m = stream_cfg_model(k);
+    return m < 0 ? LD_EUNSUPPORTED : launch(kStreamCfgs[m], 0);
+  };
+  auto forced = [&](int* rc) {
+    const char* env = getenv("LD_CONV_STREAM");
+    if (!env) return false;
+    *rc = LD_EUNSUPPORTED;
+    if (env[0] == '0' && env[1] == 0) return true;
+    StreamCfg c;
+    c.ks = 1;
+    int cap = 0;
+    if (sscanf(env, "%dx%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.wvm, &c.d, &c.ks, &cap) < 4)
+      return false;
+    while (c.d > 4 && k.Cin % (2 * c.d) != 0) c.d /= 2;
     // a forced vector-1x1 shape on a conv it cannot serve (taps, stride,
     // alignment): the model's pick instead
-    const int m = stream_cfg_model(k);
-    return m < 0 ? LD_EUNSUPPORTED : launch_stream_cfg<MODE>(k, kStreamCfgs[m], stream);
-  }
-  if (pick == -2) {
-    const int rc = launch_stream_cfg<MODE>(k, forced, stream, cap);
-    if (rc != LD_EUNSUPPORTED) return rc;
-    forced.ks = 1;  // no split-K instance at this ring depth
-    const int rc1 = launch_stream_cfg<MODE>(k, forced, stream, cap);
-    if (rc1 != LD_EUNSUPPORTED) return rc1;
-    const int m = stream_cfg_model(k);  // no such instance for this layer
-    return m < 0 ? LD_EUNSUPPORTED : launch_stream_cfg<MODE>(k, kStreamCfgs[m], stream);
-  }
-  return launch_stream_cfg<MODE>(k, kStreamCfgs[pick], stream, cap);
+    if (!(c.ks == 2 && !stream_cfg_fits(k, c))) {
+      *rc = launch(c, cap);
+      if (*rc != LD_EUNSUPPORTED) return true;
+      c.ks = 1;  // no split-K instance at this ring depth
+      *rc = launch(c, cap);
+      if (*rc != LD_EUNSUPPORTED) return true;
+    }
+    *rc = by_model();  // no such instance for this layer
+    return true;
+  };
+  return launch_picked(MODE, 0, k, kStreamCfgs, forced, stream_cfg_rec, stream_cfg_fits,
+                       stream_cfg_model, launch);
 }
 
 // Explicit tuning (ld_conv_tune_forward / ld_conv_tune_dgrad): times every
 // candidate shape of the geometry on the caller's buffers (the launch is
-// idempotent), records the winner in the table.  This is the ONLY place that
-// synchronises; returns 0 (tuned), 1 (already in the table / nothing to tune).
+// idempotent), records the winner in the table.  The tuners are the ONLY place
+// that synchronises; returns 0 (tuned), 1 (already in the table / nothing to tune).
 template <int MODE>
 int tune_stream(const ConvK& k, hipStream_t stream) {
   if (k.Cin % 8 != 0) return 1;
   const LdTuneKey key = make_tune_key(MODE, 0, k);
-  LdTuneCfg have;
-  if (ld_tune_lookup(key, &have)) return 1;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
-  if (cap != hipStreamCaptureStatusNone) return LD_EUNSUPPORTED;
+  if (int r = tune_refused(key, stream)) return r;
   int pick = stream_cfg_model(k);
   if (pick < 0) return 1;
-  // quiesce the device first: work queued on other streams (the teacher's
-  // forward) would otherwise share the CUs with some candidates and not others
-  (void)hipDeviceSynchronize();
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
+  TuneTimer timer(stream);
   float best_ms = -1.0f;
   int best_cap = 0;
   // residency caps worth timing: none, and 2-4 workgroups per CU.  A layer
@@ -2010,20 +1981,10 @@ int tune_stream(const ConvK& k, hipStream_t stream) {
   static const int kCaps[] = {0, 4, 3, 2};
   for (int i = 0; i < kNumStreamCfgs; ++i) {
     if (!stream_cfg_fits(k, kStreamCfgs[i])) continue;
-    for (int ci = 0; ci < 4; ++ci) {
-      const int cap_try = kCaps[ci];
-      if (launch_stream_cfg<MODE>(k, kStreamCfgs[i], stream, cap_try) != 0) break;
-      float ms = -1.0f;
-      for (int trial = 0; trial < 2; ++trial) {  // best of two: clocks wander
-        (void)hipEventRecord(e0, stream);
-        for (int rep = 0; rep < kTuneReps; ++rep)
-          launch_stream_cfg<MODE>(k, kStreamCfgs[i], stream, cap_try);
-        (void)hipEventRecord(e1, stream);
-        if (hipEventSynchronize(e1) != hipSuccess) break;
-        float t = 0.0f;
-        (void)hipEventElapsedTime(&t, e0, e1);
-        if (ms < 0.0f || t < ms) ms = t;
-      }
+    for (const int cap_try : kCaps) {
+      const float ms = timer.time(
+          [&] { return launch_stream_cfg<MODE>(k, kStreamCfgs[i], stream, cap_try); });
+      if (ms == TuneTimer::kLaunchFailed) break;  // no instance: nor with another cap
       if (ms < 0.0f) continue;
       // a cap must win by > 1 %: ties go to the plain launch
       if (best_ms < 0.0f || ms < best_ms * (cap_try ? 0.99f : 1.0f)) {
@@ -2033,22 +1994,21 @@ int tune_stream(const ConvK& k, hipStream_t stream) {
       }
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   const StreamCfg& c = kStreamCfgs[pick];
-  if (const char* lg = getenv("LD_CONV_TUNE_LOG"))
-    if (lg[0] == '1') {
-      const double fl = 2.0 * k.J * k.Cout * k.Cin *
-                        (MODE == 1 ? k.nth * k.ntw : k.KH * k.KW);
-      fprintf(stderr,
-              "[ld_conv] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
-              "%dx%dx%dx%dx%d cap %d  %.1f TFLOP/s\n",
-              MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels,
-              c.tm, c.tn, c.wvm, c.d, c.ks, best_cap,
-              best_ms > 0 ? fl / (best_ms * 1e-3 / kTuneReps) / 1e12 : 0.0);
-    }
-  if (best_ms > 0.0f)
-    ld_tune_store(key, LdTuneCfg{c.tm, c.tn, c.wvm, c.d, c.ks, best_cap});
+  if (tune_log_level() == 1) {
+    const double fl = 2.0 * k.J * k.Cout * k.Cin *
+                      (MODE == 1 ? k.nth * k.ntw : k.KH * k.KW);
+    fprintf(stderr,
+            "[ld_conv] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
+            "%dx%dx%dx%dx%d cap %d  %.1f TFLOP/s\n",
+            MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels,
+            c.tm, c.tn, c.wvm, c.d, c.ks, best_cap, tune_tflops(fl, best_ms));
+  }
+  if (best_ms > 0.0f) {
+    LdTuneCfg rec = stream_cfg_rec(c);
+    rec.cap = best_cap;
+    ld_tune_store(key, rec);
+  }
   return 0;
 }
 
@@ -2252,6 +2212,25 @@ extern "C" int ld_conv_weight_transform_batch(const ld_wt_job_t* jobs,
 }
 
 namespace {
+// ConvK from the caller's descriptors: the conv geometry as given (the data
+// gradient, which swaps the roles of the two sides, fills its own) ...
+inline void fill_geometry(ConvK& k, const ld_conv_t* c) {
+  k.N = c->N; k.Cin = c->Cin; k.Cout = c->Cout; k.KH = c->KH; k.KW = c->KW;
+  k.g.stride = c->stride; k.g.pad = c->pad; k.Pin = c->Pin; k.Pout = c->Pout;
+  k.g.num_levels = c->num_levels;
+  k.J = c->N * c->Pout;
+  for (int l = 0; l < LD_MAX_LEVELS; ++l) k.g.lv[l] = c->lv[l];
+}
+
+// ... and the epilogue operands every forward kernel takes
+inline void fill_epilogue(ConvK& k, const ld_conv_epilogue_t* ep) {
+  k.bias = ep ? ep->bias : nullptr;
+  k.scale = ep ? ep->scale : nullptr;
+  k.shift = ep ? ep->shift : nullptr;
+  k.residual = ep ? ep->residual : nullptr;
+  k.relu = ep ? ep->relu : 0;
+}
+
 int build_forward(const ld_conv_t* c, const float* x, const void* wt_fwd,
                   const ld_conv_epilogue_t* ep, float* y, ConvK& k, int family = 0) {
   if (int e = check_conv(c)) return e;
@@ -2261,11 +2240,7 @@ int build_forward(const ld_conv_t* c, const float* x, const void* wt_fwd,
   k.x = x;
   k.wt = (const float*)wt_fwd;
   k.y = y;
-  k.bias = ep ? ep->bias : nullptr;
-  k.scale = ep ? ep->scale : nullptr;
-  k.shift = ep ? ep->shift : nullptr;
-  k.residual = ep ? ep->residual : nullptr;
-  k.relu = ep ? ep->relu : 0;
+  fill_epilogue(k, ep);
   k.y_c8 = ep ? ep->y_c8 : nullptr;
   k.res_c8 = ep ? ep->residual_c8 : nullptr;
   k.y_raw = ep ? ep->y_raw : nullptr;
@@ -2277,11 +2252,7 @@ int build_forward(const ld_conv_t* c, const float* x, const void* wt_fwd,
   if ((k.y_c8 || k.res_c8) && (family == 0 || c->Cout % 8 != 0)) return LD_EINVAL;
   if (k.res_c8 && k.residual) return LD_EINVAL;
   if ((k.scale == nullptr) != (k.shift == nullptr)) return LD_EINVAL;
-  k.N = c->N; k.Cin = c->Cin; k.Cout = c->Cout; k.KH = c->KH; k.KW = c->KW;
-  k.g.stride = c->stride; k.g.pad = c->pad; k.Pin = c->Pin; k.Pout = c->Pout;
-  k.g.num_levels = c->num_levels;
-  k.J = c->N * c->Pout;
-  for (int l = 0; l < LD_MAX_LEVELS; ++l) k.g.lv[l] = c->lv[l];
+  fill_geometry(k, c);
   if (family >= 1) {
     // bf16 image: [tap][Cin16 / 8][Cout][8] bf16 = 4 floats per (8-block, co)
     k.Kpad = (c->Cin + 15) / 16 * 2;
@@ -2370,18 +2341,10 @@ extern "C" int ld_conv_forward_smallc(const ld_conv_t* c, const float* x,
   k.x = x;
   k.wt = wt;
   k.y = y;
-  k.bias = ep ? ep->bias : nullptr;
-  k.scale = ep ? ep->scale : nullptr;
-  k.shift = ep ? ep->shift : nullptr;
-  k.residual = ep ? ep->residual : nullptr;
-  k.relu = ep ? ep->relu : 0;
+  fill_epilogue(k, ep);
   if (ep && (ep->y_c8 || ep->residual_c8 || ep->y_raw)) return LD_EINVAL;
   if ((k.scale == nullptr) != (k.shift == nullptr)) return LD_EINVAL;
-  k.N = c->N; k.Cin = c->Cin; k.Cout = c->Cout; k.KH = c->KH; k.KW = c->KW;
-  k.g.stride = c->stride; k.g.pad = c->pad; k.Pin = c->Pin; k.Pout = c->Pout;
-  k.g.num_levels = c->num_levels;
-  k.J = c->N * c->Pout;
-  for (int l = 0; l < LD_MAX_LEVELS; ++l) k.g.lv[l] = c->lv[l];
+  fill_geometry(k, c);
   k.Kpad = kpad_rows(c->Cin * c->KH * c->KW);
   if (int e = set_extents(k, (size_t)c->N * c->Cin * c->Pin,
                           (size_t)k.Kpad * c->Cout))
@@ -3001,16 +2964,8 @@ extern "C" int ld_conv_tune_wgrad(const ld_conv_t* c, const float* x, const floa
   if (!x || !dy || !dw || !workspace) return LD_EINVAL;
   if (workspace_bytes < ld_conv_tune_wgrad_workspace_bytes(c)) return LD_ENOSPACE;
   const LdTuneKey key = wgrad_tune_key(c);
-  LdTuneCfg have;
-  if (ld_tune_lookup(key, &have)) return 1;
-  hipStream_t stream = (hipStream_t)stream_;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
-  if (cap != hipStreamCaptureStatusNone) return LD_EUNSUPPORTED;
-  (void)hipDeviceSynchronize();
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
+  if (int r = tune_refused(key, (hipStream_t)stream_)) return r;
+  TuneTimer timer((hipStream_t)stream_);
   // candidates: the wave-private kernel, then the tile instances
   std::vector<WgCfg> cands;
   cands.push_back(WgCfg{0, 0, 0, 0, 0});
@@ -3058,40 +3013,28 @@ extern "C" int ld_conv_tune_wgrad(const ld_conv_t* c, const float* x, const floa
   }
   float best_ms = -1.0f;
   WgCfg best = cands[0];
+  const int log = tune_log_level();
   for (const WgCfg& g : cands) {
-    if (wgrad_run(c, x, dy, dw, 0, workspace, workspace_bytes, stream_, 0, &g) != 0) continue;
-    float ms = -1.0f;
-    for (int trial = 0; trial < 2; ++trial) {
-      (void)hipEventRecord(e0, stream);
-      for (int rep = 0; rep < kTuneReps; ++rep)
-        wgrad_run(c, x, dy, dw, 0, workspace, workspace_bytes, stream_, 0, &g);
-      (void)hipEventRecord(e1, stream);
-      if (hipEventSynchronize(e1) != hipSuccess) break;
-      float t = 0.0f;
-      (void)hipEventElapsedTime(&t, e0, e1);
-      if (ms < 0.0f || t < ms) ms = t;
-    }
-    if (const char* lg = getenv("LD_CONV_TUNE_LOG"))
-      if (lg[0] == '2')
-        fprintf(stderr, "[ld_conv]   wgrad cand %d,%d,%d,%d,%d  %.1f us\n", g.kind, g.kg, g.bk,
-                g.splits, g.fused, ms * 1e3 / kTuneReps);
+    const float ms = timer.time([&] {
+      return wgrad_run(c, x, dy, dw, 0, workspace, workspace_bytes, stream_, 0, &g);
+    });
+    if (ms == TuneTimer::kLaunchFailed) continue;
+    if (log == 2)
+      fprintf(stderr, "[ld_conv]   wgrad cand %d,%d,%d,%d,%d  %.1f us\n", g.kind, g.kg, g.bk,
+              g.splits, g.fused, ms * 1e3 / kTuneReps);
     if (ms >= 0.0f && (best_ms < 0.0f || ms < best_ms)) {
       best_ms = ms;
       best = g;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (const char* lg = getenv("LD_CONV_TUNE_LOG"))
-    if (lg[0] == '1' || lg[0] == '2') {
-      const double fl = 2.0 * c->N * c->Pout * (double)c->Cout * c->Cin * c->KH * c->KW;
-      fprintf(stderr,
-              "[ld_conv] wgrad Cin %d Cout %d k %dx%d s%d J %d lv %d -> kind %d kg %d bk %d "
-              "splits %d fused %d  %.1f TFLOP/s\n",
-              c->Cin, c->Cout, c->KH, c->KW, c->stride, c->N * c->Pout, c->num_levels,
-              best.kind, best.kg, best.bk, best.splits, best.fused,
-              best_ms > 0 ? fl / (best_ms * 1e-3 / kTuneReps) / 1e12 : 0.0);
-    }
+  if (log >= 1) {
+    const double fl = 2.0 * c->N * c->Pout * (double)c->Cout * c->Cin * c->KH * c->KW;
+    fprintf(stderr,
+            "[ld_conv] wgrad Cin %d Cout %d k %dx%d s%d J %d lv %d -> kind %d kg %d bk %d "
+            "splits %d fused %d  %.1f TFLOP/s\n",
+            c->Cin, c->Cout, c->KH, c->KW, c->stride, c->N * c->Pout, c->num_levels,
+            best.kind, best.kg, best.bk, best.splits, best.fused, tune_tflops(fl, best_ms));
+  }
   if (best_ms > 0.0f)
     ld_tune_store(key, LdTuneCfg{best.kind, best.kg, best.bk, best.splits, best.fused, 0});
   return 0;

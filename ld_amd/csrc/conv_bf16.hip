@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "conv_tune.h"
 
 namespace {
 
@@ -2082,95 +2083,59 @@ inline int cfg_model(const ConvK& k) {
   return best;
 }
 
-inline int cfg_index(const LdTuneCfg& c) {
-  for (int i = 0; i < kNumCfgs; ++i)
-    if (kCfgs[i].tm == c.tm && kCfgs[i].tn == c.tn && kCfgs[i].wvm == c.wvm &&
-        kCfgs[i].d == c.d && kCfgs[i].ks == c.ks)
-      return i;
-  return -1;
+// how the two families encode a shape as a table record (C8: wvm = 0 marks the
+// tiled family, cap carries the schedule)
+inline LdTuneCfg cfg_rec(const StreamCfg& c) {
+  return LdTuneCfg{c.tm, c.tn, c.wvm, c.d, c.ks};
 }
-
-inline int c8_cfg_index(const LdTuneCfg& c) {
-  for (int i = 0; i < kNumC8Cfgs; ++i)
-    if (kC8Cfgs[i].tm == c.tm && kC8Cfgs[i].tn == c.tn && kC8Cfgs[i].ks == c.ks &&
-        kC8Cfgs[i].d == c.d && kC8Cfgs[i].sch == c.cap && c.wvm == 0)
-      return i;
-  return -1;
+inline LdTuneCfg c8_cfg_rec(const StreamCfg& c) {
+  return LdTuneCfg{c.tm, c.tn, 0, c.d, c.ks, c.sch};
 }
 
 template <int MODE>
 int launch_c8(const ConvK& k, hipStream_t stream) {
   if (k.Cin % 32 != 0) return LD_EUNSUPPORTED;
+  auto launch = [&](const StreamCfg& c, int) { return launch_c8_cfg<MODE>(k, c, stream); };
   // "4x4x2", "4x4x2x64" or "4x4x4x32x1": BM/32 x BN/32 x NST [x BK [x SCH]]
-  if (const char* env = getenv("LD_CONV_C8_SHAPE")) {
+  auto forced = [&](int* rc) {
+    const char* env = getenv("LD_CONV_C8_SHAPE");
     StreamCfg c{0, 0, 0, 32, 0, 0};
-    if (sscanf(env, "%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.ks, &c.d, &c.sch) >= 3 &&
-        c8_cfg_fits(k, c)) {
-      const int rc = launch_c8_cfg<MODE>(k, c, stream);
-      if (rc != LD_EUNSUPPORTED) return rc;
-    }
-  }
-  int pick = -1;
-  LdTuneCfg t;
-  if (ld_tune_lookup(make_tune_key(MODE, 2, k), &t)) {
-    pick = c8_cfg_index(t);
-    if (pick >= 0 && !c8_cfg_fits(k, kC8Cfgs[pick])) pick = -1;
-  }
-  if (pick < 0) pick = c8_cfg_model(k);
-  if (pick < 0) return LD_EUNSUPPORTED;
-  return launch_c8_cfg<MODE>(k, kC8Cfgs[pick], stream);
+    if (!env || sscanf(env, "%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.ks, &c.d, &c.sch) < 3 ||
+        !c8_cfg_fits(k, c))
+      return false;
+    *rc = launch(c, 0);
+    return *rc != LD_EUNSUPPORTED;
+  };
+  return launch_picked(MODE, 2, k, kC8Cfgs, forced, c8_cfg_rec, c8_cfg_fits, c8_cfg_model,
+                       launch);
 }
 
 template <int MODE>
 int tune_c8(const ConvK& k, hipStream_t stream) {
   if (k.Cin % 32 != 0) return 1;
   const LdTuneKey key = make_tune_key(MODE, 2, k);
-  LdTuneCfg have;
-  if (ld_tune_lookup(key, &have)) return 1;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
-  if (cap != hipStreamCaptureStatusNone) return LD_EUNSUPPORTED;
+  if (int r = tune_refused(key, stream)) return r;
   int pick = c8_cfg_model(k);
   if (pick < 0) return 1;
-  (void)hipDeviceSynchronize();
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  constexpr int kReps = 3;
+  TuneTimer timer(stream);
   float best_ms = -1.0f;
   for (int i = 0; i < kNumC8Cfgs; ++i) {
     if (!c8_cfg_fits(k, kC8Cfgs[i])) continue;
-    if (launch_c8_cfg<MODE>(k, kC8Cfgs[i], stream) != 0) continue;
-    float ms = -1.0f;
-    for (int trial = 0; trial < 2; ++trial) {
-      (void)hipEventRecord(e0, stream);
-      for (int rep = 0; rep < kReps; ++rep) launch_c8_cfg<MODE>(k, kC8Cfgs[i], stream);
-      (void)hipEventRecord(e1, stream);
-      if (hipEventSynchronize(e1) != hipSuccess) break;
-      float t = 0.0f;
-      (void)hipEventElapsedTime(&t, e0, e1);
-      if (ms < 0.0f || t < ms) ms = t;
-    }
-    if (ms < 0.0f) continue;
-    if (best_ms < 0.0f || ms < best_ms) {
+    const float ms = timer.time([&] { return launch_c8_cfg<MODE>(k, kC8Cfgs[i], stream); });
+    if (ms >= 0.0f && (best_ms < 0.0f || ms < best_ms)) {
       best_ms = ms;
       pick = i;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   const StreamCfg& c = kC8Cfgs[pick];
-  if (const char* lg = getenv("LD_CONV_TUNE_LOG"))
-    if (lg[0] == '1') {
-      const double fl = 2.0 * k.J * k.Cout * k.Cin * mode_taps(k);
-      fprintf(stderr,
-              "[ld_conv c8] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
-              "%dx%dx%d bk%d sch%d  %.1f TFLOP/s\n",
-              MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels,
-              c.tm * 32, c.tn * 32, c.ks, c.d, c.sch,
-              best_ms > 0 ? fl / (best_ms * 1e-3 / kReps) / 1e12 : 0.0);
-    }
-  if (best_ms > 0.0f) ld_tune_store(key, LdTuneCfg{c.tm, c.tn, 0, c.d, c.ks, c.sch});
+  if (tune_log_level() == 1)
+    fprintf(stderr,
+            "[ld_conv c8] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
+            "%dx%dx%d bk%d sch%d  %.1f TFLOP/s\n",
+            MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels,
+            c.tm * 32, c.tn * 32, c.ks, c.d, c.sch,
+            tune_tflops(2.0 * k.J * k.Cout * k.Cin * mode_taps(k), best_ms));
+  if (best_ms > 0.0f) ld_tune_store(key, c8_cfg_rec(c));
   return 0;
 }
 
@@ -2178,23 +2143,17 @@ template <int MODE>
 int launch_bf16(const ConvK& k, hipStream_t stream) {
   if (k.x_c8) return launch_c8<MODE>(k, stream);
   if (k.Cin % 16 != 0) return LD_EUNSUPPORTED;
-  if (const char* env = getenv("LD_CONV_BF16_SHAPE")) {  // "2x2x2x4x1": force a shape
+  auto launch = [&](const StreamCfg& c, int) { return launch_cfg<MODE>(k, c, stream); };
+  auto forced = [&](int* rc) {  // "2x2x2x4x1": force a shape
+    const char* env = getenv("LD_CONV_BF16_SHAPE");
     StreamCfg c;
-    if (sscanf(env, "%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.wvm, &c.d, &c.ks) == 5 &&
-        (c.wvm == 0 || (k.Cin / 16) % c.d == 0)) {
-      const int rc = launch_cfg<MODE>(k, c, stream);
-      if (rc != LD_EUNSUPPORTED) return rc;
-    }
-  }
-  int pick = -1;
-  LdTuneCfg t;
-  if (ld_tune_lookup(make_tune_key(MODE, 1, k), &t)) {
-    pick = cfg_index(t);
-    if (pick >= 0 && !cfg_fits(k, kCfgs[pick])) pick = -1;
-  }
-  if (pick < 0) pick = cfg_model(k);
-  if (pick < 0) return LD_EUNSUPPORTED;
-  return launch_cfg<MODE>(k, kCfgs[pick], stream);
+    if (!env || sscanf(env, "%dx%dx%dx%dx%d", &c.tm, &c.tn, &c.wvm, &c.d, &c.ks) != 5 ||
+        !(c.wvm == 0 || (k.Cin / 16) % c.d == 0))
+      return false;
+    *rc = launch(c, 0);
+    return *rc != LD_EUNSUPPORTED;
+  };
+  return launch_picked(MODE, 1, k, kCfgs, forced, cfg_rec, cfg_fits, cfg_model, launch);
 }
 
 template <int MODE>
@@ -2202,52 +2161,28 @@ int tune_bf16(const ConvK& k, hipStream_t stream) {
   if (k.x_c8) return tune_c8<MODE>(k, stream);
   if (k.Cin % 16 != 0) return 1;
   const LdTuneKey key = make_tune_key(MODE, 1, k);
-  LdTuneCfg have;
-  if (ld_tune_lookup(key, &have)) return 1;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
-  if (cap != hipStreamCaptureStatusNone) return LD_EUNSUPPORTED;
+  if (int r = tune_refused(key, stream)) return r;
   int pick = cfg_model(k);
   if (pick < 0) return 1;
-  (void)hipDeviceSynchronize();
-  hipEvent_t e0, e1;
-  (void)hipEventCreate(&e0);
-  (void)hipEventCreate(&e1);
-  constexpr int kReps = 3;
+  TuneTimer timer(stream);
   float best_ms = -1.0f;
   for (int i = 0; i < kNumCfgs; ++i) {
     if (!cfg_fits(k, kCfgs[i])) continue;
-    if (launch_cfg<MODE>(k, kCfgs[i], stream) != 0) continue;
-    float ms = -1.0f;
-    for (int trial = 0; trial < 2; ++trial) {
-      (void)hipEventRecord(e0, stream);
-      for (int rep = 0; rep < kReps; ++rep) launch_cfg<MODE>(k, kCfgs[i], stream);
-      (void)hipEventRecord(e1, stream);
-      if (hipEventSynchronize(e1) != hipSuccess) break;
-      float t = 0.0f;
-      (void)hipEventElapsedTime(&t, e0, e1);
-      if (ms < 0.0f || t < ms) ms = t;
-    }
-    if (ms < 0.0f) continue;
-    if (best_ms < 0.0f || ms < best_ms) {
+    const float ms = timer.time([&] { return launch_cfg<MODE>(k, kCfgs[i], stream); });
+    if (ms >= 0.0f && (best_ms < 0.0f || ms < best_ms)) {
       best_ms = ms;
       pick = i;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   const StreamCfg& c = kCfgs[pick];
-  if (const char* lg = getenv("LD_CONV_TUNE_LOG"))
-    if (lg[0] == '1') {
-      const double fl = 2.0 * k.J * k.Cout * k.Cin * mode_taps(k);
-      fprintf(stderr,
-              "[ld_conv bf16] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
-              "%dx%dx%dx%dx%d  %.1f TFLOP/s\n",
-              MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels, c.tm,
-              c.tn, c.wvm, c.d, c.ks,
-              best_ms > 0 ? fl / (best_ms * 1e-3 / kReps) / 1e12 : 0.0);
-    }
-  if (best_ms > 0.0f) ld_tune_store(key, LdTuneCfg{c.tm, c.tn, c.wvm, c.d, c.ks});
+  if (tune_log_level() == 1)
+    fprintf(stderr,
+            "[ld_conv bf16] mode %d Cin %d Cout %d k %dx%d s%d J %d lv %d -> "
+            "%dx%dx%dx%dx%d  %.1f TFLOP/s\n",
+            MODE, k.Cin, k.Cout, k.KH, k.KW, k.g.stride, k.J, k.g.num_levels, c.tm,
+            c.tn, c.wvm, c.d, c.ks,
+            tune_tflops(2.0 * k.J * k.Cout * k.Cin * mode_taps(k), best_ms));
+  if (best_ms > 0.0f) ld_tune_store(key, cfg_rec(c));
   return 0;
 }
 

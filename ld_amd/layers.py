@@ -6,6 +6,7 @@ handled in the (N, C, P) form: P = H*W for an ordinary NCHW map, or the sum of
 the per-level H_l*W_l of a level-concatenated FPN/head tensor (``levels`` is
 the tuple of (H, W) per level).
 """
+import collections
 import ctypes as C
 
 import torch
@@ -652,6 +653,23 @@ def _tune_once(kind, d, ep_flags, call):
         L.check(rc, 'ld_conv_tune_' + kind)
 
 
+# The C entry points of the three operand families -- 0: fp32, 1: bf16 MFMA on
+# fp32 operands, 2: bf16 MFMA on C8 images -- with the suffix of their
+# ``_timed`` kinds and the prefix of their ``_tune_once`` kinds.
+_Family = collections.namedtuple(
+    '_Family', 'forward tune_forward dgrad dgrad_acc tune_dgrad wgrad timed tune')
+_FAMILIES = (
+    _Family('ld_conv_forward', 'ld_conv_tune_forward', 'ld_conv_dgrad',
+            'ld_conv_dgrad_acc', 'ld_conv_tune_dgrad', 'ld_conv_wgrad', '', ''),
+    _Family('ld_conv_bf16_forward', 'ld_conv_bf16_tune_forward',
+            'ld_conv_bf16_dgrad', 'ld_conv_bf16_dgrad_acc',
+            'ld_conv_bf16_tune_dgrad', 'ld_conv_bf16_wgrad', '_bf16', 'bf16_'),
+    _Family('ld_conv_bf16_forward_c8', 'ld_conv_bf16_tune_forward_c8',
+            'ld_conv_bf16_dgrad_c8', 'ld_conv_bf16_dgrad_c8_acc',
+            'ld_conv_bf16_tune_dgrad_c8', 'ld_conv_bf16_wgrad_c8', '_bf16', 'c8_'),
+)
+
+
 def _epilogue(bias=None, scale=None, shift=None, residual=None, relu=False,
               y_c8=None):
     ep = L.ConvEpilogueT()
@@ -730,19 +748,16 @@ def conv_forward_raw(x3, w, stride, pad, levels, bias=None, scale=None,
                             'bias, no fp32 y_raw and an (N*Cout*Pout) bf16 buffer')
         ep.y_raw_c8 = y_raw_c8.data_ptr()
         L.keep(y_raw_c8)
-    fn = lib.ld_conv_forward_smallc if smallc else (
-        lib.ld_conv_bf16_forward_c8 if c8 else
-        lib.ld_conv_bf16_forward if bf16 else lib.ld_conv_forward)
-    with _timed('conv_fwd_bf16' if bf16 else 'conv_fwd', d,
+    fam = _FAMILIES[2 if c8 else 1 if bf16 else 0]
+    # the small-channel stem has one entry point of its own and no tuner
+    fn = lib.ld_conv_forward_smallc if smallc else getattr(lib, fam.forward)
+    with _timed('conv_fwd' + fam.timed, d,
                 fused=(int(residual is not None), int(y_raw is not None))):
         # the conversion launch is part of the conv's measured time
         xin = x3.buf if in8 else to_c8(x3) if c8 else x3
         if not smallc:
-            tune = lib.ld_conv_bf16_tune_forward_c8 if c8 else \
-                lib.ld_conv_bf16_tune_forward if bf16 else \
-                lib.ld_conv_tune_forward
-            _tune_once('c8_forward' if c8 else
-                       'bf16_forward' if bf16 else 'forward', d,
+            tune = getattr(lib, fam.tune_forward)
+            _tune_once(fam.tune + 'forward', d,
                        (bias is not None, scale is not None,
                         residual is not None, bool(relu)),
                        lambda: tune(C.byref(d), L.ptr(xin), L.ptr(wt_fwd),
@@ -1118,6 +1133,208 @@ def fan_give(c, g):
     return g
 
 
+def _conv_dgrad(lib, w, dy, d, meta, addend):
+    """dx = conv_transpose(dy) (+ addend): the data gradient of _conv_backward."""
+    stride, pad, levels, _ = meta
+    dy8 = isinstance(dy, C8Act)
+    N, cin = d.N, d.Cin
+    cout, _, kh, kw = w.shape
+    st = L.stream_ptr(dy.device)
+    bf16 = _use_bf16(cout)  # the data gradient reduces over Cout
+    d_x, dy_x = d, dy  # descriptor / operand of the data gradient
+    if not bf16 and _PAD_DGRAD[0] and _PRECISION[0] == 'bf16' and \
+            not dy8 and cin >= 16 and dy.dim() == 3:
+        # Cout % 16 != 0 (gfl_reg: 68 corner logits): the bf16 weight image
+        # of the data gradient is zero-padded to 16 channels anyway -- pad
+        # dY with zero channels to match and take the bf16 kernel instead of
+        # the fp32 one (round 6: 184 -> ~80 us at the head of the backward)
+        coutp = (cout + 15) // 16 * 16
+        dy_x = torch.empty((N, coutp, dy.shape[2]), dtype=torch.float32,
+                           device=dy.device)
+        dy_x[:, :cout].copy_(dy)
+        dy_x[:, cout:].zero_()
+        d_x, _ = conv_desc(N, cin, coutp, kh, kw, stride, pad, levels)
+        bf16 = True
+    _, wt_bwd = weight_images(w, True, bf16=bf16, need_fwd=False)
+    dx = torch.empty((N, cin, d.Pin), dtype=torch.float32,
+                     device=dy.device)
+    c8 = bf16 and (dy8 or (dy_x is dy and
+                           _use_c8(cout, kh, stride, N * d.Pin, dy)))
+    fam = _FAMILIES[2 if c8 else 1 if bf16 else 0]
+    tune, dgrad, dgrad_acc = (getattr(lib, n) for n in (
+        fam.tune_dgrad, fam.dgrad, fam.dgrad_acc))
+    with _timed('conv_dgrad' + fam.timed, d,
+                fused=(int(addend is not None), 0)):
+        dyin = dy.buf if dy8 else to_c8(dy) if c8 else dy_x
+        _tune_once(fam.tune + 'dgrad', d_x, (),
+                   lambda: tune(C.byref(d_x), L.ptr(dyin),
+                                L.ptr(wt_bwd), L.ptr(dx), st))
+        if addend is not None:
+            # the other consumers' gradient of this input, summed in the
+            # GEMM epilogue (fan protocol above)
+            if addend.numel() != dx.numel() or not addend.is_contiguous():
+                raise L.LdError('conv dgrad: addend shape mismatch')
+            if stride == 2 and kh == 1 and _FAN_INPLACE[0] and \
+                    getattr(addend, '_ld_fresh', False):
+                # 1x1 stride 2 reaches a quarter of the positions; the rest
+                # of dx IS the addend -- accumulate in place into the
+                # (exclusively owned) buffer another conv's data gradient
+                # deposited instead of copying it first
+                dx = addend.view(dx.shape)
+            L.check(dgrad_acc(C.byref(d_x), L.ptr(dyin), L.ptr(wt_bwd),
+                              L.ptr(addend), L.ptr(dx), st),
+                    'ld_conv_dgrad_acc')
+        else:
+            L.check(dgrad(C.byref(d_x), L.ptr(dyin), L.ptr(wt_bwd),
+                          L.ptr(dx), st), 'ld_conv_dgrad')
+    dx._ld_fresh = True  # nobody else holds this tensor yet
+    return dx
+
+
+def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
+    """The weight gradient of _conv_backward; None: into the gradient arena."""
+    dy8 = isinstance(dy, C8Act)
+    cin = d.Cin
+    st = L.stream_ptr(dy.device)
+    sink = _sink(pw)
+    dw = sink if sink is not None else torch.empty_like(w)
+    need = lib.ld_conv_wgrad_workspace_bytes(C.byref(d))
+    ws = None if sink is not None and _DEFER_ON[0] else \
+        workspace(dy.device, need, 'wgrad')
+    bf16 = _PRECISION[0] == 'bf16' and cin >= 16
+    family = 2 if c8w else 1 if bf16 else 0
+    fam = _FAMILIES[family]
+    wgrad = getattr(lib, fam.wgrad)
+    side = None
+    # Round 3: eager bf16 steps were HOST-bound (~14 ms of enqueue per 15.5 ms
+    # step) and the three extra stream calls per weight gradient cost more
+    # host time than the overlap returned (15.56 -> 17.31 ms), so bf16 used
+    # the side stream only inside hipGraph captures.  Round 5: the step is
+    # GPU-bound (launch lists, fan protocol, deferred finalisation) and its
+    # main queue is the critical path (65 % busy against 22 % on the side
+    # queue, profiles/r05_queue_busy_bf16.txt): with the weight gradients
+    # behind the teacher on the side stream 13.46 -> 12.42 ms per step
+    # (profiles/r05_bf16_wgrad_side_stream.txt).  LD_WGRAD_STREAM_BF16=0
+    # restores the old placement.  fp32: 36.88 -> 35.98 ms eager
+    # (profiles/r03_wgrad_side_stream.txt).
+    if sink is not None and _WGRAD_STREAM[0] and \
+            dy.device.type == 'cuda' and \
+            KernelProfile.active is None and (
+                _PRECISION[0] != 'bf16' or _WGRAD_FORCE[0] or
+                _WGRAD_BF16_EAGER[0] or
+                torch.cuda.is_current_stream_capturing()):
+        side = _wgrad_side(dy.device)
+    if family == 0:
+        # explicit tuning writes its result with accumulate = 0: into a
+        # scratch dW, never into the gradient arena
+        def _tune_wgrad():
+            # the tuner times every candidate plan: its own, larger workspace
+            tws = torch.empty(lib.ld_conv_tune_wgrad_workspace_bytes(
+                C.byref(d)), dtype=torch.uint8, device=dy.device)
+            return lib.ld_conv_tune_wgrad(
+                C.byref(d), L.ptr(x3), L.ptr(dy),
+                L.ptr(torch.empty_like(w)), L.ptr(tws), tws.numel(), st)
+        _tune_once('wgrad', d, (), _tune_wgrad)
+    # with a gradient arena only the split partials are computed here; their
+    # sum runs once per bucket (flush_deferred)
+    defer = sink is not None and _DEFER_ON[0]
+    if defer and any(j.dw == sink.data_ptr() for j, _ in _DEFER_W):
+        # a weight used twice: its slabs are still pending, possibly on the
+        # side stream
+        wgrad_join()
+        flush_deferred()
+
+    def _launch(ws_, stream_ptr):
+        if not defer:
+            L.check(wgrad(C.byref(d), L.ptr(xw), L.ptr(dyw), L.ptr(dw),
+                          0 if sink is None else 1, L.ptr(ws_),
+                          ws_.numel(), stream_ptr), 'ld_conv_wgrad')
+            return
+        slabs = _defer_buffer(pw, '_ld_slabs', need, dy.device)
+        job = L.WgradJobT()
+        L.check(lib.ld_conv_wgrad_partial(
+            C.byref(d), family, L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
+            slabs.numel(), C.byref(job), stream_ptr),
+            'ld_conv_wgrad_partial')
+        job.dw, job.accumulate = sink.data_ptr(), 1
+        _DEFER_W.append((job, dy.device))
+        DEFER_STATS['wgrad_jobs'] += 1
+
+    with _timed('conv_wgrad' + fam.timed, d):
+        # operand images are produced on the main stream (cached ones cost
+        # nothing); the wgrad itself may go to the side stream
+        xw, dyw = ((x3.buf if x8 is not None else to_c8(x3)),
+                   dy.buf if dy8 else to_c8(dy)) if c8w else (x3, dy)
+        if side is None:
+            _launch(ws, st)
+        elif defer and not torch.cuda.is_current_stream_capturing():
+            # no workspace, no host-side stream switch: fork the side stream
+            # off the main one with ONE C call and hand the launch its raw
+            # pointer (~65 weight gradients per step; the torch calls below
+            # are ~25 us of host time each, this path ~6)
+            sp = C.c_void_p(side.cuda_stream)
+            L.check(lib.ld_stream_fork(st, sp), 'ld_stream_fork')
+            _launch(ws, sp)
+            for t in (xw, dyw):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(side)
+            _WGRAD_PENDING[0] = True
+        else:
+            side.wait_stream(torch.cuda.current_stream(dy.device))
+            with torch.cuda.stream(side):
+                ws2 = ws if defer else workspace(dy.device, need,
+                                                 'wgrad')  # per stream
+                _launch(ws2, L.stream_ptr(dy.device))
+            # the caching allocator must not hand these blocks to later
+            # main-stream allocations while the side stream still reads them
+            for t in (xw, dyw):
+                if isinstance(t, torch.Tensor):
+                    t.record_stream(side)
+            _WGRAD_PENDING[0] = True
+    if sink is not None:
+        _emit(pw)
+        return None
+    return dw
+
+
+def _conv_bias_grad(lib, dy, d, pb):
+    """The bias gradient of _conv_backward; None: into the gradient arena."""
+    N, cout = d.N, d.Cout
+    st = L.stream_ptr(dy.device)
+    sink = _sink(pb)
+    if sink is not None and _DEFER_ON[0]:
+        # per-channel partial sums now, finalised with the bucket's norm
+        # gradients (ld_bn_bwd_finalize_batch, a job without dgamma)
+        if any(j.dbeta == sink.data_ptr() for j, _ in _DEFER_B):
+            # flush_deferred also reduces the pending WEIGHT slabs, which the
+            # side stream may still be writing (ADVICE r5)
+            wgrad_join(dy.device)
+            flush_deferred()
+        ns = lib.ld_bias_grad_nsplit(N, cout, dy.shape[2])
+        part = _defer_buffer(pb, '_ld_bias_partial', cout * ns * 16,
+                             dy.device)
+        L.check(lib.ld_bias_grad_partial(L.ptr(dy), N, cout, dy.shape[2],
+                                         L.ptr(part), part.numel(), st),
+                'ld_bias_grad_partial')
+        job = L.BnFinJobT()
+        job.partial, job.dgamma, job.dbeta = (part.data_ptr(), None,
+                                              sink.data_ptr())
+        job.C, job.nsplit, job.accumulate = cout, ns, 1
+        _DEFER_B.append((job, dy.device))
+        DEFER_STATS['bn_jobs'] += 1
+        _emit(pb)
+        return None
+    db = sink if sink is not None else \
+        torch.empty(cout, dtype=torch.float32, device=dy.device)
+    L.check(lib.ld_bias_grad(L.ptr(dy), N, cout, dy.shape[2],
+                             L.ptr(db), 0 if sink is None else 1, st),
+            'ld_bias_grad')
+    if sink is not None:
+        _emit(pb)
+        return None
+    return db
+
+
 def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
                    addend=None):
     """Data / weight / bias gradients of a conv (shared by ConvFn and the fused
@@ -1136,7 +1353,6 @@ def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
     N, cin, _ = x3.shape
     cout, _, kh, kw = w.shape
     d, _ = conv_desc(N, cin, cout, kh, kw, stride, pad, levels)
-    st = L.stream_ptr(dy.device)
     dx = dw = db = None
     # bf16 + C8: the weight gradient takes both operands as C8 images
     # (ld_conv_bf16_wgrad_c8); converting dy first lets the data gradient
@@ -1157,192 +1373,13 @@ def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
         raise L.LdError('a C8-only activation feeds this conv: its weight '
                         'gradient needs the C8 wgrad kernel (bf16 mode, '
                         'channel counts % 32 == 0, LD_WGRAD_C8 on)')
-    if need_x:
-        bf16 = _use_bf16(cout)  # the data gradient reduces over Cout
-        d_x, dy_x = d, dy  # descriptor / operand of the data gradient
-        if not bf16 and _PAD_DGRAD[0] and _PRECISION[0] == 'bf16' and \
-                not dy8 and cin >= 16 and dy.dim() == 3:
-            # Cout % 16 != 0 (gfl_reg: 68 corner logits): the bf16 weight image
-            # of the data gradient is zero-padded to 16 channels anyway -- pad
-            # dY with zero channels to match and take the bf16 kernel instead of
-            # the fp32 one (round 6: 184 -> ~80 us at the head of the backward)
-            coutp = (cout + 15) // 16 * 16
-            dy_x = torch.empty((N, coutp, dy.shape[2]), dtype=torch.float32,
-                               device=dy.device)
-            dy_x[:, :cout].copy_(dy)
-            dy_x[:, cout:].zero_()
-            d_x, _ = conv_desc(N, cin, coutp, kh, kw, stride, pad, levels)
-            bf16 = True
-        _, wt_bwd = weight_images(w, True, bf16=bf16, need_fwd=False)
-        dx = torch.empty((N, cin, d.Pin), dtype=torch.float32,
-                         device=dy.device)
-        c8 = bf16 and (dy8 or (dy_x is dy and
-                               _use_c8(cout, kh, stride, N * d.Pin, dy)))
-        tune = lib.ld_conv_bf16_tune_dgrad_c8 if c8 else \
-            lib.ld_conv_bf16_tune_dgrad if bf16 else \
-            lib.ld_conv_tune_dgrad
-        dgrad = lib.ld_conv_bf16_dgrad_c8 if c8 else \
-            lib.ld_conv_bf16_dgrad if bf16 else lib.ld_conv_dgrad
-        dgrad_acc = lib.ld_conv_bf16_dgrad_c8_acc if c8 else \
-            lib.ld_conv_bf16_dgrad_acc if bf16 else lib.ld_conv_dgrad_acc
-        with _timed('conv_dgrad_bf16' if bf16 else 'conv_dgrad', d,
-                    fused=(int(addend is not None), 0)):
-            dyin = dy.buf if dy8 else to_c8(dy) if c8 else dy_x
-            _tune_once('c8_dgrad' if c8 else
-                       'bf16_dgrad' if bf16 else 'dgrad', d_x, (),
-                       lambda: tune(C.byref(d_x), L.ptr(dyin),
-                                    L.ptr(wt_bwd), L.ptr(dx), st))
-            if addend is not None:
-                # the other consumers' gradient of this input, summed in the
-                # GEMM epilogue (fan protocol above)
-                if addend.numel() != dx.numel() or not addend.is_contiguous():
-                    raise L.LdError('conv dgrad: addend shape mismatch')
-                if stride == 2 and kh == 1 and _FAN_INPLACE[0] and \
-                        getattr(addend, '_ld_fresh', False):
-                    # 1x1 stride 2 reaches a quarter of the positions; the rest
-                    # of dx IS the addend -- accumulate in place into the
-                    # (exclusively owned) buffer another conv's data gradient
-                    # deposited instead of copying it first
-                    dx = addend.view(dx.shape)
-                L.check(dgrad_acc(C.byref(d_x), L.ptr(dyin), L.ptr(wt_bwd),
-                                  L.ptr(addend), L.ptr(dx), st),
-                        'ld_conv_dgrad_acc')
-            else:
-                L.check(dgrad(C.byref(d_x), L.ptr(dyin), L.ptr(wt_bwd),
-                              L.ptr(dx), st), 'ld_conv_dgrad')
-        dx._ld_fresh = True  # nobody else holds this tensor yet
     pw, pb = params
+    if need_x:
+        dx = _conv_dgrad(lib, w, dy, d, meta, addend)
     if need_w:
-        sink = _sink(pw)
-        dw = sink if sink is not None else torch.empty_like(w)
-        need = lib.ld_conv_wgrad_workspace_bytes(C.byref(d))
-        ws = None if sink is not None and _DEFER_ON[0] else \
-            workspace(dy.device, need, 'wgrad')
-        bf16 = _PRECISION[0] == 'bf16' and cin >= 16
-        wgrad = lib.ld_conv_bf16_wgrad_c8 if c8w else \
-            lib.ld_conv_bf16_wgrad if bf16 else lib.ld_conv_wgrad
-        side = None
-        # Round 3: eager bf16 steps were HOST-bound (~14 ms of enqueue per 15.5 ms
-        # step) and the three extra stream calls per weight gradient cost more
-        # host time than the overlap returned (15.56 -> 17.31 ms), so bf16 used
-        # the side stream only inside hipGraph captures.  Round 5: the step is
-        # GPU-bound (launch lists, fan protocol, deferred finalisation) and its
-        # main queue is the critical path (65 % busy against 22 % on the side
-        # queue, profiles/r05_queue_busy_bf16.txt): with the weight gradients
-        # behind the teacher on the side stream 13.46 -> 12.42 ms per step
-        # (profiles/r05_bf16_wgrad_side_stream.txt).  LD_WGRAD_STREAM_BF16=0
-        # restores the old placement.  fp32: 36.88 -> 35.98 ms eager
-        # (profiles/r03_wgrad_side_stream.txt).
-        if sink is not None and _WGRAD_STREAM[0] and \
-                dy.device.type == 'cuda' and \
-                KernelProfile.active is None and (
-                    _PRECISION[0] != 'bf16' or _WGRAD_FORCE[0] or
-                    _WGRAD_BF16_EAGER[0] or
-                    torch.cuda.is_current_stream_capturing()):
-            side = _wgrad_side(dy.device)
-        if not bf16 and not c8w:
-            # explicit tuning writes its result with accumulate = 0: into a
-            # scratch dW, never into the gradient arena
-            def _tune_wgrad():
-                # the tuner times every candidate plan: its own, larger workspace
-                tws = torch.empty(lib.ld_conv_tune_wgrad_workspace_bytes(
-                    C.byref(d)), dtype=torch.uint8, device=dy.device)
-                return lib.ld_conv_tune_wgrad(
-                    C.byref(d), L.ptr(x3), L.ptr(dy),
-                    L.ptr(torch.empty_like(w)), L.ptr(tws), tws.numel(), st)
-            _tune_once('wgrad', d, (), _tune_wgrad)
-        # with a gradient arena only the split partials are computed here; their
-        # sum runs once per bucket (flush_deferred)
-        defer = sink is not None and _DEFER_ON[0]
-        if defer and any(j.dw == sink.data_ptr() for j, _ in _DEFER_W):
-            # a weight used twice: its slabs are still pending, possibly on the
-            # side stream
-            wgrad_join()
-            flush_deferred()
-        family = 2 if c8w else 1 if bf16 else 0
-
-        def _launch(ws_, stream_ptr):
-            if not defer:
-                L.check(wgrad(C.byref(d), L.ptr(xw), L.ptr(dyw), L.ptr(dw),
-                              0 if sink is None else 1, L.ptr(ws_),
-                              ws_.numel(), stream_ptr), 'ld_conv_wgrad')
-                return
-            slabs = _defer_buffer(pw, '_ld_slabs', need, dy.device)
-            job = L.WgradJobT()
-            L.check(lib.ld_conv_wgrad_partial(
-                C.byref(d), family, L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
-                slabs.numel(), C.byref(job), stream_ptr),
-                'ld_conv_wgrad_partial')
-            job.dw, job.accumulate = sink.data_ptr(), 1
-            _DEFER_W.append((job, dy.device))
-            DEFER_STATS['wgrad_jobs'] += 1
-
-        with _timed('conv_wgrad_bf16' if bf16 else 'conv_wgrad', d):
-            # operand images are produced on the main stream (cached ones cost
-            # nothing); the wgrad itself may go to the side stream
-            xw, dyw = ((x3.buf if x8 is not None else to_c8(x3)),
-                       dy.buf if dy8 else to_c8(dy)) if c8w else (x3, dy)
-            if side is None:
-                _launch(ws, st)
-            elif defer and not torch.cuda.is_current_stream_capturing():
-                # no workspace, no host-side stream switch: fork the side stream
-                # off the main one with ONE C call and hand the launch its raw
-                # pointer (~65 weight gradients per step; the torch calls below
-                # are ~25 us of host time each, this path ~6)
-                sp = C.c_void_p(side.cuda_stream)
-                L.check(lib.ld_stream_fork(st, sp), 'ld_stream_fork')
-                _launch(ws, sp)
-                for t in (xw, dyw):
-                    if isinstance(t, torch.Tensor):
-                        t.record_stream(side)
-                _WGRAD_PENDING[0] = True
-            else:
-                side.wait_stream(torch.cuda.current_stream(dy.device))
-                with torch.cuda.stream(side):
-                    ws2 = ws if defer else workspace(dy.device, need,
-                                                     'wgrad')  # per stream
-                    _launch(ws2, L.stream_ptr(dy.device))
-                # the caching allocator must not hand these blocks to later
-                # main-stream allocations while the side stream still reads them
-                for t in (xw, dyw):
-                    if isinstance(t, torch.Tensor):
-                        t.record_stream(side)
-                _WGRAD_PENDING[0] = True
-        if sink is not None:
-            dw = None
-            _emit(pw)
+        dw = _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w)
     if has_bias and need_b:
-        sink = _sink(pb)
-        if sink is not None and _DEFER_ON[0]:
-            # per-channel partial sums now, finalised with the bucket's norm
-            # gradients (ld_bn_bwd_finalize_batch, a job without dgamma)
-            if any(j.dbeta == sink.data_ptr() for j, _ in _DEFER_B):
-                # flush_deferred also reduces the pending WEIGHT slabs, which the
-                # side stream may still be writing
-                wgrad_join(dy.device)
-                flush_deferred()
-            ns = lib.ld_bias_grad_nsplit(N, cout, dy.shape[2])
-            part = _defer_buffer(pb, '_ld_bias_partial', cout * ns * 16,
-                                 dy.device)
-            L.check(lib.ld_bias_grad_partial(L.ptr(dy), N, cout, dy.shape[2],
-                                             L.ptr(part), part.numel(), st),
-                    'ld_bias_grad_partial')
-            job = L.BnFinJobT()
-            job.partial, job.dgamma, job.dbeta = (part.data_ptr(), None,
-                                                  sink.data_ptr())
-            job.C, job.nsplit, job.accumulate = cout, ns, 1
-            _DEFER_B.append((job, dy.device))
-            DEFER_STATS['bn_jobs'] += 1
-            _emit(pb)
-            return dx, dw, None
-        db = sink if sink is not None else \
-            torch.empty(cout, dtype=torch.float32, device=dy.device)
-        L.check(lib.ld_bias_grad(L.ptr(dy), N, cout, dy.shape[2],
-                                 L.ptr(db), 0 if sink is None else 1, st),
-                'ld_bias_grad')
-        if sink is not None:
-            db = None
-            _emit(pb)
+        db = _conv_bias_grad(lib, dy, d, pb)
     return dx, dw, db
 
 
