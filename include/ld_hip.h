@@ -1214,6 +1214,44 @@ int ld_eval_ap(int num_records, const float* rec_score, const int32_t* rec_seg,
                float* precision, float* ap, void* workspace, size_t workspace_bytes,
                ld_stream_t stream);
 
+/* ---- per-image mAP ranking (eval_image.hip, eval.hip) ----------------------
+ * bbox_map_eval of the reference (tools/analysis_tools/analyze_results.py:13-45)
+ * for every image of a packed batch in ONE launch, one workgroup per image:
+ * eval_map of that image alone (tpfp_default without area ranges, 'area' AP) at
+ * each of iou_thrs (HOST float64, num_thrs <= LD_EVAL_MAX_THRS; the fp32 IoU is
+ * compared with them in float64, so an fp32 comparison is its fp32 thresholds
+ * widened), the float32 mean over the classes that have a non-ignored GT in
+ * the image, then the float64 mean over the thresholds.  Writes
+ *   ap[(i * num_thrs + t) * num_classes + c]  fp32, 0 for a class without GT
+ *   has_gt[i * num_classes + c]               1 when image i has such a GT
+ *   map[i]                                    float64, 0 for an image without GT
+ * Sums follow numpy's pairwise order, so the results are the reference's bits.
+ * Images whose boxes fit LDS (256 detections, 128 GTs + ignored GTs) stay there;
+ * larger ones, or every image with LD_EVAL_IMAGE_NO_LDS, use the workspace. */
+#define LD_EVAL_IMAGE_NO_LDS 1
+size_t ld_eval_image_map_workspace_bytes(int num_dets, int num_imgs);
+int ld_eval_image_map(const ld_eval_batch_t* batch, int num_classes, int num_thrs,
+                      const double* iou_thrs, int flags, float* ap, uint8_t* has_gt,
+                      double* map, void* workspace, size_t workspace_bytes,
+                      ld_stream_t stream);
+
+/* Stable ascending sort of num_imgs DEVICE float64 scores: order[k] is the
+ * index of the k-th lowest score (equal scores keep index order), sorted[k] its
+ * score.  Scores must not be NaN. */
+size_t ld_rank_images_workspace_bytes(int num_imgs);
+int ld_rank_images(int num_imgs, const double* scores, int32_t* order, double* sorted,
+                   void* workspace, size_t workspace_bytes, ld_stream_t stream);
+
+/* Paints rectangle outlines into img (DEVICE uint8, height x width x 3, in
+ * place): the gt_boxes (g, 4) first, then the dets (m, 5) whose score >=
+ * score_thr, each over what is already there.  Coordinates are truncated to
+ * int32; a box covers x1..x2, y1..y2 inclusive and its outline is the band of
+ * `thickness` pixels inside each edge; pixels outside the image are dropped.
+ * Colors: channel 0 in bits 0-7, channel 1 in 8-15, channel 2 in 16-23. */
+int ld_draw_boxes(uint8_t* img, int height, int width, const float* gt_boxes, int num_gts,
+                  const float* dets, int num_dets, float score_thr, int thickness,
+                  uint32_t gt_color, uint32_t det_color, ld_stream_t stream);
+
 /* ---- COCO-style bbox evaluation (coco_eval.hip) ----------------------------
  * pycocotools' COCOeval(iouType='bbox') evaluate() + accumulate() as mmdet's
  * CocoDataset.evaluate runs them, float64 throughout.  Categories are indexed

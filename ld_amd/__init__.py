@@ -27,6 +27,8 @@ from . import core, losses, resnet, fpn, heads, detectors  # noqa: F401,E402
 from .registry import (build_backbone, build_detector, build_head,  # noqa
                        build_loss, build_neck)
 from .evaluation import MapAccumulator, eval_map  # noqa: F401,E402
+from .analyze_results import (ImageMapAnalyzer,  # noqa: F401,E402
+                              bbox_map_eval, draw_gt_det_bboxes)
 from .coco_eval import (CocoEvaluator, CocoGroundTruth,  # noqa: F401,E402
                         coco_evaluate)
 from .coco_analysis import (CocoErrorAnalysis,  # noqa: F401,E402

@@ -1,0 +1,320 @@
+"""Per-image mAP ranking on the device: the reference's
+``tools/analysis_tools/analyze_results.py`` -- ``bbox_map_eval`` (lines 13-45)
+for every image, the good / bad ``topk`` selection of
+``ResultVisualizer.evaluate_and_show`` (89-134) and the box overlay of the
+images it saves -- run by eval_image.hip (``ld_eval_image_map``,
+``ld_draw_boxes``) and ``ld_rank_images`` of eval.hip.
+
+``ImageMapAnalyzer`` takes detections where the heads leave them (device
+``(n, 5)`` + ``(n,)`` per image), scores every image of a batch in one launch
+and keeps the scores on the device; ``topk`` sorts them there.
+
+Numerics are the reference's for a one-image dataset: IoU fp32, recall
+float64, precision fp32, 'area' AP summed in float64 (numpy's pairwise order)
+and stored as float32, the mean over classes with GTs a float32 ``np.mean``,
+the mean over thresholds float64.  Equal scores in one class are ordered by
+position in the class array (stable), which the reference's ``np.argsort``
+leaves open.
+
+IoU thresholds: the reference compares fp32 IoUs with the ``np.float64``
+scalars of ``np.linspace(.5, .95, 10)``.  Under NumPy 2 promotion (the
+installed numpy, 2.x) that comparison is made in float64, and this module does
+the same: the kernel takes float64 thresholds.  (NumPy 1 value-based casting
+would compare in fp32, as ``ld_amd.eval_map`` does; the two differ only for an
+IoU between a threshold and its fp32 rounding.)
+"""
+import struct
+import zlib
+
+import numpy as np
+import torch
+
+from . import lib as L
+from .evaluation import _f32, _i64
+from .lossblock import workspace
+
+__all__ = ['bbox_map_eval', 'ImageMapAnalyzer', 'draw_gt_det_bboxes',
+           'write_png', 'default_iou_thrs']
+
+
+def default_iou_thrs():
+    """analyze_results.py:38-39, as float64."""
+    return np.linspace(
+        .5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
+
+
+def _device(device):
+    dev = torch.device(device) if device is not None else \
+        torch.device('cuda', torch.cuda.current_device())
+    if dev.type != 'cuda':
+        raise L.LdError(f'analyze_results: device {dev} is not a HIP device '
+                        '(there is no CPU path)')
+    return dev
+
+
+def eval_image_map(batch, num_classes, iou_thrs, no_lds=False):
+    """ld_eval_image_map on a packed batch (the dict ``evaluation.eval_tpfp``
+    takes) -> device (map (I,) f64, ap (I, T, C) f32, has_gt (I, C) u8)."""
+    lib = L.get_lib()
+    dev = batch['det_off'].device
+    b = L.EvalBatchT()
+    for k in ('dets', 'det_labels', 'det_off', 'gts', 'gt_labels', 'gt_off',
+              'ign', 'ign_labels', 'ign_off'):
+        setattr(b, k, L.ptr(batch[k]).value)
+    I = b.num_imgs = batch['det_off'].numel() - 1
+    b.num_dets = batch['dets'].shape[0]
+    b.num_gts = batch['gts'].shape[0]
+    b.num_ign = batch['ign'].shape[0]
+    T, C_ = len(iou_thrs), int(num_classes)
+    thr = (L.C.c_double * T)(*[float(t) for t in iou_thrs])
+    ap = torch.empty((I, T, C_), dtype=torch.float32, device=dev)
+    has_gt = torch.empty((I, C_), dtype=torch.uint8, device=dev)
+    m = torch.empty((I, ), dtype=torch.float64, device=dev)
+    ws = workspace(dev, lib.ld_eval_image_map_workspace_bytes(b.num_dets, I),
+                   'eval_image_map')
+    L.check(lib.ld_eval_image_map(
+        L.C.byref(b), C_, T, L.C.cast(thr, L.C.c_void_p),
+        L.LD_EVAL_IMAGE_NO_LDS if no_lds else 0, L.ptr(ap), L.ptr(has_gt),
+        L.ptr(m), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+        'ld_eval_image_map')
+    return m, ap, has_gt
+
+
+def rank_images(scores):
+    """ld_rank_images: device float64 (I,) -> (order int32 (I,), sorted f64
+    (I,)), ascending and stable."""
+    lib = L.get_lib()
+    dev = scores.device
+    L.require_device(scores, torch.float64, 'scores')
+    n = scores.numel()
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    ws = workspace(dev, lib.ld_rank_images_workspace_bytes(n), 'rank_images')
+    L.check(lib.ld_rank_images(n, L.ptr(scores), L.ptr(order), L.ptr(out),
+                               L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+            'ld_rank_images')
+    return order, out
+
+
+def _results_to_lists(results, annotations, num_classes):
+    """The reference's list forms -> the per-image lists ``add`` takes."""
+    if len(results) != len(annotations):
+        raise ValueError('add_results: one annotation per image')
+    dets, labels, gb, gl, ib, il = [], [], [], [], [], []
+    for res, ann in zip(results, annotations):
+        if isinstance(res, tuple):  # (bbox, segm): analyze_results.py:33-34
+            res = res[0]
+        if len(res) != num_classes:
+            raise ValueError(f'add_results: {len(res)} class arrays, '
+                             f'expected {num_classes}')
+        rows = [np.asarray(r, dtype=np.float32).reshape(-1, 5) for r in res]
+        dets.append(np.concatenate(rows))
+        labels.append(np.concatenate([
+            np.full((r.shape[0], ), c, dtype=np.int64)
+            for c, r in enumerate(rows)]))
+        gb.append(np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4))
+        gl.append(np.asarray(ann['labels']).reshape(-1))
+        # get_cls_results (mean_ap.py:258-262): labels_ignore decides
+        if ann.get('labels_ignore', None) is not None:
+            ib.append(np.asarray(ann['bboxes_ignore'],
+                                 dtype=np.float32).reshape(-1, 4))
+            il.append(np.asarray(ann['labels_ignore']).reshape(-1))
+        else:
+            ib.append(np.zeros((0, 4), dtype=np.float32))
+            il.append(np.zeros((0, ), dtype=np.int64))
+    return dets, labels, gb, gl, ib, il
+
+
+class ImageMapAnalyzer:
+    """Scores every image on its own (``bbox_map_eval``) and ranks them.
+
+    ``iou_thrs``: float64 thresholds, default ``default_iou_thrs()``; they
+    reach the kernel as float64 (see the module docstring)."""
+
+    def __init__(self, num_classes, iou_thrs=None, device=None):
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError('ImageMapAnalyzer: num_classes must be >= 1')
+        thrs = default_iou_thrs() if iou_thrs is None else \
+            np.atleast_1d(np.asarray(iou_thrs, dtype=np.float64))
+        if not 1 <= len(thrs) <= L.LD_EVAL_MAX_THRS:
+            raise ValueError(f'ImageMapAnalyzer: 1..{L.LD_EVAL_MAX_THRS} IoU '
+                             f'thresholds, got {len(thrs)}')
+        self.iou_thrs = thrs
+        self.device = _device(device)
+        self._no_lds = False  # tests: every image through the workspace route
+        self._map, self._ap, self._has_gt = [], [], []
+
+    def __len__(self):
+        return sum(m.numel() for m in self._map)
+
+    def add(self, det_bboxes, det_labels, gt_bboxes, gt_labels,
+            gt_bboxes_ignore=None, gt_labels_ignore=None):
+        """One batch: per-image lists of detections (n, 5) with labels (n,)
+        -- device tensors as ``get_bboxes`` / ``aug_test`` return them -- and
+        GTs (g, 4) / (g,), optionally ignored GTs.  Packed as
+        ``MapAccumulator.add`` packs them; one launch."""
+        B = len(det_bboxes)
+        if not (len(det_labels) == len(gt_bboxes) == len(gt_labels) == B):
+            raise ValueError('ImageMapAnalyzer.add: det_bboxes, det_labels, '
+                             'gt_bboxes and gt_labels need one entry per image')
+        if (gt_bboxes_ignore is None) != (gt_labels_ignore is None):
+            raise ValueError('ImageMapAnalyzer.add: gt_bboxes_ignore and '
+                             'gt_labels_ignore go together')
+        if gt_bboxes_ignore is not None and not \
+                len(gt_bboxes_ignore) == len(gt_labels_ignore) == B:
+            raise ValueError('ImageMapAnalyzer.add: one ignored-GT entry per '
+                             'image')
+        if B == 0:
+            return
+        dev = self.device
+        d = [_f32(x, dev, 5) for x in det_bboxes]
+        dl = [_i64(x, dev) for x in det_labels]
+        g = [_f32(x, dev, 4) for x in gt_bboxes]
+        gl = [_i64(x, dev) for x in gt_labels]
+        if gt_bboxes_ignore is None:
+            ig = [torch.zeros((0, 4), dtype=torch.float32, device=dev)] * B
+            il = [torch.zeros((0, ), dtype=torch.int64, device=dev)] * B
+        else:
+            ig = [_f32(x, dev, 4) for x in gt_bboxes_ignore]
+            il = [_i64(x, dev) for x in gt_labels_ignore]
+        for a, b, what in ((d, dl, 'detections'), (g, gl, 'GTs'),
+                           (ig, il, 'ignored GTs')):
+            for x, y in zip(a, b):
+                if x.shape[0] != y.shape[0]:
+                    raise ValueError(f'ImageMapAnalyzer.add: {what} and their '
+                                     'labels differ in length')
+
+        def pack(rows):
+            off = np.zeros(B + 1, dtype=np.int32)
+            off[1:] = np.cumsum([r.shape[0] for r in rows])
+            return torch.cat(rows).contiguous(), \
+                torch.from_numpy(off).to(dev)
+
+        batch = {}
+        batch['dets'], batch['det_off'] = pack(d)
+        batch['det_labels'] = torch.cat(dl).contiguous()
+        batch['gts'], batch['gt_off'] = pack(g)
+        batch['gt_labels'] = torch.cat(gl).contiguous()
+        batch['ign'], batch['ign_off'] = pack(ig)
+        batch['ign_labels'] = torch.cat(il).contiguous()
+        m, ap, has_gt = eval_image_map(batch, self.num_classes, self.iou_thrs,
+                                       self._no_lds)
+        self._map.append(m)
+        self._ap.append(ap)
+        self._has_gt.append(has_gt)
+
+    def add_results(self, results, annotations):
+        """The reference's forms: ``results[i]`` a list of per-class (k, 5)
+        arrays (or a ``(bbox, segm)`` tuple), ``annotations[i]`` a dict of
+        ``bboxes`` / ``labels`` and optional ``bboxes_ignore`` /
+        ``labels_ignore``."""
+        self.add(*_results_to_lists(results, annotations, self.num_classes))
+
+    def _cat(self, parts, shape, dtype):
+        if not parts:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def compute(self):
+        """-> device tensors ``map`` (I,) float64 and ``ap`` (I, T, C)
+        float32, images in the order they were added."""
+        T, C_ = len(self.iou_thrs), self.num_classes
+        return (self._cat(self._map, (0, ), torch.float64),
+                self._cat(self._ap, (0, T, C_), torch.float32))
+
+    def has_gt(self):
+        """-> device (I, C) uint8: the class has a non-ignored GT in the
+        image."""
+        return self._cat(self._has_gt, (0, self.num_classes), torch.uint8)
+
+    def topk(self, k):
+        """analyze_results.py:107-129 -> ``(good, bad)``, lists of ``(index,
+        mAP)``: the images in ascending stable mAP order, ``bad`` the first k
+        and ``good`` the last k; k is ``len // 2`` when ``2 * k > len``.  The
+        sort runs on the device; only the 2k selected pairs come to the host."""
+        assert k > 0
+        n = len(self)
+        if k * 2 > n:
+            k = n // 2
+        if n == 0:
+            return [], []
+        order, scores = rank_images(self.compute()[0])
+
+        def pairs(sl):
+            return list(zip(order[sl].cpu().tolist(), scores[sl].cpu().tolist()))
+        # _mAPs[-0:] is the whole list, _mAPs[:0] is empty
+        good = pairs(slice(n - k, n)) if k > 0 else pairs(slice(0, n))
+        bad = pairs(slice(0, k))
+        return good, bad
+
+
+def bbox_map_eval(det_result, annotation):
+    """The reference's ``bbox_map_eval`` for one image: ``det_result`` a list
+    of per-class (k, 5) arrays, or a ``(bbox, segm)`` tuple whose bbox part is
+    used; ``annotation`` a dict of ``bboxes`` / ``labels`` and optional
+    ``bboxes_ignore`` / ``labels_ignore``.  -> float."""
+    bbox = det_result[0] if isinstance(det_result, tuple) else det_result
+    acc = ImageMapAnalyzer(len(bbox))
+    acc.add_results([bbox], [annotation])
+    return float(acc.compute()[0][0].item())
+
+
+def _color(c):
+    c = [int(v) for v in c]
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise ValueError(f'draw_gt_det_bboxes: color {c} is not three bytes')
+    return c[0] | (c[1] << 8) | (c[2] << 16)
+
+
+def draw_gt_det_bboxes(img_u8_hwc, gt_bboxes, det_bboxes, score_thr=0,
+                       thickness=2, gt_color=(255, 102, 61),
+                       det_color=(72, 101, 241)):
+    """The overlay of the reference's saved images, in one launch
+    (``ld_draw_boxes``): rectangle outlines painted into a COPY of the (H, W,
+    3) uint8 image, the GT boxes (g, 4) first, then the detections (m, 5) with
+    ``score >= score_thr``.  Coordinates are truncated as
+    ``bbox.astype(np.int32)`` does; a box covers x1..x2 and y1..y2 inclusive,
+    its outline is the band of ``thickness`` pixels inside each edge, and what
+    falls outside the image is dropped.  Colors go to channels 0, 1, 2 in the
+    order given.
+
+    Class names and score text are NOT drawn: the reference renders them with
+    matplotlib, which this package does not depend on.  -> device uint8
+    tensor."""
+    img = torch.as_tensor(img_u8_hwc)
+    if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+        raise ValueError('draw_gt_det_bboxes: image must be (H, W, 3) uint8')
+    dev = img.device if img.device.type == 'cuda' else _device(None)
+    out = img.to(dev).contiguous().clone()
+    g = _f32(gt_bboxes, dev, 4).contiguous()
+    d = _f32(det_bboxes, dev, 5).contiguous()
+    lib = L.get_lib()
+    L.check(lib.ld_draw_boxes(
+        L.ptr(out), out.shape[0], out.shape[1], L.ptr(g), g.shape[0], L.ptr(d),
+        d.shape[0], float(score_thr), int(thickness), _color(gt_color),
+        _color(det_color), L.stream_ptr(dev)), 'ld_draw_boxes')
+    return out
+
+
+def write_png(path, img_u8_hwc):
+    """A minimal PNG writer (8-bit RGB, no filter, stdlib zlib)."""
+    a = np.ascontiguousarray(np.asarray(
+        img_u8_hwc.cpu() if isinstance(img_u8_hwc, torch.Tensor)
+        else img_u8_hwc))
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError('write_png: image must be (H, W, 3) uint8')
+    h, w = a.shape[:2]
+    raw = np.zeros((h, 1 + 3 * w), dtype=np.uint8)  # filter type 0 per row
+    raw[:, 1:] = a.reshape(h, 3 * w)
+
+    def chunk(tag, data):
+        body = tag + data
+        return struct.pack('>I', len(data)) + body + \
+            struct.pack('>I', zlib.crc32(body) & 0xffffffff)
+
+    with open(path, 'wb') as f:
+        f.write(b'\x89PNG\r\n\x1a\n')
+        f.write(chunk(b'IHDR', struct.pack('>IIBBBBB', w, h, 8, 2, 0, 0, 0)))
+        f.write(chunk(b'IDAT', zlib.compress(raw.tobytes(), 6)))
+        f.write(chunk(b'IEND', b''))

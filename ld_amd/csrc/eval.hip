@@ -34,9 +34,13 @@
 #include <stdint.h>
 
 #include "../../include/ld_hip.h"
+#include "eval_iou.h"
 #include "ld_launch.h"
 
 namespace {
+
+using ldeval::box_area;
+using ldeval::iou_ref;
 
 constexpr int kThreads = 256;  // 4 waves of 64
 constexpr int kItems = 16;
@@ -62,22 +66,6 @@ __device__ __forceinline__ int find_img(const int32_t* off, int num_imgs, int i)
     else hi = mid - 1;
   }
   return lo;
-}
-
-__device__ __forceinline__ float box_area(const float* b) {
-  return (b[2] - b[0]) * (b[3] - b[1]);
-}
-
-// bbox_overlaps.py: overlap / max(area1 + area2 - overlap, eps); the detection
-// is bboxes1 unless the image has fewer GTs than detections, and the sum is
-// commutative either way
-__device__ __forceinline__ float iou_ref(const float* d, float area_d, const float* g) {
-  float area_g = box_area(g);
-  float xs = fmaxf(d[0], g[0]), ys = fmaxf(d[1], g[1]);
-  float xe = fminf(d[2], g[2]), ye = fminf(d[3], g[3]);
-  float ov = fmaxf(xe - xs, 0.0f) * fmaxf(ye - ys, 0.0f);
-  float uni = fmaxf(area_d + area_g - ov, 1e-6f);
-  return ov / uni;
 }
 
 __global__ void eval_match_kernel(ld_eval_batch_t b, EvalParams p, float* iou_max,
@@ -463,6 +451,27 @@ __global__ __launch_bounds__(kThreads) void ap_kernel(int n, int S, int num_segs
   if (threadIdx.x == 0) ap[blockIdx.x] = (float)sum;
 }
 
+// ------------------------------------------------------- ld_rank_images ------
+// ascending float64 score as an ascending unsigned key (NaN-free, -0 ties +0)
+__global__ void rank_keys_kernel(int n, const double* score, uint64_t* keys,
+                                 uint32_t* vals) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double s = score[i];
+  uint64_t u = (uint64_t)__double_as_longlong(s == 0.0 ? 0.0 : s);
+  keys[i] = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  vals[i] = (uint32_t)i;
+}
+
+__global__ void rank_gather_kernel(int n, const uint32_t* vals, const double* score,
+                                   int32_t* order, double* sorted) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t j = vals[i];
+  order[i] = (int32_t)j;
+  sorted[i] = score[j];
+}
+
 struct ApPlan {
   size_t keys0, keys1, vals0, vals1, hist, bsum, cum, total;
   int nb;
@@ -622,6 +631,41 @@ int ld_eval_ap(int num_records, const float* rec_score, const int32_t* rec_seg,
   LD_LAUNCH(ap_kernel, dim3(num_segs * S), dim3(kThreads), 0, stream, n, S, num_segs,
             (flags & LD_EVAL_11POINTS) ? 1 : 0, (const int32_t*)seg_start,
             (const double*)recall, (const float*)precision, ap);
+  return (int)hipGetLastError();
+}
+
+size_t ld_rank_images_workspace_bytes(int num_imgs) {
+  if (num_imgs < 0) return 0;
+  return ap_plan(num_imgs, 1).total + 256;
+}
+
+int ld_rank_images(int num_imgs, const double* scores, int32_t* order, double* sorted,
+                   void* workspace, size_t workspace_bytes, ld_stream_t stream_) {
+  const int n = num_imgs;
+  if (n < 0) return LD_EINVAL;
+  if (n == 0) return 0;
+  if (!scores || !order || !sorted) return LD_EINVAL;
+  const ApPlan o = ap_plan(n, 1);
+  if (workspace_bytes < o.total || !workspace) return LD_ENOSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  char* ws = (char*)workspace;
+  uint64_t* keys[2] = {(uint64_t*)(ws + o.keys0), (uint64_t*)(ws + o.keys1)};
+  uint32_t* vals[2] = {(uint32_t*)(ws + o.vals0), (uint32_t*)(ws + o.vals1)};
+  int32_t* hist = (int32_t*)(ws + o.hist);
+  LD_LAUNCH(rank_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, scores,
+            keys[0], vals[0]);
+  int cur = 0;
+  for (int shift = 0; shift < 64; shift += kRadixBits) {
+    LD_LAUNCH(radix_hist_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
+              (const uint64_t*)keys[cur], n, shift, o.nb, hist);
+    LD_LAUNCH(excl_scan_kernel, dim3(1), dim3(kThreads), 0, stream, hist, kBins * o.nb);
+    LD_LAUNCH(radix_scatter_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
+              (const uint64_t*)keys[cur], (const uint32_t*)vals[cur], keys[cur ^ 1],
+              vals[cur ^ 1], n, shift, o.nb, (const int32_t*)hist);
+    cur ^= 1;
+  }
+  LD_LAUNCH(rank_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n,
+            (const uint32_t*)vals[cur], scores, order, sorted);
   return (int)hipGetLastError();
 }
 

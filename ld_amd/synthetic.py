@@ -536,6 +536,74 @@ def eval_map_inputs(case):
     return det_results, annotations
 
 
+# per-image mAP ranking (tests/golden/analyze_results.npz,
+# tools/gen_golden_analyze_results.py): the EVAL_CASES rows named here, image by
+# image, and the rows of IMAGE_MAP_CASES: (name, seed, num_classes, GTs of each
+# image, extra false positives of each image, ignored GTs).  'crowd' has images
+# above what the per-image kernel keeps in LDS (256 detections / 128 GTs) and
+# one image whose GTs cover all 12 classes (-1: one GT of every class).
+IMAGE_MAP_EVAL_CASES = ('base', 'ignore', 'empty', 'exact')
+IMAGE_MAP_CASES = [
+    ('crowd', 31, 12, (3, 150, 5, -1, 0, 40, 2, 140, 6, 1, 24, 9),
+     (2, 10, 300, 4, 3, 0, 1, 150, 0, 2, 5, 280), True),
+]
+
+
+def image_map_inputs(case):
+    """A row of EVAL_CASES or IMAGE_MAP_CASES -> (det_results, annotations,
+    num_classes) in the reference's form; scores are distinct fp32 values."""
+    if len(case) == 8:
+        det_results, annotations = eval_map_inputs(case)
+        return det_results, annotations, case[3]
+    name, seed, C, gts_per_img, fps_per_img, ign = case
+    rng = np.random.RandomState(seed)
+    imgs = []
+    for ngt, nfp in zip(gts_per_img, fps_per_img):
+        if ngt < 0:
+            gl = np.arange(C, dtype=np.int64)
+        else:
+            gl = rng.randint(0, C, size=ngt).astype(np.int64)
+        gts = _eval_boxes(rng, len(gl))
+        nig = rng.randint(0, 4) if ign else 0
+        igs = _eval_boxes(rng, nig)
+        il = rng.randint(0, C, size=nig).astype(np.int64)
+        rows, labs = [], []
+        for box, lab in zip(np.concatenate([gts, igs]),
+                            np.concatenate([gl, il])):
+            w, h = box[2] - box[0], box[3] - box[1]
+            for _ in range(rng.randint(0, 5)):
+                jit = rng.normal(0, 0.1, size=4) * np.array([w, h, w, h])
+                rows.append(box + jit.astype(np.float32))
+                labs.append(lab if rng.uniform() < 0.85 else
+                            rng.randint(0, C))
+        rows += list(_eval_boxes(rng, nfp))
+        labs += list(rng.randint(0, C, size=nfp))
+        perm = rng.permutation(len(labs))
+        dets = np.array(rows, dtype=np.float32).reshape(-1, 4)[perm]
+        labs = np.array(labs, dtype=np.int64)[perm]
+        imgs.append([dets, labs, gts, gl, igs, il])
+    total = sum(len(x[1]) for x in imgs)
+    scores = ((rng.permutation(total) + 1) / (total + 1)).astype(np.float32)
+    assert len(np.unique(scores)) == total
+    det_results, annotations, k = [], [], 0
+    for dets, labs, gts, gl, igs, il in imgs:
+        n = len(labs)
+        d5 = np.concatenate([dets, scores[k:k + n, None]], 1)
+        k += n
+        det_results.append([d5[labs == c] for c in range(C)])
+        ann = {'bboxes': gts, 'labels': gl}
+        if ign:
+            ann['bboxes_ignore'], ann['labels_ignore'] = igs, il
+        annotations.append(ann)
+    return det_results, annotations, C
+
+
+def image_map_cases():
+    """Every case of the per-image fixture, by name."""
+    by_name = {c[0]: c for c in EVAL_CASES}
+    return [by_name[n] for n in IMAGE_MAP_EVAL_CASES] + IMAGE_MAP_CASES
+
+
 def eval_map_scale_inputs(num_imgs=4952, num_classes=20, dets_per_img=100,
                           seed=21):
     """VOC07-test sized input in packed form: per image (100, 5) detections
