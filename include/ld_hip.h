@@ -73,7 +73,7 @@ typedef struct {
   int32_t topk;        /* ATSS topk, 9 */
   int32_t feat_channels; /* 256 (ld_head.py:153-154 hard-codes it) */
   float lw_cls, qfl_beta;       /* QualityFocalLoss (beta must be 2) */
-  float lw_bbox, giou_eps;      /* GIoULoss        */
+  float lw_bbox, giou_eps;      /* GIoULoss / IoULoss / DIoULoss / CIoULoss: eps */
   float lw_dfl;                 /* DistributionFocalLoss */
   float lw_ld, T_ld;            /* KnowledgeDistillationKLDivLoss (main LD) */
   float lw_ld_vlr, T_ld_vlr;    /* ... (VLR LD)    */
@@ -124,6 +124,17 @@ typedef struct {
  * with avg_factor 4 (set lw_ld_vlr = 0.03 * 4 * lw_ld, T_ld_vlr = T_ld); no DFL
  * (lw_dfl = 0); KD on the positives' class logits as in LDHead. */
 #define LD_LOSS_RETINA 16
+/* The box loss loss_pos_kernel evaluates on the decoded positives, uniform per
+ * launch: a 3-bit field at LD_LOSS_BBOX_SHIFT.  0 = GIoULoss, so a flags word
+ * without the field means what it always meant.  giou_eps carries the
+ * module's eps for all of them (iou_loss.py:14-36,85-219). */
+#define LD_LOSS_BBOX_SHIFT 8
+#define LD_LOSS_BBOX_MASK 7
+#define LD_LOSS_BBOX_GIOU 0
+#define LD_LOSS_BBOX_IOU 1        /* IoULoss(linear=False): -log IoU */
+#define LD_LOSS_BBOX_IOU_LINEAR 2 /* IoULoss(linear=True): 1 - IoU */
+#define LD_LOSS_BBOX_DIOU 3
+#define LD_LOSS_BBOX_CIOU 4
 
 /* ---- library ------------------------------------------------------------ */
 /* ABI version of this header; bump on any signature change. */
@@ -374,6 +385,17 @@ int ld_dfl_rows(const float* pred, const float* target, const float* weight,
                 float* grad, ld_stream_t stream);
 /* giou_loss, iou_loss.py:85-102 (aligned boxes (rows, 4)) */
 int ld_giou_rows(const float* pred, const float* target, const float* weight,
+                 int64_t rows, float eps, float gscale, float* loss_rows,
+                 float* grad, ld_stream_t stream);
+/* iou_loss (iou_loss.py:14-36; linear != 0: 1 - IoU instead of -log IoU),
+ * diou_loss (:107-157), ciou_loss (:162-219); eps = the module's */
+int ld_iou_rows(const float* pred, const float* target, const float* weight,
+                int64_t rows, float eps, int linear, float gscale,
+                float* loss_rows, float* grad, ld_stream_t stream);
+int ld_diou_rows(const float* pred, const float* target, const float* weight,
+                 int64_t rows, float eps, float gscale, float* loss_rows,
+                 float* grad, ld_stream_t stream);
+int ld_ciou_rows(const float* pred, const float* target, const float* weight,
                  int64_t rows, float eps, float gscale, float* loss_rows,
                  float* grad, ld_stream_t stream);
 /* Integral.forward, gfl_head.py:32-44: (rows, 4*(reg_max+1)) -> (rows, 4);

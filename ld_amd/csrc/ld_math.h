@@ -203,6 +203,108 @@ LD_HD float giou_loss_grad(const Box& p, const Box& t, float eps, float* iou_out
   return 1.0f - giou;
 }
 
+// IoU loss -log(clamp(IoU, min=eps)) (linear: 1 - clamp(IoU, min=eps)) on
+// aligned boxes (iou_loss.py:14-36) and d(loss)/d(pred box).  The IoU is
+// bbox_overlaps' own (union = max(., 1e-6), iou2d_calculator.py:111-171);
+// `eps` is the module's and only clamps: no gradient below it (clamp's backward
+// passes at equality).  *iou_out is the unclamped IoU.
+LD_HD float iou_loss_grad(const Box& p, const Box& t, float eps, bool linear,
+                          float* iou_out, float g[4]) {
+  float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+  float a1 = pw * ph;
+  float a2 = (t.x2 - t.x1) * (t.y2 - t.y1);
+  float iw_raw = fminf_(p.x2, t.x2) - fmaxf_(p.x1, t.x1);
+  float ih_raw = fminf_(p.y2, t.y2) - fmaxf_(p.y1, t.y1);
+  float iw = fmaxf_(iw_raw, 0.0f), ih = fmaxf_(ih_raw, 0.0f);
+  float inter = iw * ih;
+  float union_raw = a1 + a2 - inter;
+  float uni = fmaxf_(union_raw, 1e-6f);
+  float iou = inter / uni;
+  *iou_out = iou;
+  float ic = fmaxf_(iou, eps);
+  // d loss / d iou
+  float k = iou >= eps ? (linear ? -1.0f : -1.0f / ic) : 0.0f;
+  float dU = -inter / (uni * uni) * sel_gt(union_raw, 1e-6f);
+  float gI = k * (1.0f / uni - dU);
+  float gA1 = k * dU;
+  float g_iw = gI * ih * (iw_raw >= 0.0f ? 1.0f : 0.0f);
+  float g_ih = gI * iw * (ih_raw >= 0.0f ? 1.0f : 0.0f);
+  g[0] = gA1 * (-ph) - g_iw * sel_gt(p.x1, t.x1);
+  g[1] = gA1 * (-pw) - g_ih * sel_gt(p.y1, t.y1);
+  g[2] = gA1 * ph + g_iw * sel_lt(p.x2, t.x2);
+  g[3] = gA1 * pw + g_ih * sel_lt(p.y2, t.y2);
+  return linear ? 1.0f - ic : -logf(ic);
+}
+
+// DIoU loss 1 - (IoU - rho^2 / c^2) and CIoU loss 1 - (IoU - (rho^2 / c^2 +
+// v^2 / (1 - IoU + v))) on aligned boxes (iou_loss.py:107-157, :162-219) and
+// d(loss)/d(pred box).  The conventions are the reference's own and differ from
+// bbox_overlaps': union = ap + ag - overlap + eps and c^2 = cw^2 + ch^2 + eps
+// are ADDITIVE; CIoU's heights are (y2 - y1) + eps; v = 4/pi^2 (atan(w2/h2) -
+// atan(w1/h1))^2 carries a gradient, and so does the IoU inside v's
+// denominator (no no_grad there).  Sub-gradients as in giou_loss_grad.
+// *iou_out is bbox_overlaps' IoU (the QFL quality score), not the additive one.
+LD_HD float dciou_loss_grad_(const Box& p, const Box& t, float eps, bool ciou,
+                             float* iou_out, float g[4]) {
+  float pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+  float tw = t.x2 - t.x1, th = t.y2 - t.y1;
+  float iw_raw = fminf_(p.x2, t.x2) - fmaxf_(p.x1, t.x1);
+  float ih_raw = fminf_(p.y2, t.y2) - fmaxf_(p.y1, t.y1);
+  float iw = fmaxf_(iw_raw, 0.0f), ih = fmaxf_(ih_raw, 0.0f);
+  float inter = iw * ih;
+  float union_raw = pw * ph + tw * th - inter;
+  float uni = union_raw + eps;
+  float iou = inter / uni;
+  *iou_out = inter / fmaxf_(union_raw, 1e-6f);
+  float cw_raw = fmaxf_(p.x2, t.x2) - fminf_(p.x1, t.x1);
+  float ch_raw = fmaxf_(p.y2, t.y2) - fminf_(p.y1, t.y1);
+  float cw = fmaxf_(cw_raw, 0.0f), ch = fmaxf_(ch_raw, 0.0f);
+  float c2 = cw * cw + ch * ch + eps;
+  float lx = (t.x1 + t.x2) - (p.x1 + p.x2);
+  float ly = (t.y1 + t.y2) - (p.y1 + p.y2);
+  float rho2 = (lx * lx) / 4.0f + (ly * ly) / 4.0f;
+  float pen = rho2 / c2;
+  // k_iou = d loss / d iou; g_w, g_h = d loss / d (pred width, pred height)
+  float k_iou = -1.0f, g_w = 0.0f, g_h = 0.0f;
+  if (ciou) {
+    const float factor = (float)(4.0 / (M_PI * M_PI));
+    float h1 = ph + eps, h2 = th + eps;
+    float r1 = pw / h1;
+    float d = atanf(tw / h2) - atanf(r1);
+    float v = factor * (d * d);
+    float den = 1.0f - iou + v;
+    float vd2 = (v * v) / (den * den);
+    pen = pen + (v * v) / den;
+    k_iou = -1.0f + vd2;
+    // d q / d v * d v / d r1, q = v^2 / den
+    float gr1 = (2.0f * v / den - vd2) * (-(factor * 2.0f * d) / (1.0f + r1 * r1));
+    g_w = gr1 / h1;
+    g_h = -gr1 * r1 / h1;
+  }
+  float dU = -inter / (uni * uni);
+  float gI = k_iou * (1.0f / uni - dU);
+  float gA1 = k_iou * dU;
+  float g_iw = gI * ih * (iw_raw >= 0.0f ? 1.0f : 0.0f);
+  float g_ih = gI * iw * (ih_raw >= 0.0f ? 1.0f : 0.0f);
+  float gc = -rho2 / (c2 * c2);
+  float g_cw = gc * 2.0f * cw * (cw_raw >= 0.0f ? 1.0f : 0.0f);
+  float g_ch = gc * 2.0f * ch * (ch_raw >= 0.0f ? 1.0f : 0.0f);
+  float g_lx = -lx / (2.0f * c2), g_ly = -ly / (2.0f * c2);
+  g[0] = gA1 * (-ph) - g_iw * sel_gt(p.x1, t.x1) + g_lx - g_cw * sel_lt(p.x1, t.x1) - g_w;
+  g[1] = gA1 * (-pw) - g_ih * sel_gt(p.y1, t.y1) + g_ly - g_ch * sel_lt(p.y1, t.y1) - g_h;
+  g[2] = gA1 * ph + g_iw * sel_lt(p.x2, t.x2) + g_lx + g_cw * sel_gt(p.x2, t.x2) + g_w;
+  g[3] = gA1 * pw + g_ih * sel_lt(p.y2, t.y2) + g_ly + g_ch * sel_gt(p.y2, t.y2) + g_h;
+  return 1.0f - (iou - pen);
+}
+LD_HD float diou_loss_grad(const Box& p, const Box& t, float eps, float* iou_out,
+                           float g[4]) {
+  return dciou_loss_grad_(p, t, eps, false, iou_out, g);
+}
+LD_HD float ciou_loss_grad(const Box& p, const Box& t, float eps, float* iou_out,
+                           float g[4]) {
+  return dciou_loss_grad_(p, t, eps, true, iou_out, g);
+}
+
 // One 17-bin side of the LD regression distribution.
 // Inputs: student logits s[17], teacher logits t[17].
 //   kl    = T^2/K * sum_k pt_k (log pt_k - log ps_k),  p = softmax(./T)

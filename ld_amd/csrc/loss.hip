@@ -255,7 +255,7 @@ __device__ __forceinline__ size_t part_idx(int slot, int z, const BlockMap& bm, 
   return ((size_t)slot * kZMax + z) * nb + (size_t)n * bm.blocks_per_img + blockIdx.x;
 }
 
-// ------------------------------------------------ positives: GIoU + KD stats
+// ------------------------------------------ positives: box loss + KD stats
 __global__ __launch_bounds__(kBlk) void loss_pos_kernel(
     ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t t_cls,
     ld_maps_t reg, const int64_t* __restrict__ labels,
@@ -295,7 +295,24 @@ __global__ __launch_bounds__(kBlk) void loss_pos_kernel(
       const float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
       const Box tgt = target_box(fcos, cx, cy, t, stride);
       float iou, g[4];
-      const float gl = ld::giou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+      // the box loss of the launch (LD_LOSS_BBOX_* in hp.flags; 0 = GIoU)
+      float gl;
+      switch ((hp.flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) {
+        case LD_LOSS_BBOX_IOU:
+          gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, false, &iou, g);
+          break;
+        case LD_LOSS_BBOX_IOU_LINEAR:
+          gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, true, &iou, g);
+          break;
+        case LD_LOSS_BBOX_DIOU:
+          gl = ld::diou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+          break;
+        case LD_LOSS_BBOX_CIOU:
+          gl = ld::ciou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+          break;
+        default:
+          gl = ld::giou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+      }
       s_bbox = wt * gl;
       // softmax statistics of the class logits at temperature T_kd
       const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
@@ -1162,6 +1179,8 @@ int check_hp(const ld_loss_hp_t* hp) {
   if (!hp) return LD_EINVAL;
   if (hp->reg_max != 16 || hp->qfl_beta != 2.0f) return LD_EUNSUPPORTED;
   if (hp->num_classes < 1 || hp->feat_channels < 1) return LD_EINVAL;
+  if (((hp->flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) > LD_LOSS_BBOX_CIOU)
+    return LD_EINVAL;
   if (hp->T_ld < 1.0f || hp->T_ld_vlr < 1.0f || hp->T_kd < 1.0f)
     return LD_EINVAL;  // kd_loss.py:51 assert T >= 1
   return 0;

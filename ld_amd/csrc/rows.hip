@@ -1,6 +1,6 @@
 // Reference-layout loss operators: row-major (rows, K) tensors exactly as the
 // mmdet loss modules receive them.  They back the registry modules
-// (QualityFocalLoss, DistributionFocalLoss, GIoULoss,
+// (QualityFocalLoss, DistributionFocalLoss, GIoULoss, IoULoss, DIoULoss, CIoULoss,
 // KnowledgeDistillationKLDivLoss, Integral, BboxOverlaps2D) when those are
 // used on their own; the train step itself runs the fused NCHW-direct kernels
 // of loss.hip.  One thread per row; rows are short (4..80 floats) so a
@@ -115,6 +115,31 @@ __global__ void giou_rows_kernel(const float* __restrict__ pred,
   float iou, g[4];
   const float l = ld::giou_loss_grad(Box{p.x, p.y, p.z, p.w},
                                      Box{t.x, t.y, t.z, t.w}, eps, &iou, g);
+  const float w = weight ? weight[r] : 1.0f;
+  loss_rows[r] = w * l;
+  if (grad)
+    reinterpret_cast<float4*>(grad)[r] = make_float4(
+        gscale * w * g[0], gscale * w * g[1], gscale * w * g[2], gscale * w * g[3]);
+}
+
+// iou_loss / diou_loss / ciou_loss, iou_loss.py:14-36,107-219.  MODE: 0 IoU
+// (-log), 1 IoU (linear), 2 DIoU, 3 CIoU
+template <int MODE>
+__global__ void box_rows_kernel(const float* __restrict__ pred,
+                                const float* __restrict__ target,
+                                const float* __restrict__ weight, int64_t rows,
+                                float eps, float gscale,
+                                float* __restrict__ loss_rows,
+                                float* __restrict__ grad) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const float4 p = reinterpret_cast<const float4*>(pred)[r];
+  const float4 t = reinterpret_cast<const float4*>(target)[r];
+  const Box pb{p.x, p.y, p.z, p.w}, tb{t.x, t.y, t.z, t.w};
+  float iou, g[4];
+  const float l = MODE <= 1   ? ld::iou_loss_grad(pb, tb, eps, MODE == 1, &iou, g)
+                  : MODE == 2 ? ld::diou_loss_grad(pb, tb, eps, &iou, g)
+                              : ld::ciou_loss_grad(pb, tb, eps, &iou, g);
   const float w = weight ? weight[r] : 1.0f;
   loss_rows[r] = w * l;
   if (grad)
@@ -259,6 +284,43 @@ extern "C" int ld_giou_rows(const float* pred, const float* target,
   return (int)hipGetLastError();
 }
 
+extern "C" int ld_iou_rows(const float* pred, const float* target,
+                           const float* weight, int64_t rows, float eps, int linear,
+                           float gscale, float* loss_rows, float* grad,
+                           ld_stream_t stream) {
+  if (!pred || !target || !loss_rows || rows < 0) return LD_EINVAL;
+  if (rows == 0) return 0;
+  if (linear)
+    LD_LAUNCH(box_rows_kernel<1>, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                       pred, target, weight, rows, eps, gscale, loss_rows, grad);
+  else
+    LD_LAUNCH(box_rows_kernel<0>, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                       pred, target, weight, rows, eps, gscale, loss_rows, grad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_diou_rows(const float* pred, const float* target,
+                            const float* weight, int64_t rows, float eps,
+                            float gscale, float* loss_rows, float* grad,
+                            ld_stream_t stream) {
+  if (!pred || !target || !loss_rows || rows < 0) return LD_EINVAL;
+  if (rows == 0) return 0;
+  LD_LAUNCH(box_rows_kernel<2>, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                     pred, target, weight, rows, eps, gscale, loss_rows, grad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_ciou_rows(const float* pred, const float* target,
+                            const float* weight, int64_t rows, float eps,
+                            float gscale, float* loss_rows, float* grad,
+                            ld_stream_t stream) {
+  if (!pred || !target || !loss_rows || rows < 0) return LD_EINVAL;
+  if (rows == 0) return 0;
+  LD_LAUNCH(box_rows_kernel<3>, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                     pred, target, weight, rows, eps, gscale, loss_rows, grad);
+  return (int)hipGetLastError();
+}
+
 extern "C" int ld_integral_rows(const float* x, int64_t rows, float* out,
                                 ld_stream_t stream) {
   if (!x || !out || rows < 0) return LD_EINVAL;
@@ -304,5 +366,5 @@ extern "C" int ld_sum(const float* x, int64_t n, float* out, void* workspace,
   return (int)hipGetLastError();
 }
 
-extern "C" int ld_abi_version(void) { return 13; }
+extern "C" int ld_abi_version(void) { return 14; }
 extern "C" const char* ld_target_arch(void) { return "gfx950"; }

@@ -18,6 +18,7 @@ import torch.nn as nn
 from . import layers as Y
 from . import lib as L
 from . import lossblock as LB
+from .losses import bbox_loss_mode
 from .cnn import ConvModule, Conv2d, Scale, bias_init_with_prob, normal_init
 from .registry import (HEADS, build_anchor_generator, build_assigner,
                        build_bbox_coder, build_iou_calculator, build_loss,
@@ -383,15 +384,16 @@ class GFLHead(BBoxTestMixin, nn.Module):
             qfl_beta=getattr(self.loss_cls, 'beta', 2.0),
             lw_bbox=self.loss_bbox.loss_weight,
             giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
+            bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou',
             lw_dfl=self.loss_dfl.loss_weight, lw_ld=0.0, T_ld=1.0,
             lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0, T_kd=1.0, lw_im=0.0)
         kw.update(over)
         return LB.make_hp(**kw)
 
     def _check_loss_cfg(self):
-        from .losses import GIoULoss, QualityFocalLoss
+        from .losses import QualityFocalLoss
         if not isinstance(self.loss_cls, QualityFocalLoss) or \
-                not isinstance(self.loss_bbox, GIoULoss):
+                bbox_loss_mode(self.loss_bbox) is None:
             raise NotImplementedError(
                 'the fused loss block implements QualityFocalLoss + GIoULoss '
                 f'(got {type(self.loss_cls).__name__}, '
@@ -686,9 +688,9 @@ class ATSSGFLHead(GFLHead):
                 Y.split_levels(ctr3, levels))
 
     def _check_loss_cfg(self):
-        from .losses import CrossEntropyLoss, FocalLoss, GIoULoss
+        from .losses import CrossEntropyLoss, FocalLoss
         if not isinstance(self.loss_cls, FocalLoss) or \
-                not isinstance(self.loss_bbox, GIoULoss) or \
+                bbox_loss_mode(self.loss_bbox) is None or \
                 not isinstance(self.loss_centerness, CrossEntropyLoss) or \
                 not self.loss_centerness.use_sigmoid:
             raise NotImplementedError(
@@ -902,9 +904,9 @@ class FCOSGFLHead(BBoxTestMixin, nn.Module):
     _norm_reducer = staticmethod(GFLHead._norm_reducer)
 
     def _check_loss_cfg(self):
-        from .losses import CrossEntropyLoss, FocalLoss, GIoULoss
+        from .losses import CrossEntropyLoss, FocalLoss
         if not isinstance(self.loss_cls, FocalLoss) or \
-                not isinstance(self.loss_bbox, GIoULoss) or \
+                bbox_loss_mode(self.loss_bbox) is None or \
                 not isinstance(self.loss_centerness, CrossEntropyLoss) or \
                 not self.loss_centerness.use_sigmoid:
             raise NotImplementedError(
@@ -918,7 +920,8 @@ class FCOSGFLHead(BBoxTestMixin, nn.Module):
                   feat_channels=self.feat_channels,
                   lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
                   lw_bbox=self.loss_bbox.loss_weight,
-                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6), lw_dfl=0.0,
+                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
+                  bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou', lw_dfl=0.0,
                   lw_ld=0.0, T_ld=1.0, lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0,
                   T_kd=1.0, lw_im=0.0,
                   lw_ctr=self.loss_centerness.loss_weight,
@@ -1129,9 +1132,9 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
 
     # ---------------------------------------------------------------- loss --
     def _check_loss_cfg(self):
-        from .losses import FocalLoss, GIoULoss
+        from .losses import FocalLoss
         if not isinstance(self.loss_cls, FocalLoss) or \
-                not isinstance(self.loss_bbox, GIoULoss) or \
+                bbox_loss_mode(self.loss_bbox) is None or \
                 not self.reg_decoded_bbox:
             raise NotImplementedError(
                 'the fused RetinaGFL loss block implements FocalLoss + '
@@ -1152,7 +1155,8 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
                   feat_channels=self.feat_channels,
                   lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
                   lw_bbox=self.loss_bbox.loss_weight,
-                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6), lw_dfl=0.0,
+                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
+                  bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou', lw_dfl=0.0,
                   lw_ld=0.0, T_ld=1.0, lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0,
                   T_kd=1.0, lw_im=0.0, focal_alpha=self.loss_cls.alpha,
                   flags=L.LD_LOSS_RETINA)

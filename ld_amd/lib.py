@@ -57,6 +57,9 @@ LD_IM_CENTER_INSIDE = 2
 LD_LOSS_ATSS = 4
 LD_LOSS_FCOS = 8
 LD_LOSS_RETINA = 16
+LD_LOSS_BBOX_SHIFT = 8
+LD_LOSS_BBOX_MODES = {'giou': 0, 'iou': 1, 'iou_linear': 2, 'diou': 3,
+                      'ciou': 4}
 LD_INFER_VOTING = 1
 LD_INFER_PROB = 2
 LD_INFER_POINTS = 4
@@ -241,7 +244,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -313,6 +316,12 @@ SIGNATURES = {
     'ld_dfl_rows': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp,
                               _vp]),
     'ld_giou_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
+                               _vp]),
+    'ld_iou_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _i32, _f32, _vp, _vp,
+                              _vp]),
+    'ld_diou_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
+                               _vp]),
+    'ld_ciou_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
                                _vp]),
     'ld_integral_rows': (C.c_int, [_vp, _i64, _vp, _vp]),
     'ld_integral_rows_bwd': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),

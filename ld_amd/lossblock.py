@@ -75,7 +75,14 @@ def alloc_level_views(like):
 def make_hp(num_classes=80, reg_max=16, topk=9, feat_channels=256, lw_cls=1.0,
             qfl_beta=2.0, lw_bbox=2.0, giou_eps=1e-6, lw_dfl=0.25, lw_ld=0.25,
             T_ld=10.0, lw_ld_vlr=0.25, T_ld_vlr=10.0, lw_kd=10.0, T_kd=2.0,
-            lw_im=2.0, cls_channels=0, flags=0, lw_ctr=0.0, focal_alpha=0.25):
+            lw_im=2.0, cls_channels=0, flags=0, lw_ctr=0.0, focal_alpha=0.25,
+            bbox_loss='giou'):
+    """``bbox_loss``: 'giou' | 'iou' | 'iou_linear' | 'diou' | 'ciou', the box
+    loss of the positives (a field of ``flags``; ``giou_eps`` is its eps)."""
+    if bbox_loss not in L.LD_LOSS_BBOX_MODES:
+        raise ValueError(f'bbox_loss {bbox_loss!r}: one of '
+                         f'{sorted(L.LD_LOSS_BBOX_MODES)}')
+    flags |= L.LD_LOSS_BBOX_MODES[bbox_loss] << L.LD_LOSS_BBOX_SHIFT
     hp = L.LossHpT()
     hp.cls_channels, hp.flags = cls_channels, flags
     hp.lw_ctr, hp.focal_alpha = lw_ctr, focal_alpha

@@ -3,8 +3,9 @@ arguments and ``forward(pred, target, weight, avg_factor, reduction_override)``
 contract (mmdet/models/losses/{kd_loss,gfocal_loss,iou_loss,utils}.py).
 
 Called on their own they run the reference-layout row kernels of
-libldhip.so (rows.hip); inside LDHead the whole block is fused instead
-(lossblock.py).  Reduction follows ``weight_reduce_loss``
+libldhip.so (rows.hip); inside the heads the whole block is fused instead
+(lossblock.py), with the box loss -- GIoULoss, IoULoss, DIoULoss or CIoULoss
+-- selected by ``bbox_loss_mode``.  Reduction follows ``weight_reduce_loss``
 (losses/utils.py:28-55) exactly.
 """
 import torch
@@ -100,6 +101,22 @@ def _launch_giou(pred, weight, loss_rows, grad, target, eps):
                                      pred.shape[0], float(eps), 1.0,
                                      L.ptr(loss_rows), L.ptr(grad), _st(pred)),
             'ld_giou_rows')
+
+
+def _box_launcher(symbol, *extra):
+    def launch(pred, weight, loss_rows, grad, target, eps):
+        target = L.require_device(target.contiguous(), torch.float32, 'target')
+        L.check(getattr(L.get_lib(), symbol)(
+            L.ptr(pred), L.ptr(target), L.ptr(weight), pred.shape[0],
+            float(eps), *extra, 1.0, L.ptr(loss_rows), L.ptr(grad), _st(pred)),
+            symbol)
+    return launch
+
+
+_launch_iou = _box_launcher('ld_iou_rows', 0)
+_launch_iou_linear = _box_launcher('ld_iou_rows', 1)
+_launch_diou = _box_launcher('ld_diou_rows')
+_launch_ciou = _box_launcher('ld_ciou_rows')
 
 
 def knowledge_distillation_kl_div_loss(pred, soft_label, T, weight=None,
@@ -258,18 +275,73 @@ class CrossEntropyLoss(nn.Module):
             'loss block (ld_loss_centerness)')
 
 
-@LOSSES.register_module()
-class IoULoss(nn.Module):
-    """Only *registrable* (FCOSGFLHead's constructor default,
-    fcos_gfl_head.py:111); every FCOS-GFL config overrides it with GIoULoss."""
+class _BoxRowLoss(nn.Module):
+    """What IoULoss / DIoULoss / CIoULoss share with GIoULoss
+    (iou_loss.py:247-288,372-436): reduction_override, avg_factor, an (n, 4)
+    weight reduced by ``.mean(-1)``, and a zero result when no weight is
+    positive -- from the row kernel (rows are multiplied by the weight), not
+    from the reference's ``torch.any(weight > 0)`` host sync."""
 
-    def __init__(self, linear=False, eps=1e-6, reduction='mean',
-                 loss_weight=1.0):
+    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
         super().__init__()
         self.eps, self.reduction, self.loss_weight = eps, reduction, loss_weight
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError('IoULoss is not on the LD train path')
+    def _launcher(self):
+        raise NotImplementedError
+
+    def forward(self, pred, target, weight=None, avg_factor=None,
+                reduction_override=None, **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        if weight is not None and weight.dim() > 1:
+            assert weight.shape == pred.shape
+            weight = weight.mean(-1)
+        rows = _RowLoss.apply(self._launcher(), pred, weight, target, self.eps)
+        return self.loss_weight * _reduce_weighted(rows, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class IoULoss(_BoxRowLoss):
+    """iou_loss.py:222-288: -log(IoU), or 1 - IoU with ``linear=True``
+    (FCOSGFLHead's constructor default, fcos_gfl_head.py:111)."""
+
+    def __init__(self, linear=False, eps=1e-6, reduction='mean',
+                 loss_weight=1.0):
+        super().__init__(eps, reduction, loss_weight)
+        self.linear = linear
+
+    def _launcher(self):
+        return _launch_iou_linear if self.linear else _launch_iou
+
+
+@LOSSES.register_module()
+class DIoULoss(_BoxRowLoss):
+    """iou_loss.py:363-398."""
+
+    def _launcher(self):
+        return _launch_diou
+
+
+@LOSSES.register_module()
+class CIoULoss(_BoxRowLoss):
+    """iou_loss.py:401-436 (the student of
+    configs/ld/ld_r18_gflv1_r101_fpn_voc_1x.py:50 and the GFL teachers of
+    configs/gfl/gfl_r50_fpn_1x_coco.py:43 train with it)."""
+
+    def _launcher(self):
+        return _launch_ciou
+
+
+def bbox_loss_mode(module):
+    """The ``bbox_loss`` name lossblock.make_hp takes for a loss_bbox module,
+    None for one the fused loss block does not evaluate."""
+    for cls, mode in ((GIoULoss, 'giou'), (DIoULoss, 'diou'),
+                      (CIoULoss, 'ciou')):
+        if isinstance(module, cls):
+            return mode
+    if isinstance(module, IoULoss):
+        return 'iou_linear' if module.linear else 'iou'
+    return None
 
 
 @LOSSES.register_module()
@@ -285,17 +357,3 @@ class SmoothL1Loss(nn.Module):
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError('SmoothL1Loss is not on the LD train path')
-
-
-@LOSSES.register_module()
-class CIoULoss(nn.Module):
-    """Only *registrable*: the GFL teacher configs name it
-    (configs/gfl/gfl_r50_fpn_1x_coco.py:43) but a frozen teacher never
-    evaluates a loss."""
-
-    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
-        super().__init__()
-        self.eps, self.reduction, self.loss_weight = eps, reduction, loss_weight
-
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError('CIoULoss is not on the LD train path')

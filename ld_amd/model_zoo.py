@@ -5,7 +5,8 @@ through ld_amd's registry unchanged (tests/test_configs_resolve.py checks this
 wherever a reference checkout is present); they are not shipped with this
 repository, so the bench / smoke / GPU tests construct the same settings here.
 Values follow configs/ld/ld_r18_gflv1_r101_fpn_coco_1x.py:6-58,
-configs/ld/ld_r50_gflv1_r101_fpn_coco_1x.py:2-52 and
+configs/ld/ld_r50_gflv1_r101_fpn_coco_1x.py:2-52,
+configs/ld/ld_r18_gflv1_r101_fpn_voc_1x.py:5-62 and
 configs/gfl/gfl_r50_fpn_1x_coco.py:5-56.
 """
 import copy
@@ -261,6 +262,23 @@ def ld_fcos_detector(student_depth=50, teacher_depth=101):
                 neck=_fcos_neck(student_depth), bbox_head=head,
                 train_cfg=copy.deepcopy(_FCOS_TRAIN_CFG),
                 test_cfg=copy.deepcopy(_TEST_CFG))
+
+
+def ld_voc_detector(student_depth=18, teacher_depth=101,
+                    imitation_method='finegrained'):
+    """configs/ld/ld_r18_gflv1_r101_fpn_voc_1x.py:5-62, one of the paper's two
+    VOC recipes: 20 classes, the student regresses with CIoULoss
+    (loss_weight 2) and sets loss_ld only (loss_im has weight 0, so its
+    CUDA-only default 'gibox' region is evaluated as 'finegrained' x 0, SURVEY
+    quirk Q3); the teacher is configs/gfl/gfl_r101_fpn_voc.py:2-40 (GIoULoss)."""
+    cfg = ld_detector(student_depth, teacher_depth,
+                      imitation_method=imitation_method, loss_im_weight=0,
+                      with_vlr_kd=False)
+    cfg['bbox_head'].update(num_classes=20,
+                            loss_bbox=dict(type='CIoULoss', loss_weight=2.0))
+    cfg['teacher_config']['model']['bbox_head'].update(
+        num_classes=20, loss_bbox=dict(type='GIoULoss', loss_weight=2.0))
+    return cfg
 
 
 OPTIMIZER = dict(type='SGD', lr=0.0025, momentum=0.9, weight_decay=0.0001)

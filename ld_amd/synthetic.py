@@ -700,3 +700,16 @@ def coco_eval_inputs(case):
         anns = [a for a in anns if a['category_id'] != cat_ids[-1]]
     dataset = dict(images=images, annotations=anns, categories=cats)
     return dataset, results, [c['name'] for c in cats], dict(kw)
+
+
+def box_loss_rows(n, seed=31, img_h=160, img_w=224):
+    """``n`` (pred, target) box pairs for the row box losses: seeded targets
+    and predictions jittered around them by up to +-0.4 of the target's size per
+    coordinate (so the pairs overlap partly, by little or not at all, and the
+    predicted width and height stay positive)."""
+    gen = _gen(seed)
+    target, _ = synthetic_boxes(n, img_h, img_w, gen, min_size=2.0,
+                                max_size=120.0)
+    size = (target[:, 2:] - target[:, :2]).repeat(1, 2)
+    pred = target + (torch.rand(n, 4, generator=gen) - 0.5) * 0.8 * size
+    return pred.contiguous(), target
