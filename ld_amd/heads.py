@@ -1,6 +1,25 @@
-"""GFLHead / LDHead with mmdet's constructor arguments, state_dict keys and
+"""The dense heads with mmdet's constructor arguments, state_dict keys and
 method signatures (reference: mmdet/models/dense_heads/gfl_head.py:15-625,
-ld_head.py:43-637, anchor_head.py:14-173, base_dense_head.py:6-59).
+ld_head.py:43-637, anchor_head.py:14-173, base_dense_head.py:6-59 and the
+atss_gfl / fcos_gfl / retina_gfl / gfocal heads with their ld_* variants).
+
+Class layout (plain inheritance, one private base):
+
+    _DenseHead            towers + init, packed forward trunk, _hp defaults,
+      |                   config checks, _run_block (the ONE loss-block call),
+      |                   _loss_dict, both forward_train bodies, _get_bboxes
+      +- GFLHead          <- LDHead (_FeatureLD)
+      |    +- ATSSGFLHead <- LDATSSHead (_SideLD)
+      |    +- GFocalHead  <- LDv2Head (_FeatureLD)
+      +- FCOSGFLHead      <- LDFCOSHead (_SideLD)
+      +- RetinaGFLHead    <- LDRetinaHead (_SideLD)
+
+A head states its constructor, its predictor convs (``_predictors``), its
+targets and what differs in ``_hp`` / ``_check_loss_cfg``.  ``_FeatureLD`` is
+the LD loss that reads the neck features (imitation), ``_SideLD`` the one that
+does not.  Modules are registered in the reference's order (``integral`` after
+the layers): state_dict, parameter and init-draw order are part of the
+checkpoint and optimizer formats (tests/test_heads_contract_host.py).
 
 MI355X-native execution:
   * forward: the five FPN levels are concatenated into one (N, C, P) tensor
@@ -229,63 +248,39 @@ class BBoxTestMixin:
         return bbox2result(dets, labels, self.num_classes)
 
 
-@HEADS.register_module()
-class GFLHead(BBoxTestMixin, nn.Module):
-    """Constructor = AnchorHead.__init__ (anchor_head.py:31-96) +
-    GFLHead.__init__ (gfl_head.py:76-100)."""
+ATSS_LOSS_KEYS = ['loss_cls', 'loss_bbox', 'loss_ld', 'loss_ld_neg',
+                  'loss_cls_kd', 'loss_centerness']
+# rows of the fused block's (8, L) table that carry them (LD_LOSS_ATSS)
+_ATSS_ROWS = [0, 1, 3, 4, 5, 6]
+RETINA_LOSS_KEYS = ['loss_cls', 'loss_bbox', 'loss_ld', 'loss_ld_vlr',
+                    'loss_cls_kd']
+# rows of the fused block's (8, L) table that carry them (LD_LOSS_RETINA)
+_RETINA_ROWS = [0, 1, 3, 4, 5]
 
-    def __init__(self, num_classes, in_channels, stacked_convs=4,
-                 conv_cfg=None,
-                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
-                 loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25),
-                 reg_max=16, feat_channels=256,
-                 anchor_generator=dict(type='AnchorGenerator', ratios=[1.0],
-                                       octave_base_scale=8,
-                                       scales_per_octave=1,
-                                       strides=[8, 16, 32, 64, 128]),
-                 bbox_coder=dict(type='DeltaXYWHBBoxCoder',
-                                 target_means=(.0, .0, .0, .0),
-                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
-                 reg_decoded_bbox=False,
-                 loss_cls=dict(type='QualityFocalLoss', use_sigmoid=True,
-                               beta=2.0, loss_weight=1.0),
-                 loss_bbox=dict(type='GIoULoss', loss_weight=2.0),
-                 train_cfg=None, test_cfg=None):
-        super().__init__()
-        self.stacked_convs, self.conv_cfg, self.norm_cfg = (stacked_convs,
-                                                            conv_cfg, norm_cfg)
-        self.reg_max = reg_max
-        self.in_channels, self.num_classes = in_channels, num_classes
-        self.feat_channels = feat_channels
-        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
-        self.sampling = loss_cls['type'] not in [
-            'FocalLoss', 'GHMC', 'QualityFocalLoss'
-        ]
-        self.cls_out_channels = num_classes if self.use_sigmoid_cls \
-            else num_classes + 1
-        if self.cls_out_channels <= 0:
-            raise ValueError(f'num_classes={num_classes} is too small')
-        self.reg_decoded_bbox = reg_decoded_bbox
-        self.bbox_coder = build_bbox_coder(bbox_coder)
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_bbox = build_loss(loss_bbox)
-        self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        if self.train_cfg:
-            self.assigner = build_assigner(self.train_cfg.assigner)
-            self.sampler = build_sampler(dict(type='PseudoSampler'),
-                                         context=self)
-        self.sampling = False
-        self.fp16_enabled = False
-        self.anchor_generator = build_anchor_generator(anchor_generator)
-        self.num_anchors = self.anchor_generator.num_base_anchors[0]
-        self._init_layers()
-        self.integral = Integral(self.reg_max)
-        self.loss_dfl = build_loss(loss_dfl)
-        # see SGDTrainer.step: only set for the duration of a train step
-        self.unit_upstream = False
+# the loss_bbox types the fused block evaluates, by their make_hp names
+_BOX_LOSSES = 'one of the box losses ' + ', '.join(L.LD_LOSS_BBOX_MODES)
 
-    def _init_layers(self):
-        """gfl_head.py:102-133."""
+
+class _DenseHead(BBoxTestMixin, nn.Module):
+    """What the five plain heads share: the two towers and their init, the
+    level-packed forward trunk, the hyper-parameter struct, the config checks,
+    the fused loss-block call with its loss dict, forward_train and the
+    device-side get_bboxes.  A subclass states its constructor, its predictor
+    convs (``_predictors``), its targets and what differs in ``_hp``."""
+    # predictor attributes in the reference's init order; the first one gets
+    # the bias prior
+    _predictors = ()
+    # LDHead / LDv2Head: their loss reads the features
+    _wants_packed_feats = False
+    # keys of the loss dict, the table rows that carry them (None: row i for
+    # key i) and the keys of the plain (teacher-less) loss
+    _loss_keys, _loss_rows = LOSS_KEYS, None
+    _plain_keys = ('loss_cls', 'loss_bbox', 'loss_dfl')
+
+    # ------------------------------------------------------------- layers --
+    def _build_towers(self):
+        """The cls / reg conv stacks (gfl_head.py:102-121 and the same loop of
+        atss_gfl_head.py, fcos_gfl_head.py and retina_gfl_head.py)."""
         self.relu = nn.ReLU(inplace=True)
         self.cls_convs = nn.ModuleList()
         self.reg_convs = nn.ModuleList()
@@ -297,40 +292,35 @@ class GFLHead(BBoxTestMixin, nn.Module):
             self.reg_convs.append(
                 ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
                            conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
-        assert self.num_anchors == 1, 'anchor free version'
-        self.gfl_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3,
-                              padding=1)
-        self.gfl_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3,
-                              padding=1)
-        self.scales = nn.ModuleList(
-            [Scale(1.0) for _ in self.anchor_generator.strides])
+
+    def _build_scales(self, strides):
+        self.scales = nn.ModuleList([Scale(1.0) for _ in strides])
 
     def init_weights(self):
-        """gfl_head.py:135-143."""
+        """gfl_head.py:135-143, atss_gfl_head.py:127-137, fcos_gfl_head.py:
+        167-176, retina_gfl_head.py:266-274: towers, then the predictors."""
         for m in self.cls_convs:
             normal_init(m.conv, std=0.01)
         for m in self.reg_convs:
             normal_init(m.conv, std=0.01)
-        bias_cls = bias_init_with_prob(0.01)
-        normal_init(self.gfl_cls, std=0.01, bias=bias_cls)
-        normal_init(self.gfl_reg, std=0.01)
+        for i, name in enumerate(self._predictors):
+            normal_init(getattr(self, name), std=0.01,
+                        bias=bias_init_with_prob(0.01) if i == 0 else 0)
 
     # ------------------------------------------------------------ forward --
-    def forward(self, feats):
-        """feats: tuple of per-level (N, C, H, W) -> (cls_scores, bbox_preds)
-        lists (gfl_head.py:145-183), all levels in one launch per layer."""
-        assert len(feats) == len(self.scales)
+    def _trunk(self, feats):
+        """feats: tuple of per-level (N, C, H, W) -> the two tower outputs on
+        the level-concatenated tensor, one launch per layer for all levels."""
+        scales = getattr(self, 'scales', None)
+        assert scales is None or len(feats) == len(scales)
         x3, levels = self._pack(feats)
-        cls_feat = reg_feat = x3
-        cls_feat = _tower(self.cls_convs, cls_feat, levels)
-        reg_feat = _tower(self.reg_convs, reg_feat, levels)
-        cls3, _ = self.gfl_cls.forward3(cls_feat, levels)
-        reg3, _ = self.gfl_reg.forward3(reg_feat, levels)
-        scales = torch.stack([s.scale for s in self.scales])
-        reg3 = Y.scale_levels(reg3, scales, levels)
-        return Y.split_levels(cls3, levels), Y.split_levels(reg3, levels)
+        return (_tower(self.cls_convs, x3, levels),
+                _tower(self.reg_convs, x3, levels), levels)
 
-    _wants_packed_feats = False  # LDHead / LDv2Head: their loss reads the features
+    def _scale(self, reg3, levels):
+        """The per-level learnable Scale of the box branch."""
+        return Y.scale_levels(reg3, torch.stack([s.scale for s in self.scales]),
+                              levels)
 
     def _pack(self, feats):
         """The level-concatenated head input; remembered for ``_loss_feats``
@@ -377,51 +367,43 @@ class GFLHead(BBoxTestMixin, nn.Module):
 
     # --------------------------------------------------------------- loss --
     def _hp(self, **over):
+        """The loss block's hyper-parameters.  Here: what every head reads off
+        its loss modules, no DFL, no distillation; a subclass passes what
+        differs."""
         kw = dict(
-            num_classes=self.num_classes, reg_max=self.reg_max,
-            topk=self.assigner.topk, feat_channels=self.feat_channels,
-            lw_cls=self.loss_cls.loss_weight,
-            qfl_beta=getattr(self.loss_cls, 'beta', 2.0),
+            num_classes=self.num_classes, reg_max=self.reg_max, topk=9,
+            feat_channels=self.feat_channels,
+            lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
             lw_bbox=self.loss_bbox.loss_weight,
             giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
-            bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou',
-            lw_dfl=self.loss_dfl.loss_weight, lw_ld=0.0, T_ld=1.0,
-            lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0, T_kd=1.0, lw_im=0.0)
+            bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou', lw_dfl=0.0,
+            lw_ld=0.0, T_ld=1.0, lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0,
+            T_kd=1.0, lw_im=0.0)
         kw.update(over)
         return LB.make_hp(**kw)
 
-    def _check_loss_cfg(self):
-        from .losses import QualityFocalLoss
-        if not isinstance(self.loss_cls, QualityFocalLoss) or \
-                bbox_loss_mode(self.loss_bbox) is None:
-            raise NotImplementedError(
-                'the fused loss block implements QualityFocalLoss + GIoULoss '
-                f'(got {type(self.loss_cls).__name__}, '
-                f'{type(self.loss_bbox).__name__})')
+    def _check_train_cfg(self):
         if self.train_cfg.get('allowed_border', -1) >= 0:
             raise NotImplementedError('allowed_border >= 0')
         if self.train_cfg.get('pos_weight', -1) > 0:
             raise NotImplementedError('pos_weight > 0')
 
-    def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
-                            gt_labels, hp, device):
-        """AnchorHead.get_anchors + LDHead.get_targets for the whole batch in
-        two launches (ld_head.py:377-577)."""
-        strides = [s[0] for s in self.anchor_generator.strides]
-        if not self.anchor_generator.single_square:
-            # the implicit-anchor kernels build the one square anchor of a cell
-            # from an INTEGER scale (octave_base_scale * stride)
+    def _check_focal_cfg(self, family, centerness):
+        """The heads that train with FocalLoss (and a sigmoid-CE centerness)."""
+        from .losses import CrossEntropyLoss, FocalLoss
+        ok = isinstance(self.loss_cls, FocalLoss) and \
+            bbox_loss_mode(self.loss_bbox) is not None
+        if centerness:
+            ok = ok and isinstance(self.loss_centerness, CrossEntropyLoss) \
+                and self.loss_centerness.use_sigmoid
+        if not ok:
             raise NotImplementedError(
-                f'{type(self).__name__}: one anchor per cell with a non-integer '
-                'scale or ratio != 1 (anchor_generator.py:78-98); the '
-                'single-anchor target kernels take ratios=[1.0] with an integer '
-                'octave_base_scale')
-        if gt_labels is None:
-            gt_labels = [b.new_zeros(b.shape[0], dtype=torch.long)
-                         for b in gt_bboxes]
-        return LB.atss_targets(featmap_sizes, strides, img_metas, gt_bboxes,
-                               gt_labels, hp, device,
-                               self.anchor_generator.anchor_scale)
+                f'the fused {family} loss block implements FocalLoss + '
+                f'{_BOX_LOSSES}' +
+                (' + sigmoid CrossEntropyLoss centerness' if centerness else
+                 ''))
+        if self.loss_cls.gamma != 2.0:
+            raise NotImplementedError('FocalLoss gamma != 2')
 
     @staticmethod
     def _norm_reducer():
@@ -440,53 +422,80 @@ class GFLHead(BBoxTestMixin, nn.Module):
 
         return _r
 
-    def _loss_dict(self, table, keys=LOSS_KEYS):
-        d = LossDict((k, [table[i, l] for l in range(table.shape[1])])
-                     for i, k in enumerate(LOSS_KEYS) if k in keys)
-        d.table, d.rows = table, [i for i, k in enumerate(LOSS_KEYS)
-                                  if k in keys]
+    def _loss_dict(self, table, keys=LOSS_KEYS, rows=None, want=None):
+        """The (8, L) table as the reference's dict of per-level scalars:
+        ``keys[i]`` from row ``rows[i]``, only the keys in ``want``."""
+        pairs = [(k, r) for k, r in zip(keys, rows or range(len(keys)))
+                 if want is None or k in want]
+        d = LossDict((k, [table[r, l] for l in range(table.shape[1])])
+                     for k, r in pairs)
+        d.table, d.rows = table, [r for _, r in pairs]
         return d
 
-    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas,
-             gt_bboxes_ignore=None):
-        """gfl_head.py:269-352 (plain GFL: QFL + GIoU + DFL)."""
-        self._check_loss_cfg()
+    def _level_sizes(self, cls_scores, num_levels):
         sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        device = cls_scores[0].device
-        hp = self._hp()
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
-        # no teacher, no features: feed the student's own (detached) outputs;
-        # every distillation weight is zero
-        dummy_x = [c.detach() for c in cls_scores]
-        hp.feat_channels = cls_scores[0].shape[1]
-        teacher = ([c.detach() for c in cls_scores],
-                   [b.detach() for b in bbox_preds], dummy_x)
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream,
-                                        *cls_scores, *bbox_preds, *dummy_x)
-        return self._loss_dict(table, ('loss_cls', 'loss_bbox', 'loss_dfl'))
+        assert len(sizes) == num_levels
+        return sizes
+
+    def _run_block(self, hp, targets, outs, teacher, feats=None, extra=(),
+                   reduce_norm=True, want=None):
+        """The fused loss block on ``outs`` = (cls_scores, bbox_preds).
+        ``teacher`` = (cls, reg, x[, kd]) maps, detached here; ``extra`` the
+        fourth student group (centernesses, or GFLv2's cls_feat).  ``feats`` =
+        None for a loss that reads no features: the student's own class maps
+        stand in for both feature sets (their term has weight zero)."""
+        cls_scores, bbox_preds = outs
+        teacher = [ts and [t.detach() for t in ts] for ts in teacher]
+        if feats is None:
+            feats = teacher[2] = [c.detach() for c in cls_scores]
+            hp.feat_channels = feats[0].shape[1]
+        table, _ = LB.LDLossBlock.apply(
+            hp, targets, tuple(teacher),
+            self._norm_reducer() if reduce_norm else None, self.unit_upstream,
+            *cls_scores, *bbox_preds, *feats, *extra)
+        self.last_targets = targets
+        return self._loss_dict(table, self._loss_keys, self._loss_rows, want)
+
+    def _loss(self, outs, gt_bboxes, gt_labels, img_metas, teacher=None,
+              extra=(), **hp_over):
+        """check -> hp -> targets -> block for the losses that read no
+        features.  Without a teacher the student's own detached outputs are
+        fed (every distillation weight is zero) and the plain keys returned."""
+        self._check_loss_cfg()
+        hp = self._hp(**hp_over)
+        targets = self._targets(hp, outs[0], img_metas, gt_bboxes, gt_labels)
+        if teacher is None:
+            return self._run_block(hp, targets, outs, (*outs, None),
+                                   extra=extra, want=self._plain_keys)
+        return self._run_block(hp, targets, outs, (*teacher[:2], None),
+                               extra=extra)
 
     def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None,
                       gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
         """base_dense_head.py:20-59."""
         outs = self(x)
-        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas,
-                           gt_bboxes_ignore=gt_bboxes_ignore)
         if proposal_cfg is not None:
-            raise NotImplementedError('get_bboxes (inference) is a "next" row '
-                                      'of SURVEY.md section 8f')
-        return losses
+            raise NotImplementedError('proposal_cfg')
+        return self.loss(*outs, gt_bboxes, gt_labels, img_metas,
+                         gt_bboxes_ignore=gt_bboxes_ignore)
 
-    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None,
-                   rescale=False, with_nms=True):
-        """anchor_head.py:497-589 + gfl_head.py:354-451 + multiclass_nms, one
-        C-ABI call for the whole batch (ld_get_bboxes).  Returns, per image,
-        ``(det_bboxes (k, 5), det_labels (k,))`` like the reference."""
-        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
-                                rescale, with_nms, prob=False)
+    def _forward_train_ld(self, x, out_teacher, teacher_x, img_metas,
+                          gt_bboxes, gt_labels, gt_bboxes_ignore, proposal_cfg):
+        """forward_train of the LD heads (ld_head.py:73-114, ld_gflv2.py:
+        74-114, ld_atss.py:252-290, ld_fcos_head.py:219-259, ld_retina.py:
+        139-185).  ``teacher_x`` = None for the heads whose loss reads no
+        features."""
+        outs = self(x)
+        if gt_labels is None:
+            raise NotImplementedError(f'{type(self).__name__} needs gt_labels')
+        if proposal_cfg is not None:
+            raise NotImplementedError('proposal_cfg')
+        soft = (out_teacher, ) if teacher_x is None else \
+            (out_teacher, self._loss_feats(x), teacher_x)
+        return self.loss(*outs, gt_bboxes, gt_labels, *soft, img_metas,
+                         gt_bboxes_ignore=gt_bboxes_ignore)
 
+    # ---------------------------------------------------------- inference --
     def _get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg, rescale,
                     with_nms, prob, centernesses=None, points=False,
                     strides=None, num_base=1):
@@ -524,9 +533,146 @@ class GFLHead(BBoxTestMixin, nn.Module):
 
 
 @HEADS.register_module()
-class LDHead(GFLHead):
-    """ld_head.py:43-637."""
+class GFLHead(_DenseHead):
+    """Constructor = AnchorHead.__init__ (anchor_head.py:31-96) +
+    GFLHead.__init__ (gfl_head.py:76-100)."""
+    _predictors = ('gfl_cls', 'gfl_reg')
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4,
+                 conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25),
+                 reg_max=16, feat_channels=256,
+                 anchor_generator=dict(type='AnchorGenerator', ratios=[1.0],
+                                       octave_base_scale=8,
+                                       scales_per_octave=1,
+                                       strides=[8, 16, 32, 64, 128]),
+                 bbox_coder=dict(type='DeltaXYWHBBoxCoder',
+                                 target_means=(.0, .0, .0, .0),
+                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
+                 reg_decoded_bbox=False,
+                 loss_cls=dict(type='QualityFocalLoss', use_sigmoid=True,
+                               beta=2.0, loss_weight=1.0),
+                 loss_bbox=dict(type='GIoULoss', loss_weight=2.0),
+                 train_cfg=None, test_cfg=None):
+        super().__init__()
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = (stacked_convs,
+                                                            conv_cfg, norm_cfg)
+        self.reg_max = reg_max
+        self.in_channels, self.num_classes = in_channels, num_classes
+        self.feat_channels = feat_channels
+        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
+        self.cls_out_channels = num_classes if self.use_sigmoid_cls \
+            else num_classes + 1
+        if self.cls_out_channels <= 0:
+            raise ValueError(f'num_classes={num_classes} is too small')
+        self.reg_decoded_bbox = reg_decoded_bbox
+        self.bbox_coder = build_bbox_coder(bbox_coder)
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_bbox = build_loss(loss_bbox)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        if self.train_cfg:
+            self.assigner = build_assigner(self.train_cfg.assigner)
+            self.sampler = build_sampler(dict(type='PseudoSampler'),
+                                         context=self)
+        self.sampling = False  # gfl_head.py:93 overrides AnchorHead's value
+        self.fp16_enabled = False
+        self.anchor_generator = build_anchor_generator(anchor_generator)
+        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+        self._init_layers()
+        # after the layers, like the reference (state_dict key order)
+        self.integral = Integral(self.reg_max)
+        self.loss_dfl = build_loss(loss_dfl)
+        # d(total)/d(loss_k) == 1 is promised by BaseDetector._parse_losses;
+        # SGDTrainer.step sets this for the duration of a train step so the
+        # backward reuses the gradient the fused forward launch already produced
+        self.unit_upstream = False
+
+    def _init_layers(self):
+        """gfl_head.py:102-133."""
+        self._build_towers()
+        assert self.num_anchors == 1, 'anchor free version'
+        self.gfl_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3,
+                              padding=1)
+        self.gfl_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3,
+                              padding=1)
+        self._build_scales(self.anchor_generator.strides)
+
+    def forward(self, feats):
+        """feats: tuple of per-level (N, C, H, W) -> (cls_scores, bbox_preds)
+        lists (gfl_head.py:145-183)."""
+        cls_feat, reg_feat, levels = self._trunk(feats)
+        cls3, _ = self.gfl_cls.forward3(cls_feat, levels)
+        reg3, _ = self.gfl_reg.forward3(reg_feat, levels)
+        reg3 = self._scale(reg3, levels)
+        return Y.split_levels(cls3, levels), Y.split_levels(reg3, levels)
+
+    # --------------------------------------------------------------- loss --
+    def _hp(self, **over):
+        kw = dict(topk=self.assigner.topk,
+                  qfl_beta=getattr(self.loss_cls, 'beta', 2.0),
+                  lw_dfl=self.loss_dfl.loss_weight)
+        kw.update(over)
+        return super()._hp(**kw)
+
+    def _check_loss_cfg(self):
+        from .losses import QualityFocalLoss
+        if not isinstance(self.loss_cls, QualityFocalLoss) or \
+                bbox_loss_mode(self.loss_bbox) is None:
+            raise NotImplementedError(
+                'the fused loss block implements QualityFocalLoss + '
+                f'{_BOX_LOSSES} (got {type(self.loss_cls).__name__}, '
+                f'{type(self.loss_bbox).__name__})')
+        self._check_train_cfg()
+
+    def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
+                            gt_labels, hp, device):
+        """AnchorHead.get_anchors + LDHead.get_targets for the whole batch in
+        two launches (ld_head.py:377-577)."""
+        strides = [s[0] for s in self.anchor_generator.strides]
+        if not self.anchor_generator.single_square:
+            # the implicit-anchor kernels build the one square anchor of a cell
+            # from an INTEGER scale (octave_base_scale * stride)
+            raise NotImplementedError(
+                f'{type(self).__name__}: one anchor per cell with a non-integer '
+                'scale or ratio != 1 (anchor_generator.py:78-98); the '
+                'single-anchor target kernels take ratios=[1.0] with an integer '
+                'octave_base_scale')
+        if gt_labels is None:
+            gt_labels = [b.new_zeros(b.shape[0], dtype=torch.long)
+                         for b in gt_bboxes]
+        return LB.atss_targets(featmap_sizes, strides, img_metas, gt_bboxes,
+                               gt_labels, hp, device,
+                               self.anchor_generator.anchor_scale)
+
+    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
+        sizes = self._level_sizes(cls_scores, self.anchor_generator.num_levels)
+        return self.get_targets_batched(sizes, img_metas, gt_bboxes, gt_labels,
+                                        hp, cls_scores[0].device)
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas,
+             gt_bboxes_ignore=None):
+        """gfl_head.py:269-352 (plain GFL: QFL + GIoU + DFL)."""
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas)
+
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None,
+                   rescale=False, with_nms=True):
+        """anchor_head.py:497-589 + gfl_head.py:354-451 + multiclass_nms, one
+        C-ABI call for the whole batch (ld_get_bboxes).  Returns, per image,
+        ``(det_bboxes (k, 5), det_labels (k,))`` like the reference."""
+        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
+                                rescale, with_nms, prob=False)
+
+
+class _FeatureLD:
+    """LDHead / LDv2Head (ld_head.py:43-637, ld_gflv2.py:44-644): LD on the
+    positives and on the valuable localisation region, KD on the class maps
+    and feature imitation, whose loss reads the neck features of student and
+    teacher.  The host class gives ``_split_teacher`` and its ``loss``
+    signature."""
     _wants_packed_feats = True
+    _feat256_ref = None  # where the reference hard-codes 256 channels
 
     def __init__(self, num_classes, in_channels,
                  loss_ld=dict(type='KnowledgeDistillationKLDivLoss',
@@ -546,69 +692,90 @@ class LDHead(GFLHead):
         self.loss_ld_vlr = build_loss(loss_ld_vlr)
         self.loss_kd = build_loss(loss_kd)
         self.iou_calculator = build_iou_calculator(dict(type='BboxOverlaps2D'))
-        # d(total)/d(loss_k) == 1 is promised by BaseDetector._parse_losses;
-        # the train engine sets this so the backward reuses the gradient the
-        # fused forward launch already produced
-        self.unit_upstream = False
-
-    def _imitation_flags(self, lw_im):
-        return _imitation_flags(self.imitation_method, lw_im)
 
     def forward_train(self, x, out_teacher, teacher_x, img_metas, gt_bboxes,
                       gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
                       **kwargs):
-        """ld_head.py:73-114."""
-        outs = self(x)
-        if gt_labels is None:
-            raise NotImplementedError('LDHead needs gt_labels')
-        losses = self.loss(*outs, gt_bboxes, gt_labels, out_teacher,
-                           self._loss_feats(x), teacher_x, img_metas,
-                           gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is not None:
-            raise NotImplementedError('get_bboxes (inference) is a "next" row '
-                                      'of SURVEY.md section 8f')
-        return losses
+        return self._forward_train_ld(x, out_teacher, teacher_x, img_metas,
+                                      gt_bboxes, gt_labels, gt_bboxes_ignore,
+                                      proposal_cfg)
 
-    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, soft_teacher,
-             x, teacher_x, img_metas, gt_bboxes_ignore=None):
-        """ld_head.py:284-375 -> dict of 8 lists of per-level scalars."""
+    def _ld_loss(self, outs, gt_bboxes, gt_labels, soft_teacher, x, teacher_x,
+                 img_metas, extra=()):
+        """-> dict of 8 lists of per-level scalars (LOSS_KEYS)."""
         self._check_loss_cfg()
         lw_im = float(self.loss_im.loss_weight)
-        im_flags = self._imitation_flags(lw_im)
+        im_flags = _imitation_flags(self.imitation_method, lw_im)
         if x[0].shape[1] != 256:
-            raise ValueError('LDHead hard-codes 256 feature channels '
-                             '(ld_head.py:153-154)')
-        soft_label, soft_target = soft_teacher
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        assert len(sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
+            raise ValueError(f'{type(self).__name__} hard-codes 256 feature '
+                             f'channels ({self._feat256_ref})')
         hp = self._hp(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
                       lw_ld_vlr=self.loss_ld_vlr.loss_weight,
                       T_ld_vlr=self.loss_ld_vlr.T,
                       lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T,
-                      lw_im=lw_im, flags=im_flags)
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
-        teacher = ([t.detach() for t in soft_label],
-                   [t.detach() for t in soft_target],
-                   [t.detach() for t in teacher_x])
+                      lw_im=lw_im)
+        hp.flags |= im_flags
+        targets = self._targets(hp, outs[0], img_metas, gt_bboxes, gt_labels)
+        t_kd, t_reg, *fourth = self._split_teacher(soft_teacher)
         if self.imitation_method == 'gibox' and lw_im != 0.0:
+            # ld_head.py:580-611; ld_gflv2.py:619-644 (there the raw teacher
+            # cls_feat against the student's probabilities, no sigmoids)
             targets = LB.gi_region(hp, targets,
-                                   [c.detach() for c in cls_scores],
-                                   [b.detach() for b in bbox_preds],
-                                   teacher[0], teacher[1])
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *x)
-        self.last_targets = targets
-        return self._loss_dict(table)
+                                   [c.detach() for c in outs[0]],
+                                   [b.detach() for b in outs[1]],
+                                   [t.detach() for t in t_kd],
+                                   [t.detach() for t in t_reg])
+        return self._run_block(hp, targets, outs,
+                               (t_kd, t_reg, teacher_x, *fourth), feats=x,
+                               extra=extra)
 
 
-ATSS_LOSS_KEYS = ['loss_cls', 'loss_bbox', 'loss_ld', 'loss_ld_neg',
-                  'loss_cls_kd', 'loss_centerness']
-# rows of the fused block's (8, L) table that carry them (LD_LOSS_ATSS)
-_ATSS_ROWS = [0, 1, 3, 4, 5, 6]
+@HEADS.register_module()
+class LDHead(_FeatureLD, GFLHead):
+    """ld_head.py:43-637."""
+    _feat256_ref = 'ld_head.py:153-154'
+
+    def _split_teacher(self, soft_teacher):
+        soft_label, soft_target = soft_teacher
+        return soft_label, soft_target
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, soft_teacher,
+             x, teacher_x, img_metas, gt_bboxes_ignore=None):
+        """ld_head.py:284-375."""
+        return self._ld_loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                             soft_teacher, x, teacher_x, img_metas)
+
+
+class _SideLD:
+    """LDATSSHead / LDFCOSHead / LDRetinaHead: LD on the positives weighted by
+    the max class score, ``_vlr_k`` x LD on the head's second region and KD on
+    the positives' class logits.  Their loss reads no features; the detector
+    calls them with output_feature=False:
+    forward_train(x, out_teacher, img_metas, ...)."""
+    _vlr_k = None
+
+    def __init__(self, num_classes, in_channels,
+                 loss_ld=dict(type='LocalizationDistillationLoss',
+                              loss_weight=0.25, T=10),
+                 loss_kd=None, **kwargs):
+        super().__init__(num_classes, in_channels, **kwargs)
+        self.loss_ld = build_loss(loss_ld)
+        self.loss_kd = build_loss(loss_kd)
+
+    def forward_train(self, x, out_teacher, img_metas, gt_bboxes,
+                      gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
+                      **kwargs):
+        return self._forward_train_ld(x, out_teacher, None, img_metas,
+                                      gt_bboxes, gt_labels, gt_bboxes_ignore,
+                                      proposal_cfg)
+
+    def _ld_hp(self):
+        """The reference's second term is _vlr_k * loss_ld(..., avg_factor=4);
+        the block's VLR term is lw_ld_vlr * sum / 16."""
+        return dict(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
+                    lw_ld_vlr=self._vlr_k * 4.0 * self.loss_ld.loss_weight,
+                    T_ld_vlr=self.loss_ld.T,
+                    lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T)
 
 
 @HEADS.register_module()
@@ -618,6 +785,9 @@ class ATSSGFLHead(GFLHead):
     ``atss_centerness`` output convs (state_dict names of the reference),
     FocalLoss + centerness-weighted GIoU + centerness BCE.  forward returns
     (cls_scores, bbox_preds, centernesses)."""
+    _predictors = ('atss_cls', 'atss_reg', 'atss_centerness')
+    _loss_keys, _loss_rows = ATSS_LOSS_KEYS, _ATSS_ROWS
+    _plain_keys = ('loss_cls', 'loss_bbox', 'loss_centerness')
 
     def __init__(self, num_classes, in_channels, stacked_convs=4,
                  conv_cfg=None,
@@ -640,17 +810,7 @@ class ATSSGFLHead(GFLHead):
 
     def _init_layers(self):
         """atss_gfl_head.py:90-125."""
-        self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
-            self.reg_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
+        self._build_towers()
         assert self.num_anchors == 1, 'one square anchor per position'
         self.atss_cls = Conv2d(self.feat_channels,
                                self.num_anchors * self.cls_out_channels, 3,
@@ -659,49 +819,21 @@ class ATSSGFLHead(GFLHead):
                                padding=1)
         self.atss_centerness = Conv2d(self.feat_channels, self.num_anchors, 3,
                                       padding=1)
-        self.scales = nn.ModuleList(
-            [Scale(1.0) for _ in self.anchor_generator.strides])
-
-    def init_weights(self):
-        """atss_gfl_head.py:127-137."""
-        for m in self.cls_convs:
-            normal_init(m.conv, std=0.01)
-        for m in self.reg_convs:
-            normal_init(m.conv, std=0.01)
-        normal_init(self.atss_cls, std=0.01, bias=bias_init_with_prob(0.01))
-        normal_init(self.atss_reg, std=0.01)
-        normal_init(self.atss_centerness, std=0.01)
+        self._build_scales(self.anchor_generator.strides)
 
     def forward(self, feats):
-        """atss_gfl_head.py:139-183, all levels in one launch per layer."""
-        assert len(feats) == len(self.scales)
-        x3, levels = self._pack(feats)
-        cls_feat = reg_feat = x3
-        cls_feat = _tower(self.cls_convs, cls_feat, levels)
-        reg_feat = _tower(self.reg_convs, reg_feat, levels)
+        """atss_gfl_head.py:139-183."""
+        cls_feat, reg_feat, levels = self._trunk(feats)
         cls3, _ = self.atss_cls.forward3(cls_feat, levels)
         reg3, _ = self.atss_reg.forward3(reg_feat, levels)
         ctr3, _ = self.atss_centerness.forward3(reg_feat, levels)
-        scales = torch.stack([s.scale for s in self.scales])
-        reg3 = Y.scale_levels(reg3, scales, levels)
+        reg3 = self._scale(reg3, levels)
         return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
                 Y.split_levels(ctr3, levels))
 
     def _check_loss_cfg(self):
-        from .losses import CrossEntropyLoss, FocalLoss
-        if not isinstance(self.loss_cls, FocalLoss) or \
-                bbox_loss_mode(self.loss_bbox) is None or \
-                not isinstance(self.loss_centerness, CrossEntropyLoss) or \
-                not self.loss_centerness.use_sigmoid:
-            raise NotImplementedError(
-                'the fused ATSS loss block implements FocalLoss + GIoULoss + '
-                'sigmoid CrossEntropyLoss centerness')
-        if self.loss_cls.gamma != 2.0:
-            raise NotImplementedError('FocalLoss gamma != 2')
-        if self.train_cfg.get('allowed_border', -1) >= 0:
-            raise NotImplementedError('allowed_border >= 0')
-        if self.train_cfg.get('pos_weight', -1) > 0:
-            raise NotImplementedError('pos_weight > 0')
+        self._check_focal_cfg('ATSS', centerness=True)
+        self._check_train_cfg()
 
     def _hp(self, **over):
         kw = dict(lw_dfl=0.0, lw_ctr=self.loss_centerness.loss_weight,
@@ -710,32 +842,11 @@ class ATSSGFLHead(GFLHead):
         kw.update(over)
         return super()._hp(**kw)
 
-    def _atss_loss_dict(self, table, keys):
-        d = LossDict((k, [table[r, l] for l in range(table.shape[1])])
-                     for k, r in zip(ATSS_LOSS_KEYS, _ATSS_ROWS) if k in keys)
-        d.table = table
-        d.rows = [r for k, r in zip(ATSS_LOSS_KEYS, _ATSS_ROWS) if k in keys]
-        return d
-
     def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
              img_metas, gt_bboxes_ignore=None):
         """atss_gfl_head.py:187-310: loss_cls, loss_bbox, loss_centerness."""
-        self._check_loss_cfg()
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        device = cls_scores[0].device
-        hp = self._hp()
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
-        dummy_x = [c.detach() for c in cls_scores]
-        hp.feat_channels = cls_scores[0].shape[1]
-        teacher = ([c.detach() for c in cls_scores],
-                   [b.detach() for b in bbox_preds], dummy_x)
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *dummy_x, *centernesses)
-        return self._atss_loss_dict(table, ('loss_cls', 'loss_bbox',
-                                            'loss_centerness'))
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, extra=centernesses)
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
                    cfg=None, rescale=False, with_nms=True):
@@ -748,71 +859,33 @@ class ATSSGFLHead(GFLHead):
 
 
 @HEADS.register_module()
-class LDATSSHead(ATSSGFLHead):
-    """ld_atss.py:13-250: localization distillation on the ATSS-GFL head --
-    LD on the positives weighted by the max class score, 0.15 x LD on the
-    valuable localisation region, KD on the positives' class logits.  The
-    detector calls it with output_feature=False:
-    forward_train(x, out_teacher, img_metas, ...)."""
-
-    def __init__(self, num_classes, in_channels,
-                 loss_ld=dict(type='LocalizationDistillationLoss',
-                              loss_weight=0.25, T=10),
-                 loss_kd=None, **kwargs):
-        super().__init__(num_classes, in_channels, **kwargs)
-        self.loss_ld = build_loss(loss_ld)
-        self.loss_kd = build_loss(loss_kd)
-
-    def forward_train(self, x, out_teacher, img_metas, gt_bboxes,
-                      gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
-                      **kwargs):
-        """ld_atss.py:252-290."""
-        outs = self(x)
-        if gt_labels is None:
-            raise NotImplementedError('LDATSSHead needs gt_labels')
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*outs, gt_bboxes, gt_labels, out_teacher, img_metas,
-                         gt_bboxes_ignore=gt_bboxes_ignore)
+class LDATSSHead(_SideLD, ATSSGFLHead):
+    """ld_atss.py:13-250: localization distillation on the ATSS-GFL head; the
+    second region is the valuable localisation region."""
+    # loss_ld_neg = 0.15 * loss_ld(..., avg_factor=4) (ld_atss.py:148-159)
+    _vlr_k = 0.15
 
     def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
              soft_target, img_metas, gt_bboxes_ignore=None):
         """ld_atss.py:168-250 -> the six keys of ATSS_LOSS_KEYS."""
-        self._check_loss_cfg()
-        soft_labels, soft_corners = soft_target[0], soft_target[1]
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        assert len(sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        # loss_ld_neg = 0.15 * loss_ld(..., avg_factor=4) on the VLR region
-        # (ld_atss.py:148-159); the block's VLR term is lw_ld_vlr * sum / 16
-        hp = self._hp(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
-                      lw_ld_vlr=0.15 * 4.0 * self.loss_ld.loss_weight,
-                      T_ld_vlr=self.loss_ld.T,
-                      lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T)
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
-        dummy_x = [c.detach() for c in cls_scores]
-        hp.feat_channels = cls_scores[0].shape[1]
-        teacher = ([t.detach() for t in soft_labels],
-                   [t.detach() for t in soft_corners], dummy_x)
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *dummy_x, *centernesses)
-        self.last_targets = targets
-        return self._atss_loss_dict(table, ATSS_LOSS_KEYS)
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, teacher=soft_target, extra=centernesses,
+                          **self._ld_hp())
 
 
 INF = 1e8
 
 
 @HEADS.register_module()
-class FCOSGFLHead(BBoxTestMixin, nn.Module):
+class FCOSGFLHead(_DenseHead):
     """fcos_gfl_head.py:52-346 over anchor_free_head.py:15-130: the anchor-free
     FCOS head with a general-distribution box branch.  Parameters
     ``cls_convs / reg_convs / conv_cls / conv_reg / conv_centerness / scales``
     as in the reference; forward returns (cls_scores, bbox_preds,
     centernesses); points are (x, y) * stride + stride // 2."""
+    _predictors = ('conv_cls', 'conv_reg', 'conv_centerness')
+    _loss_keys, _loss_rows = ATSS_LOSS_KEYS, _ATSS_ROWS
+    _plain_keys = ('loss_cls', 'loss_bbox', 'loss_centerness')
 
     def __init__(self, num_classes, in_channels, feat_channels=256,
                  stacked_convs=4, strides=(4, 8, 16, 32, 64),
@@ -857,78 +930,34 @@ class FCOSGFLHead(BBoxTestMixin, nn.Module):
 
     def _init_layers(self):
         """fcos_gfl_head.py:134-165."""
-        self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
-            self.reg_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
+        self._build_towers()
         self.conv_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3,
                                padding=1)
         self.conv_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3,
                                padding=1)
         self.conv_centerness = Conv2d(self.feat_channels, 1, 3, padding=1)
-        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
-
-    def init_weights(self):
-        """fcos_gfl_head.py:167-176."""
-        for m in self.cls_convs:
-            normal_init(m.conv, std=0.01)
-        for m in self.reg_convs:
-            normal_init(m.conv, std=0.01)
-        normal_init(self.conv_cls, std=0.01, bias=bias_init_with_prob(0.01))
-        normal_init(self.conv_reg, std=0.01)
-        normal_init(self.conv_centerness, std=0.01)
+        self._build_scales(self.strides)
 
     def forward(self, feats):
-        """fcos_gfl_head.py:178-224, all levels in one launch per layer."""
-        assert len(feats) == len(self.scales)
-        x3, levels = Y.pack_levels(feats)
-        cls_feat = reg_feat = x3
-        cls_feat = _tower(self.cls_convs, cls_feat, levels)
-        reg_feat = _tower(self.reg_convs, reg_feat, levels)
+        """fcos_gfl_head.py:178-224."""
+        cls_feat, reg_feat, levels = self._trunk(feats)
         cls3, _ = self.conv_cls.forward3(cls_feat, levels)
         reg3, _ = self.conv_reg.forward3(reg_feat, levels)
         ctr3, _ = self.conv_centerness.forward3(reg_feat, levels)
-        scales = torch.stack([s.scale for s in self.scales])
-        reg3 = Y.scale_levels(reg3, scales, levels)
+        reg3 = self._scale(reg3, levels)
         return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
                 Y.split_levels(ctr3, levels))
 
     # ---------------------------------------------------------------- loss --
-    _norm_reducer = staticmethod(GFLHead._norm_reducer)
-
     def _check_loss_cfg(self):
-        from .losses import CrossEntropyLoss, FocalLoss
-        if not isinstance(self.loss_cls, FocalLoss) or \
-                bbox_loss_mode(self.loss_bbox) is None or \
-                not isinstance(self.loss_centerness, CrossEntropyLoss) or \
-                not self.loss_centerness.use_sigmoid:
-            raise NotImplementedError(
-                'the fused FCOS loss block implements FocalLoss + GIoULoss + '
-                'sigmoid CrossEntropyLoss centerness')
-        if self.loss_cls.gamma != 2.0:
-            raise NotImplementedError('FocalLoss gamma != 2')
+        self._check_focal_cfg('FCOS', centerness=True)
 
     def _hp(self, **over):
-        kw = dict(num_classes=self.num_classes, reg_max=self.reg_max, topk=9,
-                  feat_channels=self.feat_channels,
-                  lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
-                  lw_bbox=self.loss_bbox.loss_weight,
-                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
-                  bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou', lw_dfl=0.0,
-                  lw_ld=0.0, T_ld=1.0, lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0,
-                  T_kd=1.0, lw_im=0.0,
-                  lw_ctr=self.loss_centerness.loss_weight,
+        kw = dict(lw_ctr=self.loss_centerness.loss_weight,
                   focal_alpha=self.loss_cls.alpha,
                   flags=L.LD_LOSS_ATSS | L.LD_LOSS_FCOS)
         kw.update(over)
-        return LB.make_hp(**kw)
+        return super()._hp(**kw)
 
     def get_targets_batched(self, featmap_sizes, gt_bboxes, gt_labels, device):
         """get_points + get_targets (ld_fcos_head.py:261-414) for the whole
@@ -938,103 +967,45 @@ class FCOSGFLHead(BBoxTestMixin, nn.Module):
                                self.regress_ranges, self.center_sampling,
                                self.center_sample_radius, device)
 
-    def _run_block(self, hp, cls_scores, bbox_preds, centernesses, gt_bboxes,
-                   gt_labels, t_cls, t_reg, keys):
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        assert len(sizes) == len(self.strides)
-        device = cls_scores[0].device
-        targets = self.get_targets_batched(sizes, gt_bboxes, gt_labels, device)
-        dummy_x = [c.detach() for c in cls_scores]
-        hp.feat_channels = cls_scores[0].shape[1]
-        teacher = ([t.detach() for t in t_cls], [t.detach() for t in t_reg],
-                   dummy_x)
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *dummy_x, *centernesses)
-        self.last_targets = targets
-        d = LossDict((k, [table[r, l] for l in range(table.shape[1])])
-                     for k, r in zip(ATSS_LOSS_KEYS, _ATSS_ROWS) if k in keys)
-        d.table = table
-        d.rows = [r for k, r in zip(ATSS_LOSS_KEYS, _ATSS_ROWS) if k in keys]
-        return d
+    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
+        sizes = self._level_sizes(cls_scores, len(self.strides))
+        return self.get_targets_batched(sizes, gt_bboxes, gt_labels,
+                                        cls_scores[0].device)
 
     def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
              img_metas, gt_bboxes_ignore=None):
         """fcos_gfl_head.py:276-345: loss_cls, loss_bbox, loss_centerness."""
-        self._check_loss_cfg()
-        return self._run_block(self._hp(), cls_scores, bbox_preds,
-                               centernesses, gt_bboxes, gt_labels, cls_scores,
-                               bbox_preds, ('loss_cls', 'loss_bbox',
-                                            'loss_centerness'))
-
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None,
-                      gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*self(x), gt_bboxes, gt_labels, img_metas,
-                         gt_bboxes_ignore=gt_bboxes_ignore)
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, extra=centernesses)
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
                    cfg=None, rescale=False, with_nms=True):
         """fcos_gfl_head.py:347-546: as ATSSGFLHead.get_bboxes, decoded about
         the FCOS points (x, y) * stride + stride // 2."""
-        return GFLHead._get_bboxes(self, cls_scores, bbox_preds, img_metas,
-                                   cfg, rescale, with_nms, prob=False,
-                                   centernesses=centernesses, points=True,
-                                   strides=self.strides)
+        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
+                                rescale, with_nms, prob=False,
+                                centernesses=centernesses, points=True,
+                                strides=self.strides)
 
 
 @HEADS.register_module()
-class LDFCOSHead(FCOSGFLHead):
-    """ld_fcos_head.py:13-445: localization distillation on the FCOS-GFL head:
-    LD on the positives weighted by the max class score, 0.25 x LD on the
-    "remain" points (inside a gt box, assigned to none) weighted by the
-    student's max class score, KD on the positives' class logits."""
-
-    def __init__(self, num_classes, in_channels,
-                 loss_ld=dict(type='LocalizationDistillationLoss',
-                              loss_weight=0.25, T=10),
-                 loss_kd=None, **kwargs):
-        super().__init__(num_classes, in_channels, **kwargs)
-        self.loss_ld = build_loss(loss_ld)
-        self.loss_kd = build_loss(loss_kd)
-
-    def forward_train(self, x, out_teacher, img_metas, gt_bboxes,
-                      gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
-                      **kwargs):
-        """ld_fcos_head.py:219-259."""
-        if gt_labels is None:
-            raise NotImplementedError('LDFCOSHead needs gt_labels')
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*self(x), gt_bboxes, gt_labels, out_teacher,
-                         img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+class LDFCOSHead(_SideLD, FCOSGFLHead):
+    """ld_fcos_head.py:13-445: localization distillation on the FCOS-GFL head;
+    the second region is the "remain" points (inside a gt box, assigned to
+    none), weighted by the student's max class score."""
+    # loss_ld_neg = 0.25 * loss_ld(..., avg_factor=4) (ld_fcos_head.py:125-129)
+    _vlr_k = 0.25
 
     def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
              out_teacher, img_metas, gt_bboxes_ignore=None):
         """ld_fcos_head.py:138-217 -> the six keys of ATSS_LOSS_KEYS."""
-        self._check_loss_cfg()
-        soft_labels, soft_targets = out_teacher[0], out_teacher[1]
-        # loss_ld_neg = 0.25 * loss_ld(..., avg_factor=4) (ld_fcos_head.py:
-        # 125-129); the block's VLR term is lw_ld_vlr * sum / 16
-        hp = self._hp(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
-                      lw_ld_vlr=0.25 * 4.0 * self.loss_ld.loss_weight,
-                      T_ld_vlr=self.loss_ld.T,
-                      lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T)
-        return self._run_block(hp, cls_scores, bbox_preds, centernesses,
-                               gt_bboxes, gt_labels, soft_labels, soft_targets,
-                               ATSS_LOSS_KEYS)
-
-
-RETINA_LOSS_KEYS = ['loss_cls', 'loss_bbox', 'loss_ld', 'loss_ld_vlr',
-                    'loss_cls_kd']
-# rows of the fused block's (8, L) table that carry them (LD_LOSS_RETINA)
-_RETINA_ROWS = [0, 1, 3, 4, 5]
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, teacher=out_teacher, extra=centernesses,
+                          **self._ld_hp())
 
 
 @HEADS.register_module()
-class RetinaGFLHead(BBoxTestMixin, nn.Module):
+class RetinaGFLHead(_DenseHead):
     """retina_gfl_head.py:50-330 over anchor_head.py:14-173: the RetinaNet head
     (ratios x scales anchors per cell, conv + ReLU towers without a norm
     layer) with a general-distribution box branch.  ``atss_cls`` /
@@ -1044,6 +1015,9 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
     Loss execution: the B anchors of a cell are B pseudo-images of the fused
     one-anchor-per-cell loss block (an (N, B * C, H, W) map IS the (N * B, C,
     H, W) map of them), targets come from ld_retina_targets."""
+    _predictors = ('atss_cls', 'atss_reg')
+    _loss_keys, _loss_rows = RETINA_LOSS_KEYS, _RETINA_ROWS
+    _plain_keys = ('loss_cls', 'loss_bbox')
 
     def __init__(self, num_classes, in_channels, stacked_convs=4,
                  conv_cfg=None, norm_cfg=None, reg_max=16, feat_channels=256,
@@ -1085,22 +1059,13 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
         self.anchor_generator = build_anchor_generator(anchor_generator)
         self.num_anchors = self.anchor_generator.num_base_anchors[0]
         self._init_layers()
+        # after the layers, like the reference (state_dict key order)
         self.integral = Integral(self.reg_max)
         self.unit_upstream = False
 
     def _init_layers(self):
-        """retina_gfl_head.py:231-264."""
-        self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
-            self.reg_convs.append(
-                ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
+        """retina_gfl_head.py:231-264 (no per-level Scale)."""
+        self._build_towers()
         self.atss_cls = Conv2d(self.feat_channels,
                                self.num_anchors * self.cls_out_channels, 3,
                                padding=1)
@@ -1108,60 +1073,30 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
                                self.num_anchors * (self.reg_max + 1) * 4, 3,
                                padding=1)
 
-    def init_weights(self):
-        """retina_gfl_head.py:266-274."""
-        for m in self.cls_convs:
-            normal_init(m.conv, std=0.01)
-        for m in self.reg_convs:
-            normal_init(m.conv, std=0.01)
-        normal_init(self.atss_cls, std=0.01, bias=bias_init_with_prob(0.01))
-        normal_init(self.atss_reg, std=0.01)
-
     def forward(self, feats):
-        """retina_gfl_head.py:276-299, all levels in one launch per layer."""
-        x3, levels = Y.pack_levels(feats)
-        cls_feat = reg_feat = x3
-        cls_feat = _tower(self.cls_convs, cls_feat, levels)
-        reg_feat = _tower(self.reg_convs, reg_feat, levels)
+        """retina_gfl_head.py:276-299."""
+        cls_feat, reg_feat, levels = self._trunk(feats)
         cls3, _ = self.atss_cls.forward3(cls_feat, levels)
         reg3, _ = self.atss_reg.forward3(reg_feat, levels)
         return Y.split_levels(cls3, levels), Y.split_levels(reg3, levels)
 
-    anchor_center = GFLHead.anchor_center
-    get_anchors = GFLHead.get_anchors
-
     # ---------------------------------------------------------------- loss --
     def _check_loss_cfg(self):
-        from .losses import FocalLoss
-        if not isinstance(self.loss_cls, FocalLoss) or \
-                bbox_loss_mode(self.loss_bbox) is None or \
-                not self.reg_decoded_bbox:
+        if not self.reg_decoded_bbox:
             raise NotImplementedError(
-                'the fused RetinaGFL loss block implements FocalLoss + '
-                'GIoULoss on decoded boxes (reg_decoded_bbox=True)')
-        if self.loss_cls.gamma != 2.0:
-            raise NotImplementedError('FocalLoss gamma != 2')
-        if self.train_cfg.get('allowed_border', -1) >= 0:
-            raise NotImplementedError('allowed_border >= 0')
-        if self.train_cfg.get('pos_weight', -1) > 0:
-            raise NotImplementedError('pos_weight > 0')
+                'the fused RetinaGFL loss block evaluates its box loss on '
+                'decoded boxes (reg_decoded_bbox=True)')
+        self._check_focal_cfg('RetinaGFL', centerness=False)
+        self._check_train_cfg()
         if type(self.assigner).__name__ != 'MaxIoUAssigner':
             raise NotImplementedError(
                 f'{type(self.assigner).__name__}: the RetinaGFL targets kernel '
                 'implements MaxIoUAssigner')
 
     def _hp(self, **over):
-        kw = dict(num_classes=self.num_classes, reg_max=self.reg_max, topk=9,
-                  feat_channels=self.feat_channels,
-                  lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
-                  lw_bbox=self.loss_bbox.loss_weight,
-                  giou_eps=getattr(self.loss_bbox, 'eps', 1e-6),
-                  bbox_loss=bbox_loss_mode(self.loss_bbox) or 'giou', lw_dfl=0.0,
-                  lw_ld=0.0, T_ld=1.0, lw_ld_vlr=0.0, T_ld_vlr=1.0, lw_kd=0.0,
-                  T_kd=1.0, lw_im=0.0, focal_alpha=self.loss_cls.alpha,
-                  flags=L.LD_LOSS_RETINA)
+        kw = dict(focal_alpha=self.loss_cls.alpha, flags=L.LD_LOSS_RETINA)
         kw.update(over)
-        return LB.make_hp(**kw)
+        return super()._hp(**kw)
 
     def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
                             gt_labels, device, want_gt_inds=False):
@@ -1178,108 +1113,57 @@ class RetinaGFLHead(BBoxTestMixin, nn.Module):
                                  self.assigner, self.num_classes, device,
                                  want_gt_inds=want_gt_inds)
 
+    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
+        sizes = self._level_sizes(cls_scores, self.anchor_generator.num_levels)
+        return self.get_targets_batched(sizes, img_metas, gt_bboxes, gt_labels,
+                                        cls_scores[0].device)
+
     def _pseudo(self, maps, channels):
         """(N, B * C, H, W) -> the (N * B, C, H, W) view of the same memory."""
         B = self.num_anchors
         return [t.view(t.shape[0] * B, channels, t.shape[2], t.shape[3])
                 for t in maps]
 
-    def _run_block(self, hp, cls_scores, bbox_preds, gt_bboxes, gt_labels,
-                   img_metas, t_cls, t_reg, keys):
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        assert len(sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, device)
+    def _run_block(self, hp, targets, outs, teacher, **kw):
+        """The block runs on the pseudo-image views.  num_total_samples is the
+        LOCAL count (ld_retina.py:228-229): no cross-rank reduction of the
+        normaliser."""
         C_, R4 = self.cls_out_channels, 4 * (self.reg_max + 1)
-        cls_p, reg_p = self._pseudo(cls_scores, C_), self._pseudo(bbox_preds,
-                                                                  R4)
-        t_cls_p = self._pseudo([t.detach() for t in t_cls], C_)
-        t_reg_p = self._pseudo([t.detach() for t in t_reg], R4)
-        dummy_x = [c.detach() for c in cls_p]
-        hp.feat_channels = C_
-        # num_total_samples is the LOCAL count (ld_retina.py:228-229): no
-        # cross-rank reduction of the normaliser
-        table, _ = LB.LDLossBlock.apply(hp, targets, (t_cls_p, t_reg_p,
-                                                      dummy_x), None,
-                                        self.unit_upstream, *cls_p, *reg_p,
-                                        *dummy_x)
-        self.last_targets = targets
-        d = LossDict((k, [table[r, l] for l in range(table.shape[1])])
-                     for k, r in zip(RETINA_LOSS_KEYS, _RETINA_ROWS)
-                     if k in keys)
-        d.table = table
-        d.rows = [r for k, r in zip(RETINA_LOSS_KEYS, _RETINA_ROWS)
-                  if k in keys]
-        return d
+        outs = self._pseudo(outs[0], C_), self._pseudo(outs[1], R4)
+        teacher = (self._pseudo(teacher[0], C_), self._pseudo(teacher[1], R4),
+                   None)
+        return super()._run_block(hp, targets, outs, teacher,
+                                  reduce_norm=False, **kw)
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas,
              gt_bboxes_ignore=None):
         """retina_gfl_head.py:157-229: loss_cls, loss_bbox."""
-        self._check_loss_cfg()
-        return self._run_block(self._hp(), cls_scores, bbox_preds, gt_bboxes,
-                               gt_labels, img_metas, cls_scores, bbox_preds,
-                               ('loss_cls', 'loss_bbox'))
-
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None,
-                      gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*self(x), gt_bboxes, gt_labels, img_metas,
-                         gt_bboxes_ignore=gt_bboxes_ignore)
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas)
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None,
                    rescale=False, with_nms=True):
         """anchor_head.py:497-589 + retina_gfl_head.py:301-412: sigmoid scores,
         Integral * stride, per-level top-nms_pre over all (cell, base anchor)
         rows, decode about the cell centre, multiclass_nms."""
-        return GFLHead._get_bboxes(self, cls_scores, bbox_preds, img_metas,
-                                   cfg, rescale, with_nms, prob=False,
-                                   num_base=self.num_anchors)
+        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
+                                rescale, with_nms, prob=False,
+                                num_base=self.num_anchors)
 
 
 @HEADS.register_module()
-class LDRetinaHead(RetinaGFLHead):
-    """ld_retina.py:13-636: localization distillation on the RetinaGFL head --
-    LD over the 68 corner logits of every positive anchor weighted by its max
-    class score, 0.03 x the same on the valuable localisation region of the
-    background anchors, KD on the positives' class logits.  The detector calls
-    it with output_feature=False: forward_train(x, out_teacher, img_metas,
-    ...)."""
-
-    def __init__(self, num_classes, in_channels,
-                 loss_ld=dict(type='LocalizationDistillationLoss',
-                              loss_weight=0.25, T=10),
-                 loss_kd=None, **kwargs):
-        super().__init__(num_classes, in_channels, **kwargs)
-        self.loss_ld = build_loss(loss_ld)
-        self.loss_kd = build_loss(loss_kd)
-
-    def forward_train(self, x, out_teacher, img_metas, gt_bboxes,
-                      gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
-                      **kwargs):
-        """ld_retina.py:139-185."""
-        if gt_labels is None:
-            raise NotImplementedError('LDRetinaHead needs gt_labels')
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*self(x), gt_bboxes, gt_labels, out_teacher,
-                         img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+class LDRetinaHead(_SideLD, RetinaGFLHead):
+    """ld_retina.py:13-636: localization distillation on the RetinaGFL head,
+    LD over the 68 corner logits of every positive anchor; the second region
+    is the valuable localisation region of the background anchors."""
+    # loss_ld_vlr = 0.03 * loss_ld(..., avg_factor=4) (ld_retina.py:109-110)
+    _vlr_k = 0.03
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, out_teacher,
              img_metas, gt_bboxes_ignore=None):
         """ld_retina.py:187-254 -> the five keys of RETINA_LOSS_KEYS."""
-        self._check_loss_cfg()
-        soft_labels, soft_targets = out_teacher[0], out_teacher[1]
-        # loss_ld_vlr = 0.03 * loss_ld(..., avg_factor=4) (ld_retina.py:109-110);
-        # the block's VLR term is lw_ld_vlr * sum / 16
-        hp = self._hp(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
-                      lw_ld_vlr=0.03 * 4.0 * self.loss_ld.loss_weight,
-                      T_ld_vlr=self.loss_ld.T,
-                      lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T)
-        return self._run_block(hp, cls_scores, bbox_preds, gt_bboxes,
-                               gt_labels, img_metas, soft_labels, soft_targets,
-                               RETINA_LOSS_KEYS)
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, teacher=out_teacher, **self._ld_hp())
 
 
 class _Marker(nn.Module):
@@ -1339,17 +1223,12 @@ class GFocalHead(GFLHead):
                 normal_init(m, std=0.01)
 
     def forward(self, feats):
-        """gfocal_head.py:160-217, all levels per launch: towers, predictors,
-        per-level Scale, then the fused quality kernel."""
-        assert len(feats) == len(self.scales)
-        x3, levels = self._pack(feats)
-        cls_feat = reg_feat = x3
-        cls_feat = _tower(self.cls_convs, cls_feat, levels)
-        reg_feat = _tower(self.reg_convs, reg_feat, levels)
+        """gfocal_head.py:160-217: GFLHead's forward, then the fused quality
+        kernel."""
+        cls_feat, reg_feat, levels = self._trunk(feats)
         cls3, _ = self.gfl_cls.forward3(cls_feat, levels)
         reg3, _ = self.gfl_reg.forward3(reg_feat, levels)
-        scales = torch.stack([s.scale for s in self.scales])
-        reg3 = Y.scale_levels(reg3, scales, levels)
+        reg3 = self._scale(reg3, levels)
         c0, c2 = self.reg_conf[0], self.reg_conf[2]
         score3, _ = Y.QualityFn.apply(reg3, cls3, c0.weight, c0.bias,
                                       c2.weight, c2.bias)
@@ -1357,9 +1236,10 @@ class GFocalHead(GFLHead):
                 Y.split_levels(cls3, levels))
 
     def _hp(self, **over):
-        over.setdefault('cls_channels', self.cls_out_channels)
-        over.setdefault('flags', L.LD_LOSS_PROB_CLS)
-        return super()._hp(**over)
+        kw = dict(cls_channels=self.cls_out_channels,
+                  flags=L.LD_LOSS_PROB_CLS)
+        kw.update(over)
+        return super()._hp(**kw)
 
     def _check_loss_cfg(self):
         super()._check_loss_cfg()
@@ -1372,30 +1252,18 @@ class GFocalHead(GFLHead):
     def loss(self, cls_scores, bbox_preds, cls_feat, gt_bboxes, gt_labels,
              img_metas, gt_bboxes_ignore=None):
         """gfocal_head.py:230-352 (plain GFLv2: QFL on probabilities + GIoU +
-        DFL); the distillation terms of the fused block run with weight 0 on
-        the student's own detached maps."""
+        DFL); the KD term of the fused block reads cls_feat, so the student's
+        own detached cls_feat is its KD teacher and stands in for the
+        features."""
         self._check_loss_cfg()
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        device = cls_scores[0].device
         hp = self._hp()
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
+        targets = self._targets(hp, cls_scores, img_metas, gt_bboxes,
+                                gt_labels)
         det = [c.detach() for c in cls_feat]
-        hp.feat_channels = cls_feat[0].shape[1]
-        teacher = (det, [b.detach() for b in bbox_preds], det, det)
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *det, *cls_feat)
-        return self._loss_dict(table, ('loss_cls', 'loss_bbox', 'loss_dfl'))
-
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None,
-                      gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        outs = self(x)
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*outs, gt_bboxes, gt_labels, img_metas,
-                         gt_bboxes_ignore=gt_bboxes_ignore)
+        hp.feat_channels = det[0].shape[1]
+        return self._run_block(hp, targets, (cls_scores, bbox_preds),
+                               (det, bbox_preds, det, det), feats=det,
+                               extra=cls_feat, want=self._plain_keys)
 
     def get_bboxes(self, cls_scores, bbox_preds, cls_feat, img_metas, cfg=None,
                    rescale=False, with_nms=True):
@@ -1410,81 +1278,22 @@ class GFocalHead(GFLHead):
 
 
 @HEADS.register_module()
-class LDv2Head(GFocalHead):
+class LDv2Head(_FeatureLD, GFocalHead):
     """ld_gflv2.py:44-644: LDHead's distillation terms on a GFocalHead.
     Differences from LDHead that the fused block is told through its hp flags
     (ld_gflv2.py:200,243,326): weight_targets = max_c cls_score with no
     sigmoid, QFL on probabilities over 81 channels, KD on the raw cls_feat of
     student and teacher (``soft_teacher`` = (cls_score, bbox_pred, cls_feat),
     of which the first is ignored)."""
-    _wants_packed_feats = True
+    _feat256_ref = 'ld_gflv2.py:155-156'
 
-    def __init__(self, num_classes, in_channels,
-                 loss_ld=dict(type='KnowledgeDistillationKLDivLoss',
-                              loss_weight=0.25, T=10),
-                 loss_ld_vlr=dict(type='KnowledgeDistillationKLDivLoss',
-                                  loss_weight=0.25, T=10),
-                 loss_kd=dict(type='KnowledgeDistillationKLDivLoss',
-                              loss_weight=10, T=2),
-                 loss_im=dict(type='IMLoss', loss_weight=0),
-                 imitation_method='gibox', **kwargs):
-        super().__init__(num_classes, in_channels, **kwargs)
-        assert imitation_method in ['gibox', 'finegrained', 'fitnet',
-                                    'decouple']
-        self.imitation_method = imitation_method
-        self.loss_im = build_loss(loss_im)
-        self.loss_ld = build_loss(loss_ld)
-        self.loss_ld_vlr = build_loss(loss_ld_vlr)
-        self.loss_kd = build_loss(loss_kd)
-        self.iou_calculator = build_iou_calculator(dict(type='BboxOverlaps2D'))
-
-    def forward_train(self, x, out_teacher, teacher_x, img_metas, gt_bboxes,
-                      gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
-                      **kwargs):
-        """ld_gflv2.py:74-114."""
-        outs = self(x)
-        if gt_labels is None:
-            raise NotImplementedError('LDv2Head needs gt_labels')
-        if proposal_cfg is not None:
-            raise NotImplementedError('proposal_cfg')
-        return self.loss(*outs, gt_bboxes, gt_labels, out_teacher,
-                         self._loss_feats(x), teacher_x, img_metas,
-                         gt_bboxes_ignore=gt_bboxes_ignore)
+    def _split_teacher(self, soft_teacher):
+        _, soft_target, soft_label = soft_teacher  # ld_gflv2.py:326
+        return soft_label, soft_target, soft_label
 
     def loss(self, cls_scores, bbox_preds, cls_feat, gt_bboxes, gt_labels,
              soft_teacher, x, teacher_x, img_metas, gt_bboxes_ignore=None):
-        """ld_gflv2.py:286-380 -> dict of 8 lists of per-level scalars."""
-        self._check_loss_cfg()
-        lw_im = float(self.loss_im.loss_weight)
-        im_flags = _imitation_flags(self.imitation_method, lw_im)
-        if x[0].shape[1] != 256:
-            raise ValueError('LDv2Head hard-codes 256 feature channels '
-                             '(ld_gflv2.py:155-156)')
-        _, soft_target, soft_label = soft_teacher  # ld_gflv2.py:326
-        sizes = [tuple(int(v) for v in f.shape[-2:]) for f in cls_scores]
-        assert len(sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        hp = self._hp(lw_ld=self.loss_ld.loss_weight, T_ld=self.loss_ld.T,
-                      lw_ld_vlr=self.loss_ld_vlr.loss_weight,
-                      T_ld_vlr=self.loss_ld_vlr.T,
-                      lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T,
-                      lw_im=lw_im)
-        hp.flags |= im_flags
-        targets = self.get_targets_batched(sizes, img_metas, gt_bboxes,
-                                           gt_labels, hp, device)
-        t_kd = [t.detach() for t in soft_label]
-        teacher = (t_kd, [t.detach() for t in soft_target],
-                   [t.detach() for t in teacher_x], t_kd)
-        if self.imitation_method == 'gibox' and lw_im != 0.0:
-            # ld_gflv2.py:619-644: raw teacher cls_feat vs the student's
-            # probabilities, no sigmoids
-            targets = LB.gi_region(hp, targets,
-                                   [c.detach() for c in cls_scores],
-                                   [b.detach() for b in bbox_preds], t_kd,
-                                   teacher[1])
-        table, _ = LB.LDLossBlock.apply(hp, targets, teacher,
-                                        self._norm_reducer(),
-                                        self.unit_upstream, *cls_scores,
-                                        *bbox_preds, *x, *cls_feat)
-        self.last_targets = targets
-        return self._loss_dict(table)
+        """ld_gflv2.py:286-380."""
+        return self._ld_loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                             soft_teacher, x, teacher_x, img_metas,
+                             extra=cls_feat)

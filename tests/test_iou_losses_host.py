@@ -143,5 +143,6 @@ def test_heads_accept_the_four_box_losses_only():
         assert hp.giou_eps == np.float32(cfg.get('eps', 1e-6))
     head = _gfl_head(dict(type='SmoothL1Loss'))
     with pytest.raises(NotImplementedError,
-                       match='QualityFocalLoss \\+ GIoULoss'):
+                       match='QualityFocalLoss \\+ one of the box losses '
+                       'giou, iou, iou_linear, diou, ciou '):
         head._check_loss_cfg()
