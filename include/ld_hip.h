@@ -1027,7 +1027,7 @@ int ld_gconv_forward(const float* x, const float* wimage, float* y, int N, int C
                      const float* scale, const float* shift, int relu,
                      ld_stream_t stream);
 
-/* ---- deformable convolution v1, forward only (config 4's R101-DCN teacher) ---
+/* ---- deformable convolution v1 (config 4's R101-DCN teacher; trainable) -------
  * mmcv.ops.DeformConv2dPack under resnet.py:171-194 (deform_groups = 1,
  * groups = 1).  ld_deform_im2col samples x (N, Cin, Hin, Win) bilinearly at
  * p*stride - pad + k*dilation + offset and writes the column tensor
@@ -1041,6 +1041,37 @@ int ld_gconv_forward(const float* x, const float* wimage, float* y, int N, int C
 int ld_deform_im2col(const float* x, const float* offset, int N, int Cin, int Hin,
                      int Win, int KH, int KW, int stride, int pad, int dilation,
                      float* col, ld_stream_t stream);
+/* Backward of the sampling (fp32; d_col (N, Cin*KH*KW, Hout*Wout) is the data
+ * gradient of the 1x1 GEMM).  No float atomics: both results are bitwise
+ * reproducible from run to run.
+ * ld_deform_offset_grad: d_offset (N, 2*KH*KW, Hout*Wout), the analytic
+ * derivative of the forward's four-term bilinear expression with the forward's
+ * own floor (at an integer coordinate: the forward difference into the next
+ * cell); 0 outside (-1, H) x (-1, W); a corner outside the map contributes 0.
+ * Data gradient d_x (N, Cin, Hin*Win), in two calls that share one caller-owned
+ * workspace of ld_deform_col2im_workspace_bytes (0: invalid geometry, or no
+ * device to size the radix sort for):
+ *   ld_deform_col2im_index  keys every (n, tap, position, corner) entry by the
+ *     cell it touches, sorts the entries by cell (stable radix sort, hipcub, on
+ *     `stream`) and finds each cell's segment; needs `offset` only and serves
+ *     all Cin channels;
+ *   ld_deform_col2im_sum    zeroes d_x, then sums every cell's segment in a
+ *     fixed order (64-entry chunks of the sorted list, per-chunk partial sums
+ *     added in chunk order for cells that cross chunk boundaries).
+ * Nothing here allocates or synchronises; every launch goes to `stream`.
+ * LD_EINVAL: bad arguments, or more than 2^31 entries / cells; LD_ENOSPACE:
+ * workspace too small. */
+int ld_deform_offset_grad(const float* x, const float* offset, const float* d_col, int N,
+                          int Cin, int Hin, int Win, int KH, int KW, int stride, int pad,
+                          int dilation, float* d_offset, ld_stream_t stream);
+size_t ld_deform_col2im_workspace_bytes(int N, int Cin, int Hin, int Win, int KH, int KW,
+                                        int stride, int pad, int dilation);
+int ld_deform_col2im_index(const float* offset, int N, int Cin, int Hin, int Win, int KH,
+                           int KW, int stride, int pad, int dilation, void* workspace,
+                           size_t workspace_bytes, ld_stream_t stream);
+int ld_deform_col2im_sum(const float* d_col, int N, int Cin, int Hin, int Win, int KH,
+                         int KW, int stride, int pad, int dilation, void* workspace,
+                         size_t workspace_bytes, float* d_x, ld_stream_t stream);
 
 /* ---- device input pipeline ---------------------
  * Resize(keep_ratio) -> flip -> Normalize(to_rgb) -> Pad -> collate of the

@@ -170,8 +170,23 @@ class DeformConv2dPack(nn.Module):
     whose offsets come from its own ``conv_offset`` 3x3 conv (zero-initialised,
     with bias).  Parameter names / shapes as mmcv's: ``weight`` (Cout, Cin, k,
     k), no bias, ``conv_offset.weight`` (2*k*k*deform_groups, Cin, k, k),
-    ``conv_offset.bias``.  FORWARD ONLY: it exists for the frozen R101-DCN
-    teacher of config 4 (resnet.py:171-194); deform_groups = groups = 1."""
+    ``conv_offset.bias``.  deform_groups = 1, no dilation.
+
+    Frozen or under ``torch.no_grad()`` (the R101-DCN teacher of config 4,
+    resnet.py:171-194): offset conv -> ld_deform_im2col -> 1x1 GEMM with the
+    fused epilogue, three launches, no autograd (``groups`` > 1: the grouped
+    GEMM of the X-101 teacher).
+
+    Trainable (``forward3`` / ``forward3_fused`` / ``forward3_bn`` with
+    autograd on and anything upstream or inside that needs a gradient;
+    configs/gfl/gfl_r101_fpn_dconv_c3-c5_mstrain_2x_coco.py): the offset conv is
+    a layers.ConvFn, the sampling a layers.DeformIm2colFn (offset gradient +
+    sorted, atomic-free data gradient, csrc/dcn.hip) and the product with
+    ``weight.view(Cout, Cin*k*k, 1, 1)`` the differentiable 1x1 conv
+    (layers.conv2d, or layers.conv_bn_act with the following eval-mode BN), so
+    the GEMM's dgrad / wgrad and the BN backward are the existing kernels.
+    groups = 1 only, and the input must exist in fp32 (not C8-only).  The 4-D
+    convenience ``forward`` stays inference-only."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
                  padding=0, dilation=1, groups=1, deform_groups=1, bias=False,
@@ -201,6 +216,7 @@ class DeformConv2dPack(nn.Module):
             raise NotImplementedError('dilated DCN')
         self.reset_parameters()
         self._w2d = None
+        self._w2d_train = None
 
     def reset_parameters(self):
         # mmcv: uniform(-stdv, stdv), stdv = 1/sqrt(Cin*k*k); offsets start at 0
@@ -222,15 +238,81 @@ class DeformConv2dPack(nn.Module):
             self._w2d = v
         return v
 
+    def _weight_2d_train(self):
+        """The (Cout, Cin*k*k, 1, 1) weight of the differentiable 1x1 conv.  With
+        a gradient arena (train.GradArena gave the parameter ``_ld_grad``) a
+        persistent leaf view that carries the matching view of the arena slice
+        and forwards the ready callback to the parameter: the wgrad kernel then
+        accumulates straight into the arena, and the GEMM images cached on the
+        view are refreshed with every other trainable weight.  Without an
+        arena an autograd view, whose gradient flows back to ``weight.grad``."""
+        w = self.weight
+        if not w.requires_grad:
+            return self._weight_2d()
+        sink = getattr(w, '_ld_grad', None) if Y.DIRECT_GRADS[0] else None
+        if sink is None:
+            v = w.view(self.out_channels, -1, 1, 1)
+            v._ld_static = True  # a fresh tensor per call: nothing to refresh
+            return v
+        v = self._w2d_train
+        if v is None or v.data_ptr() != w.data_ptr() or \
+                v.device != w.device or \
+                v._ld_grad.data_ptr() != sink.data_ptr():
+            v = w.detach().view(self.out_channels, -1, 1, 1).requires_grad_(True)
+            v._ld_grad = sink.view(v.shape)
+            v._ld_pending = 0
+            self._w2d_train = v
+        v._ld_ready = lambda _v, w=w: w._ld_ready(w)
+        return v
+
+    def needs_grad(self, x3):
+        return torch.is_grad_enabled() and (
+            (isinstance(x3, torch.Tensor) and x3.requires_grad) or
+            any(p.requires_grad for p in self.parameters()))
+
+    def forward3_bn(self, x3, levels, bn=None, residual=None, relu=False):
+        """The trainable path: relu?(BN_eval(dcn(x)) + residual), or the plain
+        deformable conv with ``bn`` None.  Every piece is an autograd node."""
+        if self.groups != 1:
+            raise NotImplementedError(
+                'grouped DCN is forward-only here (the ResNeXt-DCN teacher): '
+                'call it under torch.no_grad()')
+        if self.deform_groups != 1 or self.dilation != (1, 1):
+            raise NotImplementedError(
+                'trainable DCN: deform_groups = 1 and no dilation are built')
+        if isinstance(x3, Y.C8Act) or Y._unwritten(x3):
+            raise NotImplementedError(
+                'trainable DCN needs its input in fp32; this one exists only as '
+                'a C8 image (C8Act / trunk_c8_scope)')
+        if len(levels) != 1:
+            raise NotImplementedError('DCN on level-concatenated tensors')
+        (h, w), = levels
+        k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        co = self.conv_offset
+        off3, out_levels = Y.conv2d(x3, co.weight, co.bias, s, p, levels)
+        col = Y.deform_im2col_fn(x3, off3, h, w, k, s, p)
+        w2 = self._weight_2d_train()
+        if bn is None:
+            if residual is not None or relu:
+                raise NotImplementedError('DCN epilogue without a norm layer')
+            return Y.conv2d(col, w2, None, 1, 0, out_levels)
+        return Y.conv_bn_act(col, w2, bn.weight, bn.bias, bn.running_mean,
+                             bn.running_var, bn.eps, 1, 0, out_levels, residual,
+                             relu)
+
     def forward3_fused(self, x3, levels, scale=None, shift=None, residual=None,
                        relu=False):
         """offset conv -> deformable im2col -> 1x1 GEMM with the fused epilogue
-        (BN affine / residual / ReLU)."""
-        if torch.is_grad_enabled() and (x3.requires_grad or
-                                        self.weight.requires_grad):
-            raise NotImplementedError(
-                'DeformConv2dPack is forward-only here (the frozen teacher of '
-                'config 4): call it under torch.no_grad()')
+        (BN affine / residual / ReLU); inference only when an epilogue is
+        given (the trainable conv + BN pair is ``forward3_bn``)."""
+        if self.needs_grad(x3):
+            if scale is not None or shift is not None or \
+                    residual is not None or relu:
+                raise NotImplementedError(
+                    'DeformConv2dPack.forward3_fused with a folded epilogue is '
+                    'inference-only: the trainable conv + BN pair is '
+                    'forward3_bn (resnet._conv_bn takes it)')
+            return self.forward3_bn(x3, levels)
         if len(levels) != 1:
             raise NotImplementedError('DCN on level-concatenated tensors')
         (h, w), = levels
@@ -259,6 +341,12 @@ class DeformConv2dPack(nn.Module):
         return self.forward3_fused(x3, levels)
 
     def forward(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or
+                                        self.weight.requires_grad):
+            raise NotImplementedError(
+                'DeformConv2dPack.forward (4-D) is inference-only: call it '
+                'under torch.no_grad(); the trainable entry points are '
+                'forward3 / forward3_bn on (N, C, H*W) tensors')
         n, c, h, w = x.shape
         y3, lv = self.forward3(x.reshape(n, c, h * w), ((h, w), ))
         return y3.view(n, self.out_channels, lv[0][0], lv[0][1])

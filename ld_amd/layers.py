@@ -2292,7 +2292,8 @@ def scale_levels(x3, scales, levels):
 
 def deform_im2col(x3, off3, h, w, k, stride, pad, dilation):
     """(N, Cin, H*W) + offsets (N, 2*k*k, Hout*Wout) -> column tensor
-    (N, Cin*k*k, Hout*Wout), forward only (ld_deform_im2col)."""
+    (N, Cin*k*k, Hout*Wout), no autograd (ld_deform_im2col; the differentiable
+    form is deform_im2col_fn)."""
     lib = L.get_lib()
     _dev_f32(x3, 'dcn input')
     _dev_f32(off3, 'dcn offset')
@@ -2306,6 +2307,91 @@ def deform_im2col(x3, off3, h, w, k, stride, pad, dilation):
                                  stride, pad, dilation, L.ptr(col),
                                  L.stream_ptr(x3.device)), 'ld_deform_im2col')
     return col
+
+
+def deform_col2im_index(off3, cin, h, w, k, stride, pad, dilation=1):
+    """The per-cell entry index of the DCN data gradient (ld_deform_col2im_index)
+    for these offsets: a caller-owned workspace tensor, valid for any d_col of
+    ``cin`` channels until the offsets change."""
+    lib = L.get_lib()
+    _dev_f32(off3, 'dcn offset')
+    N = off3.shape[0]
+    geo = (N, cin, h, w, k, k, stride, pad, dilation)
+    need = lib.ld_deform_col2im_workspace_bytes(*geo)
+    if not need:
+        raise L.LdError(f'deform_col2im: unsupported geometry {geo}')
+    ws = torch.empty(need, dtype=torch.uint8, device=off3.device)
+    L.check(lib.ld_deform_col2im_index(L.ptr(off3), *geo, L.ptr(ws), need,
+                                       L.stream_ptr(off3.device)),
+            'ld_deform_col2im_index')
+    return ws
+
+
+def deform_col2im_sum(dcol, ws, cin, h, w, k, stride, pad, dilation=1):
+    """d_x (N, Cin, H*W) of the sampling from d_col and the index ``ws``."""
+    lib = L.get_lib()
+    _dev_f32(dcol, 'dcn column gradient')
+    N = dcol.shape[0]
+    dx = torch.empty((N, cin, h * w), dtype=torch.float32, device=dcol.device)
+    L.check(lib.ld_deform_col2im_sum(L.ptr(dcol), N, cin, h, w, k, k, stride,
+                                     pad, dilation, L.ptr(ws), ws.numel(),
+                                     L.ptr(dx), L.stream_ptr(dcol.device)),
+            'ld_deform_col2im_sum')
+    return dx
+
+
+def deform_offset_grad(x3, off3, dcol, h, w, k, stride, pad, dilation=1):
+    """d_offset (N, 2*k*k, Hout*Wout) of the sampling (ld_deform_offset_grad)."""
+    lib = L.get_lib()
+    N, cin, _ = x3.shape
+    doff = torch.empty_like(off3)
+    L.check(lib.ld_deform_offset_grad(L.ptr(x3), L.ptr(off3), L.ptr(dcol), N,
+                                      cin, h, w, k, k, stride, pad, dilation,
+                                      L.ptr(doff), L.stream_ptr(x3.device)),
+            'ld_deform_offset_grad')
+    return doff
+
+
+class DeformIm2colFn(torch.autograd.Function):
+    """col = deformable im2col(x, offset) of DCNv1 (deform_groups = 1, fp32).
+    backward: the offset gradient in one launch, the data gradient as sort +
+    per-cell sum (csrc/dcn.hip; no float atomics, bitwise reproducible).  ``x3``
+    also feeds the layer's conv_offset: its gradient is handed over through the
+    fan protocol and summed in that conv's data-gradient epilogue."""
+
+    @staticmethod
+    def forward(ctx, x3, off3, h, w, k, stride, pad):
+        if isinstance(x3, C8Act) or _unwritten(x3):
+            raise NotImplementedError(
+                'deformable sampling needs the fp32 input; this one exists '
+                'only as a C8 image (C8Act / trunk_c8_scope)')
+        col = deform_im2col(x3, off3, h, w, k, stride, pad, 1)
+        ctx.save_for_backward(x3, off3)
+        ctx.geo = (h, w, k, stride, pad)
+        ctx.fan = fan_in(ctx, 0, x3)
+        return col
+
+    @staticmethod
+    def backward(ctx, dcol):
+        x3, off3 = ctx.saved_tensors
+        dcol = dcol.contiguous()
+        _dev_f32(dcol, 'dcn column gradient')
+        cin = x3.shape[1]
+        dx = doff = None
+        if ctx.needs_input_grad[1]:
+            doff = deform_offset_grad(x3, off3, dcol, *ctx.geo)
+        if ctx.needs_input_grad[0]:
+            ws = deform_col2im_index(off3, cin, *ctx.geo)
+            dx = deform_col2im_sum(dcol, ws, cin, *ctx.geo)
+            dx._ld_fresh = True
+        return fan_give(ctx.fan, dx), doff, None, None, None, None, None
+
+
+def deform_im2col_fn(x3, off3, h, w, k, stride, pad):
+    """Differentiable deform_im2col (dilation 1)."""
+    if torch.is_grad_enabled() and (x3.requires_grad or off3.requires_grad):
+        return DeformIm2colFn.apply(x3, off3, h, w, k, stride, pad)
+    return deform_im2col(x3, off3, h, w, k, stride, pad, 1)
 
 
 def gconv_weight_image(w, groups):

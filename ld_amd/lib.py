@@ -286,6 +286,12 @@ SIGNATURES = {
                                       C.POINTER(C.c_float), _i32, _vp, _vp]),
     'ld_deform_im2col': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _i32, _i32, _vp, _vp]),
+    'ld_deform_offset_grad': (C.c_int, [_vp, _vp, _vp] + [_i32] * 9 +
+                              [_vp, _vp]),
+    'ld_deform_col2im_workspace_bytes': (_sz, [_i32] * 9),
+    'ld_deform_col2im_index': (C.c_int, [_vp] + [_i32] * 9 + [_vp, _sz, _vp]),
+    'ld_deform_col2im_sum': (C.c_int, [_vp] + [_i32] * 9 +
+                             [_vp, _sz, _vp, _vp]),
     'ld_quality_forward': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp]),
     'ld_quality_backward_workspace_bytes': (_sz, [_i32, _i32]),

@@ -72,6 +72,17 @@ def gfl_detector(depth=101):
                 test_cfg=copy.deepcopy(_TEST_CFG))
 
 
+def gfl_dcn_detector(depth=101):
+    """configs/gfl/gfl_r101_fpn_dconv_c3-c5_mstrain_2x_coco.py:6-12: the GFL
+    teacher with DCNv1 in the conv2 of every c3-c5 Bottleneck (30 layers at
+    depth 101), trainable -- the teacher config 4 distils from."""
+    cfg = gfl_detector(depth)
+    cfg['backbone'].update(
+        dcn=dict(type='DCN', deform_groups=1, fallback_on_stride=False),
+        stage_with_dcn=(False, True, True, True))
+    return cfg
+
+
 def ld_detector(student_depth=50, teacher_depth=101,
                 imitation_method='finegrained', loss_im_weight=2.0,
                 with_vlr_kd=True):

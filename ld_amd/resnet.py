@@ -32,7 +32,10 @@ def _conv_bn(x3, levels, conv, bn, residual=None, relu=True):
     if bn.training:
         raise NotImplementedError('BatchNorm in training mode (use '
                                   'norm_eval=True; resnet.py:639-648)')
-    if hasattr(conv, 'forward3_fused'):  # DCN: forward-only, fused epilogue
+    if hasattr(conv, 'forward3_bn') and (need_grad or conv.needs_grad(x3)):
+        # trainable DCN: offset conv, sampling and conv + BN as autograd nodes
+        return conv.forward3_bn(x3, levels, bn, residual, relu)
+    if hasattr(conv, 'forward3_fused'):  # forward-only: fused epilogue
         scale, shift, _ = Y.bn_prepare(bn.weight, bn.bias, bn.running_mean,
                                        bn.running_var, bn.eps)
         return conv.forward3_fused(x3, levels, scale, shift, residual, relu)
