@@ -1008,7 +1008,7 @@ int ld_probe_copy(const float* src, float* dst, int64_t n, int width, int nt,
 int ld_probe_planes(const float* s, const float* t, float* g, int64_t rows, int nt,
                     int side_fast, ld_stream_t stream);
 
-/* ---- grouped convolution, forward only (config 5's X-101 teacher) --------------
+/* ---- grouped convolution, forward (config 5's X-101 teacher) ---------------------
  * The 3x3 conv2 of ResNeXt's Bottleneck (mmdet/models/backbones/resnext.py:49-61,
  * nn.Conv2d(width, width, 3, stride, padding=1, groups=32, bias=False)) and,
  * with K = 1, the grouped GEMM behind a grouped deformable conv (:62-74 over
@@ -1026,6 +1026,41 @@ int ld_gconv_forward(const float* x, const float* wimage, float* y, int N, int C
                      int Cout, int groups, int K, int stride, int pad, int Hin, int Win,
                      const float* scale, const float* shift, int relu,
                      ld_stream_t stream);
+
+/* ---- grouped convolution, backward (the trainable ResNeXt teachers) -------------
+ * fp32, single level, Cout / groups in {4, 8, 16, 32}, K in {1, 3}, stride in
+ * {1, 2} (LD_EUNSUPPORTED otherwise); Cin / groups is free (9 * Cout / groups
+ * for the K = 1 GEMM behind a grouped DCN).  No float atomics, no host
+ * synchronisation, no allocation: two runs are bit-identical and every launch
+ * can be captured.
+ *
+ * ld_gconv_dgrad: dx (N, Cin, Hin*Win) = the data gradient of ld_gconv_forward
+ * for dy (N, Cout, Hout*Wout), as a gather (one thread per input position and
+ * chunk of <= 32 of the group's input channels); addend non-NULL: dx = addend
+ * + gradient (same shape as dx; may alias it).  wimage_bwd =
+ * ld_gconv_weight_transform_bwd of the PyTorch weight:
+ * [group][chunk][co][tap][c], ld_gconv_weight_image_bwd_floats floats (zero
+ * padded to whole chunks).
+ *
+ * ld_gconv_wgrad: dw (Cout, Cin/groups, K, K) = (accumulate ? dw : 0) + the
+ * weight gradient.  The N * Hout*Wout positions are cut into
+ * ld_gconv_wgrad_slabs slabs (fixed size, per image); the first launch writes
+ * one partial per (slab, element) into ``workspace`` (at least
+ * ld_gconv_wgrad_workspace_floats floats, caller-owned), the second sums the
+ * slabs in slab order. */
+size_t ld_gconv_weight_image_bwd_floats(int Cout, int Cin, int groups, int K);
+int ld_gconv_weight_transform_bwd(const float* w, int Cout, int Cin, int groups, int K,
+                                  float* image, ld_stream_t stream);
+int ld_gconv_dgrad(const float* dy, const float* wimage_bwd, const float* addend,
+                   float* dx, int N, int Cin, int Cout, int groups, int K, int stride,
+                   int pad, int Hin, int Win, ld_stream_t stream);
+int ld_gconv_wgrad_slabs(int N, int K, int stride, int pad, int Hin, int Win);
+size_t ld_gconv_wgrad_workspace_floats(int N, int Cin, int Cout, int groups, int K,
+                                       int stride, int pad, int Hin, int Win);
+int ld_gconv_wgrad(const float* x, const float* dy, float* dw, int accumulate,
+                   float* workspace, size_t workspace_floats, int N, int Cin, int Cout,
+                   int groups, int K, int stride, int pad, int Hin, int Win,
+                   ld_stream_t stream);
 
 /* ---- deformable convolution v1 (config 4's R101-DCN teacher; trainable) -------
  * mmcv.ops.DeformConv2dPack under resnet.py:171-194 (deform_groups = 1,

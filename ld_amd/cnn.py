@@ -109,11 +109,18 @@ class Conv2d(nn.Module):
 
 class GroupedConv2d(nn.Module):
     """nn.Conv2d(..., groups=G > 1)'s parameters and keys: ``weight`` (Cout,
-    Cin / G, k, k).  FORWARD ONLY -- it exists for the frozen ResNeXt teacher of
-    BASELINE config 5 (resnext.py:49-61: the 3x3 conv2 of every Bottleneck,
-    groups = 32); runs ld_gconv_forward with the following eval-mode BN and ReLU
-    folded into its epilogue (``forward3_fused``, the hook resnet._conv_bn
-    takes for forward-only convs)."""
+    Cin / G, k, k) -- the 3x3 conv2 of every ResNeXt Bottleneck
+    (resnext.py:49-61, groups = 32 / 64).
+
+    Frozen or under ``torch.no_grad()`` (the X-101 teacher of BASELINE config
+    5): ld_gconv_forward with the following eval-mode BN and ReLU folded into
+    its epilogue (``forward3_fused``, the hook resnet._conv_bn takes for
+    forward-only convs).
+
+    Trainable (``forward3`` / ``forward3_bn`` with autograd on and an input or
+    weight that needs a gradient; configs/gfl/gfl_x101_*): layers.gconv2d
+    (GroupedConvFn: ld_gconv_dgrad / ld_gconv_wgrad) followed by the eval-mode
+    BN as its own autograd node.  fp32 only, and the input must exist in fp32."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
                  padding=0, dilation=1, groups=1, bias=False):
@@ -139,19 +146,38 @@ class GroupedConv2d(nn.Module):
         self.bias = None
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
 
+    def needs_grad(self, x3):
+        return torch.is_grad_enabled() and (
+            (isinstance(x3, torch.Tensor) and x3.requires_grad) or
+            self.weight.requires_grad)
+
+    def forward3_bn(self, x3, levels, bn=None, residual=None, relu=False):
+        """The trainable path: relu?(BN_eval(gconv(x)) + residual), or the plain
+        grouped conv with ``bn`` None."""
+        y3, out_levels = Y.gconv2d(x3, self.weight, self.groups,
+                                   self.stride[0], self.padding[0], levels)
+        if bn is None:
+            if residual is not None or relu:
+                raise NotImplementedError(
+                    'grouped conv epilogue without a norm layer')
+            return y3, out_levels
+        return bn.forward3(y3, residual, relu), out_levels
+
     def forward3_fused(self, x3, levels, scale=None, shift=None, residual=None,
                        relu=False):
-        if torch.is_grad_enabled() and (x3.requires_grad or
-                                        self.weight.requires_grad):
+        if self.needs_grad(x3):
             raise NotImplementedError(
-                'grouped convs are forward-only here (the frozen ResNeXt '
-                'teacher of config 5): call them under torch.no_grad()')
+                'GroupedConv2d.forward3_fused (the folded-epilogue hook) is '
+                'inference-only: the trainable entry points are forward3 / '
+                'forward3_bn (resnet._conv_bn takes the latter)')
         if residual is not None:
             raise NotImplementedError('grouped conv with a fused residual')
         return Y.gconv_forward(x3, self.weight, self.groups, self.stride[0],
                                self.padding[0], levels, scale, shift, relu)
 
     def forward3(self, x3, levels):
+        if self.needs_grad(x3):
+            return self.forward3_bn(x3, levels)
         return self.forward3_fused(x3, levels)
 
     def forward(self, x):
@@ -185,7 +211,10 @@ class DeformConv2dPack(nn.Module):
     ``weight.view(Cout, Cin*k*k, 1, 1)`` the differentiable 1x1 conv
     (layers.conv2d, or layers.conv_bn_act with the following eval-mode BN), so
     the GEMM's dgrad / wgrad and the BN backward are the existing kernels.
-    groups = 1 only, and the input must exist in fp32 (not C8-only).  The 4-D
+    ``groups`` > 1 (configs/imv2/gflv2_x101_fpn_2x_coco.py): the product is
+    layers.gconv2d over the Cin*k*k column channels followed by the BN node,
+    fp32 only and only as that conv + BN pair.  The input must exist in fp32
+    (not C8-only).  The 4-D
     convenience ``forward`` stays inference-only."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
@@ -273,10 +302,13 @@ class DeformConv2dPack(nn.Module):
     def forward3_bn(self, x3, levels, bn=None, residual=None, relu=False):
         """The trainable path: relu?(BN_eval(dcn(x)) + residual), or the plain
         deformable conv with ``bn`` None.  Every piece is an autograd node."""
-        if self.groups != 1:
+        if self.groups != 1 and bn is None:
             raise NotImplementedError(
-                'grouped DCN is forward-only here (the ResNeXt-DCN teacher): '
-                'call it under torch.no_grad()')
+                'grouped DCN trains as the conv + BN pair of a ResNeXt '
+                'Bottleneck only (forward3_bn with its norm layer)')
+        if self.groups != 1 and Y.get_precision() == 'bf16':
+            raise NotImplementedError(
+                'trainable grouped DCN is fp32 only (bf16 mode is not built)')
         if self.deform_groups != 1 or self.dilation != (1, 1):
             raise NotImplementedError(
                 'trainable DCN: deform_groups = 1 and no dilation are built')
@@ -292,6 +324,12 @@ class DeformConv2dPack(nn.Module):
         off3, out_levels = Y.conv2d(x3, co.weight, co.bias, s, p, levels)
         col = Y.deform_im2col_fn(x3, off3, h, w, k, s, p)
         w2 = self._weight_2d_train()
+        if self.groups != 1:
+            # grouped DCN (resnext.py:62-74): rows [g * cg * k * k, (g + 1) * cg
+            # * k * k) of the column tensor feed group g -- the differentiable
+            # grouped 1x1 conv over Cin * k * k channels, then the BN node
+            y3, _ = Y.gconv2d(col, w2, self.groups, 1, 0, out_levels)
+            return bn.forward3(y3, residual, relu), out_levels
         if bn is None:
             if residual is not None or relu:
                 raise NotImplementedError('DCN epilogue without a norm layer')

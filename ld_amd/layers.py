@@ -197,6 +197,7 @@ import weakref  # noqa: E402
 
 _WT_REG, _BN_REG = {}, {}
 _WT_REG_BF16 = {}
+_GW_REG = {}  # trainable grouped conv weights (gconv_weight_images)
 _TABLES = {}
 
 # Matrix-operand precision of the convolutions: 'fp32' (v_mfma_f32_32x32x2_f32,
@@ -537,6 +538,24 @@ def refresh_params(device):
                     cache['stamp'] = stamp
                 if has_bwd and cache['bwd'] is not None:
                     cache['bwd_stamp'] = stamp
+    for key_w, ref in list(_GW_REG.items()):
+        # grouped conv weights: a handful per net (33 in X-101), one transform
+        # launch per image
+        w = ref()
+        if w is None:
+            del _GW_REG[key_w]
+            continue
+        cache = getattr(w, '_ld_gimages', None) if w is not None else None
+        if cache is None or w.device != device or \
+                cache['ident'] != (w.data_ptr(), cache['ident'][1]):
+            continue
+        stamp = (w._version, gen) + cache['ident']
+        if cache['fwd'] is not None:
+            _gconv_xform(lib, w, cache['ident'][1], cache['fwd'], False)
+            cache['stamp'] = stamp
+        if cache['bwd'] is not None:
+            _gconv_xform(lib, w, cache['ident'][1], cache['bwd'], True)
+            cache['bwd_stamp'] = stamp
     if tabs['b'] is not None:
         jobs, bmap, nb = tabs['b']
         L.check(lib.ld_bn_prepare_batch(L.ptr(jobs), L.ptr(bmap), nb, st),
@@ -1191,6 +1210,60 @@ def _conv_dgrad(lib, w, dy, d, meta, addend):
     return dx
 
 
+def _wgrad_side_for(sink, device):
+    """The side stream a weight gradient with destination ``sink`` goes to, or
+    None for the main stream (shared by the dense and the grouped convs)."""
+    # Round 3: eager bf16 steps were HOST-bound (~14 ms of enqueue per 15.5 ms
+    # step) and the three extra stream calls per weight gradient cost more
+    # host time than the overlap returned (15.56 -> 17.31 ms), so bf16 used
+    # the side stream only inside hipGraph captures.  Round 5: the step is
+    # GPU-bound (launch lists, fan protocol, deferred finalisation) and its
+    # main queue is the critical path (65 % busy against 22 % on the side
+    # queue, profiles/r05_queue_busy_bf16.txt): with the weight gradients
+    # behind the teacher on the side stream 13.46 -> 12.42 ms per step
+    # (profiles/r05_bf16_wgrad_side_stream.txt).  LD_WGRAD_STREAM_BF16=0
+    # restores the old placement.  fp32: 36.88 -> 35.98 ms eager
+    # (profiles/r03_wgrad_side_stream.txt).
+    if sink is not None and _WGRAD_STREAM[0] and \
+            device.type == 'cuda' and \
+            KernelProfile.active is None and (
+                _PRECISION[0] != 'bf16' or _WGRAD_FORCE[0] or
+                _WGRAD_BF16_EAGER[0] or
+                torch.cuda.is_current_stream_capturing()):
+        return _wgrad_side(device)
+    return None
+
+
+def _wgrad_dispatch(launch, side, ws, need, defer, operands, device):
+    """Run ``launch(workspace, stream_ptr)`` of a weight gradient on the main
+    stream (``side`` None) or forked onto the side stream."""
+    lib = L.get_lib()
+    st = L.stream_ptr(device)
+    if side is None:
+        launch(ws, st)
+        return
+    if defer and not torch.cuda.is_current_stream_capturing():
+        # no workspace, no host-side stream switch: fork the side stream
+        # off the main one with ONE C call and hand the launch its raw
+        # pointer (~65 weight gradients per step; the torch calls below
+        # are ~25 us of host time each, this path ~6)
+        sp = C.c_void_p(side.cuda_stream)
+        L.check(lib.ld_stream_fork(st, sp), 'ld_stream_fork')
+        launch(ws, sp)
+    else:
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            ws2 = ws if defer else workspace(device, need,
+                                             'wgrad')  # per stream
+            launch(ws2, L.stream_ptr(device))
+    # the caching allocator must not hand these blocks to later
+    # main-stream allocations while the side stream still reads them
+    for t in operands:
+        if isinstance(t, torch.Tensor):
+            t.record_stream(side)
+    _WGRAD_PENDING[0] = True
+
+
 def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
     """The weight gradient of _conv_backward; None: into the gradient arena."""
     dy8 = isinstance(dy, C8Act)
@@ -1205,25 +1278,7 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
     family = 2 if c8w else 1 if bf16 else 0
     fam = _FAMILIES[family]
     wgrad = getattr(lib, fam.wgrad)
-    side = None
-    # Round 3: eager bf16 steps were HOST-bound (~14 ms of enqueue per 15.5 ms
-    # step) and the three extra stream calls per weight gradient cost more
-    # host time than the overlap returned (15.56 -> 17.31 ms), so bf16 used
-    # the side stream only inside hipGraph captures.  Round 5: the step is
-    # GPU-bound (launch lists, fan protocol, deferred finalisation) and its
-    # main queue is the critical path (65 % busy against 22 % on the side
-    # queue, profiles/r05_queue_busy_bf16.txt): with the weight gradients
-    # behind the teacher on the side stream 13.46 -> 12.42 ms per step
-    # (profiles/r05_bf16_wgrad_side_stream.txt).  LD_WGRAD_STREAM_BF16=0
-    # restores the old placement.  fp32: 36.88 -> 35.98 ms eager
-    # (profiles/r03_wgrad_side_stream.txt).
-    if sink is not None and _WGRAD_STREAM[0] and \
-            dy.device.type == 'cuda' and \
-            KernelProfile.active is None and (
-                _PRECISION[0] != 'bf16' or _WGRAD_FORCE[0] or
-                _WGRAD_BF16_EAGER[0] or
-                torch.cuda.is_current_stream_capturing()):
-        side = _wgrad_side(dy.device)
+    side = _wgrad_side_for(sink, dy.device)
     if family == 0:
         # explicit tuning writes its result with accumulate = 0: into a
         # scratch dW, never into the gradient arena
@@ -1265,32 +1320,7 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
         # nothing); the wgrad itself may go to the side stream
         xw, dyw = ((x3.buf if x8 is not None else to_c8(x3)),
                    dy.buf if dy8 else to_c8(dy)) if c8w else (x3, dy)
-        if side is None:
-            _launch(ws, st)
-        elif defer and not torch.cuda.is_current_stream_capturing():
-            # no workspace, no host-side stream switch: fork the side stream
-            # off the main one with ONE C call and hand the launch its raw
-            # pointer (~65 weight gradients per step; the torch calls below
-            # are ~25 us of host time each, this path ~6)
-            sp = C.c_void_p(side.cuda_stream)
-            L.check(lib.ld_stream_fork(st, sp), 'ld_stream_fork')
-            _launch(ws, sp)
-            for t in (xw, dyw):
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(side)
-            _WGRAD_PENDING[0] = True
-        else:
-            side.wait_stream(torch.cuda.current_stream(dy.device))
-            with torch.cuda.stream(side):
-                ws2 = ws if defer else workspace(dy.device, need,
-                                                 'wgrad')  # per stream
-                _launch(ws2, L.stream_ptr(dy.device))
-            # the caching allocator must not hand these blocks to later
-            # main-stream allocations while the side stream still reads them
-            for t in (xw, dyw):
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(side)
-            _WGRAD_PENDING[0] = True
+        _wgrad_dispatch(_launch, side, ws, need, defer, (xw, dyw), dy.device)
     if sink is not None:
         _emit(pw)
         return None
@@ -2394,27 +2424,56 @@ def deform_im2col_fn(x3, off3, h, w, k, stride, pad):
     return deform_im2col(x3, off3, h, w, k, stride, pad, 1)
 
 
-def gconv_weight_image(w, groups):
-    """[group][ci][tap][co] image of a grouped conv weight (Cout, Cin/groups, K,
-    K), cached on the tensor (the X-101 teacher is frozen)."""
+def _gconv_xform(lib, w, groups, img, backward):
+    cout, cin_g, k, _ = w.shape
+    fn, what = (lib.ld_gconv_weight_transform_bwd,
+                'ld_gconv_weight_transform_bwd') if backward else \
+        (lib.ld_gconv_weight_transform, 'ld_gconv_weight_transform')
+    L.check(fn(L.ptr(w.detach().contiguous()), cout, cin_g * groups, groups, k,
+               L.ptr(img), L.stream_ptr(w.device)), what)
+
+
+def gconv_weight_images(w, groups, need_bwd=False, need_fwd=True):
+    """(forward [group][ci][tap][co], data-gradient [group][chunk][co][tap][c])
+    images of a grouped conv weight (Cout, Cin/groups, K, K), cached on the
+    tensor and rebuilt when it changed.  A trainable weight follows the
+    parameter-generation protocol of ``weight_images``: the arena optimizer does
+    not bump ``_version``, so its stamp carries ``_PARAM_GEN`` and the weight is
+    registered for ``refresh_params``."""
     lib = L.get_lib()
     _dev_f32(w, 'grouped conv weight')
-    stamp = (w._version, w.data_ptr(), groups)
-    hit = getattr(w, '_ld_gimg', None)
-    if hit is not None and hit[0] == stamp:
-        return hit[1]
+    dynamic = w.requires_grad and not getattr(w, '_ld_static', False)
+    ident = (w.data_ptr(), groups)
+    stamp = (w._version, _PARAM_GEN[0] if dynamic else -1) + ident
+    cache = getattr(w, '_ld_gimages', None)
+    if cache is None or cache['ident'] != ident:
+        cache = dict(ident=ident, stamp=None, fwd=None, bwd=None,
+                     bwd_stamp=None)
+        try:
+            w._ld_gimages = cache
+        except AttributeError:
+            pass
     cout, cin_g, k, _ = w.shape
-    img = torch.empty(lib.ld_gconv_weight_image_floats(cout, cin_g * groups,
-                                                       groups, k),
-                      dtype=torch.float32, device=w.device)
-    L.check(lib.ld_gconv_weight_transform(
-        L.ptr(w.detach().contiguous()), cout, cin_g * groups, groups, k,
-        L.ptr(img), L.stream_ptr(w.device)), 'ld_gconv_weight_transform')
-    try:
-        w._ld_gimg = (stamp, img)
-    except AttributeError:
-        pass
-    return img
+    for need, key, skey, sizer, backward in (
+            (need_fwd, 'fwd', 'stamp', lib.ld_gconv_weight_image_floats, False),
+            (need_bwd, 'bwd', 'bwd_stamp',
+             lib.ld_gconv_weight_image_bwd_floats, True)):
+        if not need or cache[skey] == stamp:
+            continue
+        if cache[key] is None:
+            cache[key] = torch.empty(sizer(cout, cin_g * groups, groups, k),
+                                     dtype=torch.float32, device=w.device)
+        _gconv_xform(lib, w, groups, cache[key], backward)
+        cache[skey] = stamp
+        ref = _GW_REG.get(id(w))
+        if dynamic and (ref is None or ref() is not w):
+            _GW_REG[id(w)] = weakref.ref(w)  # also an id reused after a free
+    return cache['fwd'], cache['bwd']
+
+
+def gconv_weight_image(w, groups):
+    """The forward image of ``gconv_weight_images``."""
+    return gconv_weight_images(w, groups)[0]
 
 
 def gconv_forward(x3, w, groups, stride, pad, levels, scale=None, shift=None,
@@ -2438,6 +2497,122 @@ def gconv_forward(x3, w, groups, stride, pad, levels, scale=None, shift=None,
         stride, pad, h, wd, L.ptr(scale), L.ptr(shift), 1 if relu else 0,
         L.stream_ptr(x3.device)), 'ld_gconv_forward')
     return y, ((ho, wo), )
+
+
+def _gconv_geo(x_shape, w, groups, stride, pad, levels):
+    if len(levels) != 1:
+        raise NotImplementedError('grouped conv on level-concatenated tensors')
+    (h, wd), = levels
+    N, cin, P = x_shape
+    cout, cin_g, k, _ = w.shape
+    if P != h * wd or cin != cin_g * groups:
+        raise L.LdError('grouped conv: shape mismatch')
+    return N, cin, cout, groups, k, stride, pad, h, wd
+
+
+def gconv_dgrad(dy, w, groups, stride, pad, levels, x_shape, addend=None):
+    """dx (N, Cin, H*W) of a grouped conv (ld_gconv_dgrad: a gather, bitwise
+    reproducible); ``addend`` is summed in (the fan protocol)."""
+    lib = L.get_lib()
+    _dev_f32(dy, 'grouped conv output gradient')
+    geo = _gconv_geo(x_shape, w, groups, stride, pad, levels)
+    N, cin, cout, _, k, _, _, h, wd = geo
+    ho, wo = out_size(h, k, stride, pad), out_size(wd, k, stride, pad)
+    if dy.shape != (N, cout, ho * wo) or not dy.is_contiguous():
+        raise L.LdError('gconv_dgrad: dy shape mismatch')
+    _, img = gconv_weight_images(w, groups, need_bwd=True, need_fwd=False)
+    dx = torch.empty((N, cin, h * wd), dtype=torch.float32, device=dy.device)
+    if addend is not None and (addend.numel() != dx.numel() or
+                               not addend.is_contiguous()):
+        raise L.LdError('gconv_dgrad: addend shape mismatch')
+    L.check(lib.ld_gconv_dgrad(L.ptr(dy), L.ptr(img), L.ptr(addend), L.ptr(dx),
+                               *geo, L.stream_ptr(dy.device)), 'ld_gconv_dgrad')
+    dx._ld_fresh = True
+    return dx
+
+
+def gconv_wgrad(x3, dy, w, groups, stride, pad, levels, pw=None):
+    """dw of a grouped conv (ld_gconv_wgrad: slab partials + a fixed-order sum,
+    no atomics).  With a gradient arena slice on ``pw`` it is accumulated
+    there -- on the weight-gradient side stream under _conv_wgrad's rule -- and
+    None is returned."""
+    lib = L.get_lib()
+    _dev_f32(x3, 'grouped conv input')
+    _dev_f32(dy, 'grouped conv output gradient')
+    geo = _gconv_geo(x3.shape, w, groups, stride, pad, levels)
+    if not x3.is_contiguous() or not dy.is_contiguous():
+        raise L.LdError('gconv_wgrad: operands must be contiguous')
+    need = lib.ld_gconv_wgrad_workspace_floats(*geo)
+    if not need:
+        raise L.LdError(f'gconv_wgrad: bad geometry {geo}')
+    sink = _sink(pw)
+    dw = sink if sink is not None else torch.empty_like(w)
+    side = _wgrad_side_for(sink, dy.device)
+    ws = workspace(dy.device, need * 4, 'gwgrad') if side is None else None
+
+    def _launch(ws_, stream_ptr):
+        L.check(lib.ld_gconv_wgrad(
+            L.ptr(x3), L.ptr(dy), L.ptr(dw), 0 if sink is None else 1,
+            L.ptr(ws_), ws_.numel() // 4, *geo, stream_ptr), 'ld_gconv_wgrad')
+
+    _wgrad_dispatch(_launch, side, ws, need * 4, False, (x3, dy), dy.device)
+    if sink is not None:
+        _emit(pw)
+        return None
+    return dw
+
+
+class GroupedConvFn(torch.autograd.Function):
+    """y = grouped conv(x, w), fp32, single level (csrc/gconv.hip): ConvFn's
+    protocol (fan-in data gradient, weight gradient straight into the arena)."""
+
+    @staticmethod
+    def forward(ctx, x3, w, groups, stride, pad, levels):
+        if isinstance(x3, C8Act) or _unwritten(x3):
+            raise NotImplementedError(
+                'a trainable grouped conv needs its input in fp32; this one '
+                'exists only as a C8 image (C8Act / trunk_c8_scope)')
+        if _PRECISION[0] == 'bf16':
+            raise NotImplementedError(
+                'trainable grouped convs are fp32 only (bf16 mode is not built)')
+        x3 = x3.contiguous()
+        y3, _ = gconv_forward(x3, w, groups, stride, pad, levels)
+        ctx.save_for_backward(x3, w)
+        ctx.meta = (groups, stride, pad, levels)
+        ctx.pw = w
+        ctx.fan = fan_in(ctx, 0, x3)
+        _note_use(w)
+        return y3
+
+    @staticmethod
+    def backward(ctx, dy):
+        x3, _ = ctx.saved_tensors
+        w = ctx.pw  # the object that carries the cached images / arena slice
+        dy = dy.contiguous()
+        dx = dw = None
+        addend = fan_take(ctx.fan)
+        if ctx.needs_input_grad[0]:
+            dx = gconv_dgrad(dy, w, *ctx.meta, x3.shape, addend=addend)
+        elif addend is not None:
+            raise L.LdError('grouped conv: a fan deposit without a data gradient')
+        if ctx.needs_input_grad[1]:
+            dw = gconv_wgrad(x3, dy, w, *ctx.meta, pw=ctx.pw)
+        return fan_give(ctx.fan, dx), dw, None, None, None, None
+
+
+def gconv2d(x3, w, groups, stride, pad, levels):
+    """Differentiable grouped conv on an (N, C, P) tensor.  Returns (y3,
+    out_levels); plain ``gconv_forward`` when nothing needs a gradient."""
+    if torch.is_grad_enabled() and (
+            (isinstance(x3, torch.Tensor) and x3.requires_grad) or
+            w.requires_grad):
+        (h, wd), = levels
+        k = w.shape[2]
+        out_levels = ((out_size(h, k, stride, pad),
+                       out_size(wd, k, stride, pad)), )
+        return GroupedConvFn.apply(x3, w, groups, stride, pad, levels), \
+            out_levels
+    return gconv_forward(x3, w, groups, stride, pad, levels)
 
 
 class QualityFn(torch.autograd.Function):

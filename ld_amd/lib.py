@@ -313,6 +313,17 @@ SIGNATURES = {
     'ld_gconv_forward': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _i32, _i32, _vp, _vp, _i32,
                                    _vp]),
+    'ld_gconv_weight_image_bwd_floats': (_sz, [_i32, _i32, _i32, _i32]),
+    'ld_gconv_weight_transform_bwd': (C.c_int, [_vp, _i32, _i32, _i32, _i32,
+                                                _vp, _vp]),
+    'ld_gconv_dgrad': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                 _i32, _i32, _i32, _i32, _i32, _vp]),
+    'ld_gconv_wgrad_slabs': (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    'ld_gconv_wgrad_workspace_floats': (_sz, [_i32, _i32, _i32, _i32, _i32,
+                                              _i32, _i32, _i32, _i32]),
+    'ld_gconv_wgrad': (C.c_int, [_vp, _vp, _vp, _i32, _vp, _sz, _i32, _i32,
+                                 _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                 _vp]),
     'ld_kl_integral_dense': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp,
                                        _vp, _vp, _vp]),
     'ld_kd_kl_rows': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _f32, _vp,

@@ -83,6 +83,26 @@ def gfl_dcn_detector(depth=101):
     return cfg
 
 
+def gfl_x101_detector():
+    """configs/gfl/gfl_x101_32x4d_fpn_mstrain_2x_coco.py: GFL on a trainable
+    ResNeXt-101 32x4d (33 grouped 3x3 convs, 30 of them past the frozen
+    stage 1).  Key for key that file's resolved ``model`` except ``pretrained``:
+    the file names 'open-mmlab://resnext101_32x4d', every zoo entry is None
+    (weights come from a state dict; no checkpoint hub here)."""
+    cfg = gfl_detector(101)
+    cfg['backbone'] = _x101_backbone(101)
+    return cfg
+
+
+def gfl_x101_dcn_detector():
+    """configs/gfl/gfl_x101_32x4d_fpn_dconv_c4-c5_mstrain_2x_coco.py: the same
+    with grouped DCNv1 as the conv2 of every c4-c5 Bottleneck (``pretrained``
+    None as in gfl_x101_detector)."""
+    cfg = gfl_detector(101)
+    cfg['backbone'] = _x101_backbone(101, dcn=True)
+    return cfg
+
+
 def ld_detector(student_depth=50, teacher_depth=101,
                 imitation_method='finegrained', loss_im_weight=2.0,
                 with_vlr_kd=True):
@@ -131,6 +151,16 @@ def gflv2_detector(depth=101):
                 neck=_neck(depth), bbox_head=head,
                 train_cfg=copy.deepcopy(_TRAIN_CFG),
                 test_cfg=copy.deepcopy(_TEST_CFG))
+
+
+def gflv2_x101_detector(dcn=True):
+    """configs/imv2/gflv2_x101_fpn_2x_coco.py: the GFLv2 ResNeXt-101 32x4d
+    teacher of BASELINE config 5, with that file's grouped DCN in c4-c5
+    (``dcn=False``: the plain ResNeXt composition ldv2_x101_detector pins).
+    ``pretrained`` is None where the file names the open-mmlab checkpoint."""
+    cfg = gflv2_detector(101)
+    cfg['backbone'] = _x101_backbone(101, dcn)
+    return cfg
 
 
 def ldv2_x101_detector(student_depth=50, imitation_method='finegrained',

@@ -454,10 +454,12 @@ class ResNet(nn.Module):
 @BACKBONES.register_module()
 class ResNeXt(ResNet):
     """ResNeXt backbone (mmdet/models/backbones/resnext.py:88-153): ResNet with
-    grouped Bottlenecks.  Here it is the frozen X-101 (32x4d) TEACHER of
-    BASELINE config 5 -- its grouped convs are forward-only
-    (ld_amd/csrc/gconv.hip), so it must run under ``torch.no_grad()`` with
-    ``norm_eval=True``."""
+    grouped Bottlenecks (ld_amd/csrc/gconv.hip): frozen under
+    ``torch.no_grad()`` it is the X-101 (32x4d) teacher of BASELINE config 5
+    with BN and ReLU folded into the grouped conv's epilogue; trainable
+    (configs/gfl/gfl_x101_*, configs/imv2/gflv2_x101_*) its grouped convs and
+    grouped DCNs take the fp32 data / weight gradient kernels.
+    ``norm_eval=True`` in both."""
     arch_settings = {
         50: (ResNeXtBottleneck, (3, 4, 6, 3)),
         101: (ResNeXtBottleneck, (3, 4, 23, 3)),
