@@ -1340,6 +1340,50 @@ int ld_draw_boxes(uint8_t* img, int height, int width, const float* gt_boxes, in
                   const float* dets, int num_dets, float score_thr, int thickness,
                   uint32_t gt_color, uint32_t det_color, ld_stream_t stream);
 
+/* ---- proposal recall (recall.hip) -------------------------------------------
+ * eval_recalls / _recalls of the reference (core/evaluation/recall.py:10-40,
+ * 83-103).  One batch of images per ld_eval_recalls_match call: proposals
+ * (k, prop_cols) fp32, prop_cols 5 = [x1 y1 x2 y2 score] or 4 = boxes already in
+ * order, and GTs (g, 4) fp32, packed image after image; prop_off / gt_off are
+ * DEVICE int32 arrays of num_imgs + 1 offsets.  max_img_props is a host bound:
+ * the most proposals of one batch image.  proposal_nums: HOST int32, num_nums <=
+ * LD_EVAL_RECALLS_MAX_NUMS, each >= 0; the proposals of an image are cut to
+ * proposal_nums[num_nums - 1] (the LAST entry, as the reference does) after a
+ * descending score sort (equal scores: the later index first).
+ *
+ * One workgroup per image computes the fp32 GT x proposal IoU tile and, for
+ * every budget p, the reference's greedy matching over the first
+ * min(k, proposal_nums[p]) columns.  Round j of image i writes
+ *   gt_ious[p * gt_stride + gt_base + gt_off[i] + j]
+ * the IoU of the GT matched in that round: -1 once the columns are used up, 0
+ * for a budget without columns.  gt_ious is a DEVICE (num_nums, gt_stride) fp32
+ * table that the caller grows batch after batch; gt_base is the number of GTs
+ * of the batches before this one, gt_base + num_gts <= gt_stride.  Images
+ * without GTs write nothing.  The tile stays in LDS when it fits (12288 IoUs,
+ * 1024 kept proposals, 256 GTs); larger images, or every image with
+ * LD_EVAL_RECALLS_NO_LDS, use the workspace.  Both routes give the same bits.
+ * The host does not see the offsets, so the workspace (4-byte aligned,
+ * ld_eval_recalls_workspace_bytes) is sized for the whole batch whichever route
+ * its images take. */
+#define LD_EVAL_RECALLS_MAX_NUMS 16
+#define LD_EVAL_RECALLS_NO_LDS 1
+size_t ld_eval_recalls_workspace_bytes(int num_props, int num_gts, int max_img_props,
+                                       int cap);
+int ld_eval_recalls_match(const float* props, int prop_cols, const int32_t* prop_off,
+                          const float* gts, const int32_t* gt_off, int num_imgs,
+                          int num_props, int num_gts, int max_img_props, int num_nums,
+                          const int32_t* proposal_nums, int flags, float* gt_ious,
+                          long long gt_stride, long long gt_base, void* workspace,
+                          size_t workspace_bytes, ld_stream_t stream);
+
+/* recalls[p * num_thrs + t] = count((double)gt_ious[p][g] >= iou_thrs[t], g <
+ * total_gt) / (double)total_gt (DEVICE float64; iou_thrs HOST float64, num_thrs
+ * <= LD_EVAL_MAX_THRS).  total_gt == 0 gives NaN, as the reference's division
+ * does.  Integer counts, one writer per output: two runs give the same bits. */
+int ld_eval_recalls_count(const float* gt_ious, long long gt_stride, long long total_gt,
+                          int num_nums, int num_thrs, const double* iou_thrs,
+                          double* recalls, ld_stream_t stream);
+
 /* ---- COCO-style bbox evaluation (coco_eval.hip) ----------------------------
  * pycocotools' COCOeval(iouType='bbox') evaluate() + accumulate() as mmdet's
  * CocoDataset.evaluate runs them, float64 throughout.  Categories are indexed

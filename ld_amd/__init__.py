@@ -33,5 +33,9 @@ from .coco_eval import (CocoEvaluator, CocoGroundTruth,  # noqa: F401,E402
                         coco_evaluate)
 from .coco_analysis import (CocoErrorAnalysis,  # noqa: F401,E402
                             coco_error_analysis)
+from .recall import (CocoProposalEvaluator,  # noqa: F401,E402
+                     RecallAccumulator, coco_proposal_evaluate, eval_recalls,
+                     plot_iou_recall, plot_num_recall, print_recall_summary,
+                     set_recall_param)
 
 __version__ = '0.1.0'

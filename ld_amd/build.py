@@ -32,6 +32,7 @@ PER_FILE = {
     'infer.hip': ['-ffp-contract=off'],
     'eval.hip': ['-ffp-contract=off'],
     'eval_image.hip': ['-ffp-contract=off'],
+    'recall.hip': ['-ffp-contract=off'],
     'coco_eval.hip': ['-ffp-contract=off'],
     'quality.hip': ['-ffp-contract=off'],
     'pipeline.hip': ['-ffp-contract=off'],

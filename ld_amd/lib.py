@@ -80,6 +80,8 @@ LD_EVAL_MAX_SCALES = 16
 LD_EVAL_MAX_THRS = 16
 LD_EVAL_11POINTS = 1
 LD_EVAL_IMAGE_NO_LDS = 1
+LD_EVAL_RECALLS_MAX_NUMS = 16
+LD_EVAL_RECALLS_NO_LDS = 1
 
 
 class EvalBatchT(C.Structure):
@@ -244,7 +246,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -377,6 +379,13 @@ SIGNATURES = {
     'ld_rank_images': (C.c_int, [_i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_draw_boxes': (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _f32,
                                 _i32, C.c_uint32, C.c_uint32, _vp]),
+    'ld_eval_recalls_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'ld_eval_recalls_match': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32,
+                                        _i32, _i32, _i32, _vp, _i32, _vp,
+                                        C.c_longlong, C.c_longlong, _vp, _sz,
+                                        _vp]),
+    'ld_eval_recalls_count': (C.c_int, [_vp, C.c_longlong, C.c_longlong, _i32,
+                                        _i32, _vp, _vp, _vp]),
     'ld_coco_match_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'ld_coco_match': (C.c_int, [C.POINTER(CocoBatchT), _i32, _vp, _i32, _vp,
                                 _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,

@@ -702,6 +702,134 @@ def coco_eval_inputs(case):
     return dataset, results, [c['name'] for c in cats], dict(kw)
 
 
+# ----------------------------------------------------------- eval_recalls ----
+# (name, seed, GTs of each image (None: no GT entry), proposals of each image,
+#  score column).  Proposals are GT boxes jittered by a few amplitudes plus
+#  random distractors (uniformly random boxes alone recall nothing), shuffled,
+#  with pairwise distinct scores inside an image: the reference's argsort has
+#  one answer (tests/golden/recall.npz, tools/gen_golden_recall.py).  'mixed'
+#  has an image without a GT entry, an empty one, one without proposals and one
+#  with fewer proposals than GTs; 'big' one image above what the kernel keeps
+#  in LDS (1500 proposals, cut to 1000, and 130 GTs); 'ties' is hand-made.
+RECALL_CASES = [
+    ('mixed', 41, (3, None, 0, 7, 5, 1), (40, 12, 9, 0, 3, 25), True),
+    ('noscore', 42, (4, 0, 6, 2, None, 7), (30, 5, 40, 0, 11, 4), False),
+    ('equal', 43, (5, 5, 5, 5), (30, 30, 30, 30), True),
+    ('big', 44, (130, 4, 2), (1500, 20, 1), True),
+    ('nogt', 45, (None, 0, 0), (6, 0, 9), True),
+    ('ties', 0, None, None, True),
+]
+_RECALL_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1,
+                           endpoint=True)
+# (tag, case, proposal_nums, iou_thrs, through eval_recalls whole, recalls
+#  must lie strictly between 0 and 1 at several entries)
+RECALL_RUNS = [
+    ('mixed', 'mixed', (5, 20, 100), _RECALL_THRS, False, True),
+    ('unsorted_nums', 'mixed', (12, 3, 8), _RECALL_THRS, False, True),
+    ('ties', 'ties', (2, 4, 6, 20), (0.5, 0.75, 1.0), False, False),
+    ('noscore', 'noscore', (5, 20, 100), _RECALL_THRS, False, True),
+    ('equal', 'equal', (5, 10, 30), [0.5, 0.7, 0.9], True, True),
+    ('equal_int_float', 'equal', 10, 0.75, True, False),
+    ('equal_none', 'equal', [20], None, True, False),
+    ('big', 'big', (100, 300, 1000), _RECALL_THRS, False, True),
+    ('nogt', 'nogt', (5, 20), (0.5, 0.75), False, False),
+]
+
+
+def recall_is_interior(recalls):
+    """The generator's assertion: at least three entries (all of them in a
+    smaller table) lie strictly between 0 and 1."""
+    r = np.asarray(recalls)
+    return int(((r > 0) & (r < 1)).sum()) >= min(3, r.size)
+
+
+def _recall_ties():
+    a, b = [10, 10, 50, 50], [100, 100, 160, 140]
+    gts = [
+        # duplicated GTs, a GT every proposal misses (twice), a plain one
+        np.array([a, b, a, [300, 300, 340, 340], [200, 200, 260, 260],
+                  [600, 20, 640, 60]], np.float32),
+        np.array([a, a, a], np.float32),  # more equal GTs than proposals
+    ]
+    props = [
+        np.array([[12, 11, 52, 49], a, [104, 98, 158, 143], a, b,
+                  [104, 98, 158, 143], [205, 204, 262, 258],
+                  [205, 204, 262, 258], [400, 400, 420, 420],
+                  [14, 14, 46, 50]], np.float32),
+        np.array([[12, 12, 50, 50], a], np.float32),
+    ]
+    scores = [np.array([.9, .3, .8, .7, .2, .6, .5, .4, .95, .1], np.float32),
+              np.array([.5, .4], np.float32)]
+    return gts, [np.concatenate([p, s[:, None]], 1)
+                 for p, s in zip(props, scores)]
+
+
+def recall_inputs(case):
+    """A RECALL_CASES row -> (gts, proposals): ``gts[i]`` (n, 4) float32 or
+    None, ``proposals[i]`` (k, 5) float32, or (k, 4) for a case without the
+    score column."""
+    name, seed, gts_per_img, props_per_img, with_score = case
+    if name == 'ties':
+        return _recall_ties()
+    rng = np.random.RandomState(seed)
+    gts, proposals = [], []
+    for ngt, k in zip(gts_per_img, props_per_img):
+        g = _eval_boxes(rng, ngt or 0)
+        rows = []
+        if len(g):
+            wh = np.concatenate([g[:, 2:] - g[:, :2]] * 2, 1)
+            for amp in (0.03, 0.08, 0.2):
+                src = rng.permutation(len(g))[:max(1, (2 * len(g)) // 3)]
+                jit = rng.normal(0, amp, size=(len(src), 4)) * wh[src]
+                rows.append(g[src] + jit.astype(np.float32))
+        near = np.concatenate(rows) if rows else np.zeros((0, 4), np.float32)
+        near = near[rng.permutation(len(near))[:(2 * k) // 3]]
+        p = np.concatenate([near, _eval_boxes(rng, k - len(near))])
+        p = p[rng.permutation(k)].astype(np.float32)
+        if with_score:
+            s = ((rng.permutation(k) + 1) / (k + 1)).astype(np.float32)
+            assert len(np.unique(s)) == k
+            p = np.concatenate([p, s[:, None]], 1)
+        gts.append(None if ngt is None else g)
+        proposals.append(p)
+    return gts, proposals
+
+
+def recall_cases():
+    """Every run of the recall fixture -> (tag, gts, proposals, proposal_nums,
+    iou_thrs, whole, interior)."""
+    by_name = {c[0]: c for c in RECALL_CASES}
+    inputs = {}
+    out = []
+    for tag, name, nums, thrs, whole, interior in RECALL_RUNS:
+        if name not in inputs:
+            inputs[name] = recall_inputs(by_name[name])
+        out.append((tag, ) + inputs[name] + (nums, thrs, whole, interior))
+    return out
+
+
+def recall_scale_inputs(num_imgs=5000, props_per_img=1000, seed=46):
+    """val2017-sized input in packed form: per image (1000, 5) proposals
+    around and away from its 1..13 (about 7) GTs, distinct scores."""
+    rng = np.random.RandomState(seed)
+    ngt = rng.randint(1, 14, size=num_imgs)
+    gts = _eval_boxes(rng, int(ngt.sum()))
+    goff = np.concatenate([[0], np.cumsum(ngt)])
+    N = num_imgs * props_per_img
+    src = goff[:-1].repeat(props_per_img) + (
+        rng.randint(0, 1 << 30, size=N) % ngt.repeat(props_per_img))
+    box = gts[src]
+    wh = np.concatenate([box[:, 2:] - box[:, :2]] * 2, 1)
+    amp = rng.choice([0.03, 0.1, 0.3, 1.0], size=(N, 1))
+    props = box + (rng.normal(0, 1, size=(N, 4)) * amp * wh).astype(np.float32)
+    score = np.stack([rng.permutation(props_per_img)
+                      for _ in range(num_imgs)]).reshape(-1)
+    score = ((score + 1) / np.float32(props_per_img + 1)).astype(np.float32)
+    props = np.concatenate([props, score[:, None]], 1).astype(np.float32)
+    return dict(proposals=props.reshape(num_imgs, props_per_img, 5), gts=gts,
+                gt_off=goff)
+
+
 def box_loss_rows(n, seed=31, img_h=160, img_w=224):
     """``n`` (pred, target) box pairs for the row box losses: seeded targets
     and predictions jittered around them by up to +-0.4 of the target's size per
