@@ -892,6 +892,41 @@ int ld_gn_backward_c8_lean(const ld_levels_t* lv, const float* dy, const float* 
  * forward only (the stem is frozen, frozen_stages=1). */
 int ld_maxpool3x3s2(const float* x, int rows, int H, int W, float* y,
                     ld_stream_t stream);
+/* ---- Res2Net block glue (backbones/res2net.py:108-162) ----------------------
+ * Everything between the convs of a Bottle2neck, one launch each, on `stream`,
+ * nothing allocated or synchronised.  u is relu(bn1(conv1(x))) of shape
+ * (N, C = scales*w, P); all tensors contiguous fp32.  Pools are a row-major fp32
+ * sum followed by one IEEE division; pool backwards sum dy / divisor addends in
+ * ascending (oh, ow) order; no atomics anywhere (runs are bit-identical).  The
+ * 16-byte paths are taken only when every address they form is 16-byte aligned.
+ * Null pointers / bad geometry: LD_EINVAL before any launch.
+ *
+ * ld_res2_gather: y (N, w, P) = u[:, slice*w : (slice+1)*w] (+ addend (N, w, P),
+ *   or NULL): the operand of conv `slice` with the hierarchical add fused.  The
+ *   block's backward uses it on d cat: d sp_i = d cat[:, slice i] (+ d x_{i+1}).
+ * ld_res2_concat: y (N, 4w, Py) = cat(a, b, c, tail); a, b, c are (N, w, Py) and
+ *   tail is slice `tslice` (width w) of t (N, Ct, Pt):
+ *     LD_RES2_TAIL_COPY      Pt = Py = H*W, tail copied;
+ *     LD_RES2_TAIL_POOL      t at H x W, y at Ho x Wo = floor((H-1)/stride)+1:
+ *                            AvgPool2d(3, stride, padding=1), divisor 9;
+ *     LD_RES2_TAIL_POOL_BWD  t at Ho x Wo, y at H x W: that pool's backward.
+ *   The block's backward uses it to assemble d u from the three conv-input
+ *   gradients and d cat (COPY, or POOL_BWD where the forward pooled).
+ * ld_avgpool_ceil_*: AvgPool2d(k, k, ceil_mode=True, count_include_pad=False)
+ *   of the avg_down shortcut on rows = N*C planes, H x W -> ceil(H/k) x
+ *   ceil(W/k); a partial last window divides by its number of valid elements. */
+#define LD_RES2_TAIL_COPY 0
+#define LD_RES2_TAIL_POOL 1
+#define LD_RES2_TAIL_POOL_BWD 2
+int ld_res2_gather(const float* u, const float* addend, int N, int C, int w, int slice,
+                   long long P, float* y, ld_stream_t stream);
+int ld_res2_concat(const float* a, const float* b, const float* c, const float* t,
+                   int N, int w, int Ct, int tslice, int H, int W, int stride, int mode,
+                   float* y, ld_stream_t stream);
+int ld_avgpool_ceil_forward(const float* x, long long rows, int H, int W, int k,
+                            float* y, ld_stream_t stream);
+int ld_avgpool_ceil_backward(const float* dy, long long rows, int H, int W, int k,
+                             float* dx, ld_stream_t stream);
 /* FPN top-down step (fpn.py:182-191): out = fine + nearest_up(coarse) with the
  * finer map's size as target; rows = N*C planes.  Backward: dfine = dout
  * (identity), dcoarse[q] = sum of dout over the fine cells that read q. */

@@ -36,6 +36,7 @@ PER_FILE = {
     'coco_eval.hip': ['-ffp-contract=off'],
     'quality.hip': ['-ffp-contract=off'],
     'pipeline.hip': ['-ffp-contract=off'],
+    'res2net.hip': ['-ffp-contract=off'],
 }
 
 

@@ -2227,6 +2227,175 @@ def maxpool3x3s2(x4):
     return y
 
 
+# ---------------------------------------------------------------------------
+# Res2Net block glue (csrc/res2net.hip; backbones/res2net.py:108-162)
+# ---------------------------------------------------------------------------
+# u = relu(bn1(conv1(x))) is (N, 4w, P).  Forward, per Bottle2neck: one gather per
+# 3x3 conv (slice i of u, plus the previous conv's output in 'normal' blocks) and
+# one concatenate (the three conv outputs + slice 3 of u, copied or pooled).
+# Backward, the same kernels the other way round:
+#   Res2CatFn.backward     keeps d cat; hands out d sp_i = d cat[:, slice i] as a
+#                          gather -- all three in a 'stage' block, only the last
+#                          one in a 'normal' block;
+#   Res2GatherFn.backward  keeps d x_i (the conv's data gradient) and, in a
+#                          'normal' block, returns d sp_{i-1} = d cat[:, slice
+#                          i-1] + d x_i as ONE gather with the add fused;
+#   the last gather to run assembles d u = cat(d x_0, d x_1, d x_2, tail') in one
+#                          launch (tail' = d cat[:, slice 3] or its pool backward).
+# The other consumers return None for u, so autograd never sums (N, 4w, P) tensors.
+RES2_TAIL_COPY, RES2_TAIL_POOL, RES2_TAIL_POOL_BWD = 0, 1, 2
+
+
+class Res2State:
+    """What one Bottle2neck forward shares between its glue nodes' backwards."""
+
+    def __init__(self, width, hw, stride, pool):
+        self.width, self.hw, self.stride, self.pool = width, hw, stride, pool
+        self.dcat = None
+        self.dx = [None, None, None]
+
+
+def _res2_gather(src, slice_, w, addend):
+    _dev_f32(src, 'res2 gather input')
+    N, c, P = src.shape
+    if addend is not None and (tuple(addend.shape) != (N, w, P) or
+                               not addend.is_contiguous()):
+        raise L.LdError('res2 gather: addend shape mismatch')
+    if not src.is_contiguous() or _unwritten(src):
+        raise L.LdError('res2 gather: the input must be a written, contiguous '
+                        'fp32 tensor')
+    y = torch.empty((N, w, P), dtype=torch.float32, device=src.device)
+    L.check(L.get_lib().ld_res2_gather(L.ptr(src), L.ptr(addend), N, c, w,
+                                       slice_, P, L.ptr(y),
+                                       L.stream_ptr(src.device)),
+            'ld_res2_gather')
+    return y
+
+
+def _res2_concat(parts, t, w, hw, stride, mode):
+    a, b, c = parts
+    N = a.shape[0]
+    h, w_ = hw
+    if mode == RES2_TAIL_COPY:
+        py = pt = h * w_
+    else:
+        po = out_size(h, 3, stride, 1) * out_size(w_, 3, stride, 1)
+        py, pt = (po, h * w_) if mode == RES2_TAIL_POOL else (h * w_, po)
+    for p in parts:
+        if tuple(p.shape) != (N, w, py) or not p.is_contiguous():
+            raise L.LdError('res2 concat: part shape mismatch')
+    _dev_f32(t, 'res2 concat tail')
+    if t.shape[0] != N or t.shape[2] != pt or t.shape[1] < 4 * w or \
+            not t.is_contiguous() or _unwritten(t):
+        raise L.LdError('res2 concat: tail source shape mismatch')
+    y = torch.empty((N, 4 * w, py), dtype=torch.float32, device=a.device)
+    L.check(L.get_lib().ld_res2_concat(
+        L.ptr(a), L.ptr(b), L.ptr(c), L.ptr(t), N, w, t.shape[1], 3, h, w_,
+        stride, mode, L.ptr(y), L.stream_ptr(a.device)), 'ld_res2_concat')
+    return y
+
+
+class Res2GatherFn(torch.autograd.Function):
+    """x_i = u[:, i*w:(i+1)*w] (+ prev): the contiguous operand of conv i."""
+
+    @staticmethod
+    def forward(ctx, u, prev, i, st):
+        ctx.i, ctx.st = i, st
+        return _res2_gather(u, i, st.width, prev)
+
+    @staticmethod
+    def backward(ctx, g):
+        st, i = ctx.st, ctx.i
+        g = g.contiguous()
+        st.dx[i] = g
+        dprev = du = None
+        if ctx.needs_input_grad[1]:
+            dprev = _res2_gather(st.dcat, i - 1, st.width, g)
+        if ctx.needs_input_grad[0] and all(d is not None for d in st.dx):
+            du = _res2_concat(st.dx, st.dcat, st.width, st.hw, st.stride,
+                              RES2_TAIL_POOL_BWD if st.pool else RES2_TAIL_COPY)
+            st.dx, st.dcat = [None, None, None], None
+        return du, dprev, None, None
+
+
+class Res2CatFn(torch.autograd.Function):
+    """cat(sp_0, sp_1, sp_2, tail(u[:, 3w:4w])), tail copied or pooled."""
+
+    @staticmethod
+    def forward(ctx, sp0, sp1, sp2, u, st, chained):
+        ctx.st, ctx.chained = st, chained
+        return _res2_concat((sp0, sp1, sp2), u, st.width, st.hw, st.stride,
+                            RES2_TAIL_POOL if st.pool else RES2_TAIL_COPY)
+
+    @staticmethod
+    def backward(ctx, dcat):
+        st = ctx.st
+        st.dcat = dcat = dcat.contiguous()
+        # 'normal' block: sp_0 / sp_1 also feed the next gather, whose backward
+        # returns their whole gradient (slice of d cat + d x_{i+1}) in one launch
+        ds = [_res2_gather(dcat, i, st.width, None)
+              if ctx.needs_input_grad[i] and (i == 2 or not ctx.chained)
+              else None for i in range(3)]
+        return ds[0], ds[1], ds[2], None, None, None
+
+
+def res2_gather(u, prev, i, st):
+    if torch.is_grad_enabled() and (u.requires_grad or (
+            prev is not None and prev.requires_grad)):
+        return Res2GatherFn.apply(u, prev, i, st)
+    return _res2_gather(u, i, st.width, prev)
+
+
+def res2_concat(sps, u, st, chained):
+    if torch.is_grad_enabled() and (u.requires_grad or
+                                    any(s.requires_grad for s in sps)):
+        return Res2CatFn.apply(sps[0], sps[1], sps[2], u, st, chained)
+    return _res2_concat(tuple(sps), u, st.width, st.hw, st.stride,
+                        RES2_TAIL_POOL if st.pool else RES2_TAIL_COPY)
+
+
+def _avgpool_ceil(x3, hw, k, backward):
+    _dev_f32(x3, 'avgpool input')
+    N, c, P = x3.shape
+    h, w = hw
+    ho, wo = -(-h // k), -(-w // k)
+    if P != (ho * wo if backward else h * w) or not x3.is_contiguous() or \
+            _unwritten(x3):
+        raise L.LdError('avgpool_ceil: shape mismatch')
+    y = torch.empty((N, c, h * w if backward else ho * wo),
+                    dtype=torch.float32, device=x3.device)
+    lib = L.get_lib()
+    fn = lib.ld_avgpool_ceil_backward if backward else \
+        lib.ld_avgpool_ceil_forward
+    L.check(fn(L.ptr(x3), N * c, h, w, k, L.ptr(y), L.stream_ptr(x3.device)),
+            'ld_avgpool_ceil')
+    return y
+
+
+class AvgPoolCeilFn(torch.autograd.Function):
+    """AvgPool2d(k, k, ceil_mode=True, count_include_pad=False) on (N, C, H*W):
+    the avg_down shortcut (res2net.py:199-214)."""
+
+    @staticmethod
+    def forward(ctx, x3, hw, k):
+        ctx.hw, ctx.k = hw, k
+        ctx.fan = fan_in(ctx, 0, x3)
+        return _avgpool_ceil(x3, hw, k, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = _avgpool_ceil(dy.contiguous(), ctx.hw, ctx.k, True)
+        return fan_give(ctx.fan, dx), None, None
+
+
+def avgpool_ceil(x3, hw, k):
+    """-> (y3, (ho, wo))."""
+    out = (-(-hw[0] // k), -(-hw[1] // k))
+    if torch.is_grad_enabled() and x3.requires_grad:
+        return AvgPoolCeilFn.apply(x3, hw, k), out
+    return _avgpool_ceil(x3, hw, k, False), out
+
+
 class UpsampleAddFn(torch.autograd.Function):
     """out = fine + nearest_up(coarse)  (FPN top-down step)."""
 

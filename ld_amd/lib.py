@@ -495,6 +495,14 @@ SIGNATURES = {
                                  _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
                                  _sz, _vp]),
     'ld_maxpool3x3s2': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
+    'ld_res2_gather': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32,
+                                 C.c_longlong, _vp, _vp]),
+    'ld_res2_concat': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
+                                 _i32, _i32, _i32, _i32, _vp, _vp]),
+    'ld_avgpool_ceil_forward': (C.c_int, [_vp, C.c_longlong, _i32, _i32, _i32,
+                                          _vp, _vp]),
+    'ld_avgpool_ceil_backward': (C.c_int, [_vp, C.c_longlong, _i32, _i32,
+                                           _i32, _vp, _vp]),
     'ld_upsample_add_forward': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32,
                                           _i32, _vp, _vp]),
     'ld_upsample_add_backward': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32,

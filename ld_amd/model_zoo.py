@@ -43,6 +43,23 @@ def _x101_backbone(depth=101, dcn=False):
     return cfg
 
 
+def _r2n_backbone(depth=101, dcn=True):
+    """The Res2Net (v1d, 26w x 4s) backbone of
+    configs/imv2/gflv2_r2n101_dcn_fpn_2x.py:8-20 (configs/im/ has the same
+    file): deep stem, avg_down shortcuts, DCNv1 as the three 3x3 convs of every
+    c4-c5 Bottle2neck.  ``dcn=False``: the plain composition the golden
+    fixture pins (the reference's DCN op does not run on the CPU)."""
+    cfg = dict(type='Res2Net', depth=depth, num_stages=4, scales=4,
+               base_width=26, out_indices=(0, 1, 2, 3), frozen_stages=1,
+               norm_cfg=dict(type='BN', requires_grad=True), norm_eval=True,
+               style='pytorch')
+    if dcn:
+        cfg.update(dcn=dict(type='DCN', deform_groups=1,
+                            fallback_on_stride=False),
+                   stage_with_dcn=(False, False, True, True))
+    return cfg
+
+
 def _neck(depth):
     return dict(type='FPN', in_channels=list(_RESNET_CH[depth]),
                 out_channels=256, start_level=1, add_extra_convs='on_output',
@@ -160,6 +177,28 @@ def gflv2_x101_detector(dcn=True):
     ``pretrained`` is None where the file names the open-mmlab checkpoint."""
     cfg = gflv2_detector(101)
     cfg['backbone'] = _x101_backbone(101, dcn)
+    return cfg
+
+
+def gflv2_r2n101_dcn_detector(depth=101, dcn=True):
+    """configs/imv2/gflv2_r2n101_dcn_fpn_2x.py and configs/im/
+    gflv2_r2n101_dcn_fpn_2x.py (identical ``model`` dicts): the GFLv2
+    Res2Net-101-DCN teacher.  ``pretrained`` is None where the files name
+    'open-mmlab://res2net101_v1d_26w_4s' (as in gfl_x101_detector)."""
+    cfg = gflv2_detector(101)
+    cfg['backbone'] = _r2n_backbone(depth, dcn)
+    return cfg
+
+
+def ldv2_x101_r2n101_detector(imitation_method='finegrained',
+                              loss_im_weight=2.0):
+    """The reference README's best row -- "Main KD + Main LD + VLR LD
+    Res2Net101-DCN -> X101-32x4d-DCN": the LDv2 head on a ResNeXt-101 32x4d
+    DCN student with the GFLv2 Res2Net-101-DCN teacher (the reference ships no
+    such file; this is the composition, like ldv2_x101_detector)."""
+    cfg = ldv2_detector(101, 101, imitation_method, loss_im_weight)
+    cfg['backbone'] = _x101_backbone(101, dcn=True)
+    cfg['teacher_config']['model'] = gflv2_r2n101_dcn_detector()
     return cfg
 
 

@@ -18,7 +18,7 @@ import torch.nn as nn
 
 from . import layers as Y
 from . import lib as L
-from .cnn import (BatchNorm2d, Conv2d, GroupedConv2d, build_conv_layer,
+from .cnn import (BatchNorm2d, Conv2d, GroupedConv2d, ReLU, build_conv_layer,
                   build_norm_layer, constant_init, kaiming_init)
 from .registry import BACKBONES
 
@@ -250,6 +250,7 @@ class ResNet(nn.Module):
         101: (Bottleneck, (3, 4, 23, 3)),
         152: (Bottleneck, (3, 8, 36, 3))
     }
+    _deep_variants = False  # deep_stem / avg_down: the Res2Net subclass only
 
     def __init__(self, depth, in_channels=3, stem_channels=64, base_channels=64,
                  num_stages=4, strides=(1, 2, 2, 2), dilations=(1, 1, 1, 1),
@@ -261,9 +262,10 @@ class ResNet(nn.Module):
         super().__init__()
         if depth not in self.arch_settings:
             raise KeyError(f'invalid depth {depth} for resnet')
-        if deep_stem or avg_down or plugins is not None or \
-                tuple(dilations) != (1, 1, 1, 1):
+        if ((deep_stem or avg_down) and not self._deep_variants) or \
+                plugins is not None or tuple(dilations) != (1, 1, 1, 1):
             raise NotImplementedError('ResNet variant outside the LD configs')
+        self.deep_stem, self.avg_down = deep_stem, avg_down
         self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
         if dcn is not None:
             assert len(stage_with_dcn) == num_stages
@@ -282,11 +284,7 @@ class ResNet(nn.Module):
         self.stage_blocks = stage_blocks[:num_stages]
         self.inplanes = stem_channels
 
-        self.conv1 = build_conv_layer(conv_cfg, in_channels, stem_channels, 7,
-                                      stride=2, padding=3, bias=False)
-        self.norm1_name, norm1 = build_norm_layer(norm_cfg, stem_channels,
-                                                  postfix=1)
-        self.add_module(self.norm1_name, norm1)
+        self._make_stem_layer(in_channels, stem_channels)
 
         self.res_layers = []
         for i, num_blocks in enumerate(self.stage_blocks):
@@ -309,13 +307,36 @@ class ResNet(nn.Module):
         """resnet.py:515-517 (the hook ResNeXt overrides)."""
         return ResLayer(**kwargs)
 
+    def _make_stem_layer(self, in_channels, stem_channels):
+        """resnet.py:523-570: the 7x7 stem, or (``deep_stem``, Res2Net only)
+        three 3x3 convs as ``stem.0/1/3/4/6/7``; the max pool is a kernel."""
+        if self.deep_stem:
+            mid = stem_channels // 2
+            mods = []
+            for cin, cout, s in ((in_channels, mid, 2), (mid, mid, 1),
+                                 (mid, stem_channels, 1)):
+                mods += [build_conv_layer(self.conv_cfg, cin, cout, 3, stride=s,
+                                          padding=1, bias=False),
+                         build_norm_layer(self.norm_cfg, cout)[1], ReLU()]
+            self.stem = nn.Sequential(*mods)
+            return
+        self.conv1 = build_conv_layer(self.conv_cfg, in_channels, stem_channels,
+                                      7, stride=2, padding=3, bias=False)
+        self.norm1_name, norm1 = build_norm_layer(self.norm_cfg, stem_channels,
+                                                  postfix=1)
+        self.add_module(self.norm1_name, norm1)
+
     @property
     def norm1(self):
         return getattr(self, self.norm1_name)
 
     def _freeze_stages(self):
         """resnet.py:572-588."""
-        if self.frozen_stages >= 0:
+        if self.frozen_stages >= 0 and self.deep_stem:
+            self.stem.eval()
+            for p in self.stem.parameters():
+                p.requires_grad = False
+        elif self.frozen_stages >= 0:
             self.norm1.eval()
             for m in [self.conv1, self.norm1]:
                 for p in m.parameters():
@@ -360,8 +381,12 @@ class ResNet(nn.Module):
             raise NotImplementedError(
                 'a trainable stem needs a max-pool backward; the LD configs '
                 'freeze it (frozen_stages=1)')
-        x3 = x.reshape(n, c, h * w)
-        x3, lv = _conv_bn(x3, ((h, w), ), self.conv1, self.norm1)
+        x3, lv = x.reshape(n, c, h * w), ((h, w), )
+        if self.deep_stem:
+            for i in (0, 3, 6):
+                x3, lv = _conv_bn(x3, lv, self.stem[i], self.stem[i + 1])
+        else:
+            x3, lv = _conv_bn(x3, lv, self.conv1, self.norm1)
         x4 = Y.maxpool3x3s2(x3.view(n, -1, lv[0][0], lv[0][1]))
         lv = ((x4.shape[2], x4.shape[3]), )
         x3 = x4.reshape(n, x4.shape[1], -1)
@@ -473,3 +498,206 @@ class ResNeXt(ResNet):
     def make_res_layer(self, **kwargs):
         return ResLayer(groups=self.groups, base_width=self.base_width,
                         base_channels=self.base_channels, **kwargs)
+
+
+class Bottle2neck(nn.Module):
+    """Bottle2neck block of Res2Net (mmdet/models/backbones/res2net.py:17-162):
+    conv1 widens to ``scales * width`` channels, ``scales - 1`` 3x3 convs
+    (``convs.i`` / ``bns.i``; DCNs when the stage has ``dcn``) each take one
+    width-``width`` slice of it, the last slice passes through, conv3 reads the
+    concatenation.  ``stage_type='stage'`` (the first block of a layer): the
+    convs read their slices as they are and, when the 3x3 stride is not 1, the
+    last slice goes through AvgPool2d(3, stride, padding=1); ``'normal'``: the
+    input of conv i >= 1 is its slice plus the previous conv's output.  The
+    slicing, the adds, the concatenation and the pool are the glue kernels of
+    csrc/res2net.hip (layers.res2_gather / res2_concat), at most four launches
+    per block plus the shortcut pool; module order and state_dict keys are the
+    reference's (conv1, bn1, conv3, bn3, downsample, convs, bns)."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, scales=4, base_width=26,
+                 base_channels=64, stage_type='normal', stride=1, dilation=1,
+                 downsample=None, style='pytorch', with_cp=False, conv_cfg=None,
+                 norm_cfg=dict(type='BN'), dcn=None, plugins=None):
+        super().__init__()
+        assert style in ['pytorch', 'caffe']
+        assert dcn is None or isinstance(dcn, dict)
+        assert plugins is None and dilation == 1
+        assert stage_type in ('normal', 'stage')
+        if scales != 4:
+            raise NotImplementedError(
+                'Res2Net with scales != 4 (the block glue kernels concatenate '
+                'three conv outputs and one tail)')
+        self.dcn, self.with_dcn = dcn, dcn is not None
+        self.conv1_stride, self.conv2_stride = (1, stride) \
+            if style == 'pytorch' else (stride, 1)
+        width = int(math.floor(planes * (base_width / base_channels)))
+        self.norm1_name, norm1 = build_norm_layer(norm_cfg, width * scales,
+                                                  postfix=1)
+        self.norm3_name, norm3 = build_norm_layer(
+            norm_cfg, planes * self.expansion, postfix=3)
+        self.conv1 = build_conv_layer(conv_cfg, inplanes, width * scales, 1,
+                                      stride=self.conv1_stride, bias=False)
+        self.add_module(self.norm1_name, norm1)
+        self.conv3 = build_conv_layer(conv_cfg, width * scales,
+                                      planes * self.expansion, 1, bias=False)
+        self.add_module(self.norm3_name, norm3)
+        self.downsample = downsample
+        fallback_on_stride = False
+        if self.with_dcn:  # res2net.py:57-92
+            dcn = dict(dcn)
+            fallback_on_stride = dcn.pop('fallback_on_stride', False)
+        if not self.with_dcn or fallback_on_stride:
+            cfg3 = conv_cfg
+        else:
+            assert conv_cfg is None, 'conv_cfg must be None for DCN'
+            cfg3 = dcn
+        self.convs = nn.ModuleList(
+            build_conv_layer(cfg3, width, width, 3, stride=self.conv2_stride,
+                             padding=1, bias=False)
+            for _ in range(scales - 1))
+        self.bns = nn.ModuleList(
+            build_norm_layer(norm_cfg, width, postfix=i + 1)[1]
+            for i in range(scales - 1))
+        self.stage_type, self.scales, self.width = stage_type, scales, width
+        self.stride = stride
+
+    @property
+    def norm1(self):
+        return getattr(self, self.norm1_name)
+
+    @property
+    def norm3(self):
+        return getattr(self, self.norm3_name)
+
+    def forward3(self, x3, levels):
+        u, lv = _conv_bn(x3, levels, self.conv1, self.norm1)
+        chained = self.stage_type == 'normal'
+        pool = not chained and self.conv2_stride != 1
+        st = Y.Res2State(self.width, lv[0], self.conv2_stride, pool)
+        sps, sp, out_lv = [], None, lv
+        for i in range(self.scales - 1):
+            xi = Y.res2_gather(u, sp if chained and i else None, i, st)
+            sp, out_lv = _conv_bn(xi, lv, self.convs[i], self.bns[i])
+            sps.append(sp)
+        out = Y.res2_concat(sps, u, st, chained)
+        identity = x3
+        if self.downsample is not None:
+            pooled, plv = x3, levels
+            k = self.downsample[0].kernel_size
+            if k != 1:  # stride 1 (layer1): the pool is the identity, no launch
+                pooled, hw = Y.avgpool_ceil(x3, levels[0], k)
+                plv = (hw, )
+            identity, _ = _conv_bn(pooled, plv, self.downsample[1],
+                                   self.downsample[2], relu=False)
+        return _conv_bn(out, out_lv, self.conv3, self.norm3, residual=identity)
+
+
+class AvgPool2d(nn.Module):
+    """nn.AvgPool2d(k, k, ceil_mode=True, count_include_pad=False) of the
+    avg_down shortcut: parameter-free (``downsample.0``); Bottle2neck runs it as
+    layers.avgpool_ceil."""
+
+    def __init__(self, kernel_size):
+        super().__init__()
+        self.kernel_size = self.stride = kernel_size
+        self.ceil_mode, self.count_include_pad = True, False
+
+    def extra_repr(self):
+        return (f'kernel_size={self.kernel_size}, stride={self.stride}, '
+                'ceil_mode=True, count_include_pad=False')
+
+
+class Res2Layer(nn.Sequential):
+    """mmdet/models/backbones/res2net.py:165-241: the first block is a 'stage'
+    block whose shortcut (``avg_down``) is AvgPool2d -> 1x1 conv, stride 1 ->
+    BN: ``downsample.1.weight`` and ``downsample.2.*``."""
+
+    def __init__(self, block, inplanes, planes, num_blocks, stride=1,
+                 avg_down=True, conv_cfg=None, norm_cfg=dict(type='BN'),
+                 scales=4, base_width=26, **kwargs):
+        if not avg_down:
+            raise NotImplementedError('Res2Layer without avg_down')
+        downsample = None
+        if stride != 1 or inplanes != planes * block.expansion:
+            downsample = nn.Sequential(
+                AvgPool2d(stride),
+                build_conv_layer(conv_cfg, inplanes, planes * block.expansion,
+                                 1, stride=1, bias=False),
+                build_norm_layer(norm_cfg, planes * block.expansion)[1])
+        layers = [block(inplanes=inplanes, planes=planes, stride=stride,
+                        downsample=downsample, conv_cfg=conv_cfg,
+                        norm_cfg=norm_cfg, scales=scales,
+                        base_width=base_width, stage_type='stage', **kwargs)]
+        inplanes = planes * block.expansion
+        for _ in range(1, num_blocks):
+            layers.append(block(inplanes=inplanes, planes=planes, stride=1,
+                                conv_cfg=conv_cfg, norm_cfg=norm_cfg,
+                                scales=scales, base_width=base_width, **kwargs))
+        super().__init__(*layers)
+
+
+@BACKBONES.register_module()
+class Res2Net(ResNet):
+    """Res2Net backbone (mmdet/models/backbones/res2net.py:244-351): ResNet
+    with the deep stem (three 3x3 convs, ``stem.*``), avg_down shortcuts and
+    Bottle2neck blocks.  Under ``torch.no_grad()`` it is the GFLv2
+    Res2Net-101-DCN teacher (configs/imv2/gflv2_r2n101_dcn_fpn_2x.py); with
+    ``frozen_stages=1, norm_eval=True`` stages 2-4 train.  fp32 activations
+    throughout: in bf16 mode its convs follow the usual operand rules but the
+    trunk never runs C8-only (the glue kernels read fp32)."""
+    arch_settings = {
+        50: (Bottle2neck, (3, 4, 6, 3)),
+        101: (Bottle2neck, (3, 4, 23, 3)),
+        152: (Bottle2neck, (3, 8, 36, 3))
+    }
+    _deep_variants = True
+
+    def __init__(self, scales=4, base_width=26, style='pytorch',
+                 deep_stem=True, avg_down=True, **kwargs):
+        self.scales, self.base_width = scales, base_width
+        super().__init__(style='pytorch', deep_stem=True, avg_down=True,
+                         **kwargs)
+
+    def make_res_layer(self, **kwargs):
+        return Res2Layer(scales=self.scales, base_width=self.base_width,
+                         base_channels=self.base_channels, **kwargs)
+
+    def init_weights(self, pretrained=None):
+        """res2net.py:321-351."""
+        if isinstance(pretrained, str):
+            from .checkpoint import load_checkpoint
+            load_checkpoint(self, pretrained, strict=False)
+        elif pretrained is None:
+            for m in self.modules():
+                if isinstance(m, Conv2d):
+                    kaiming_init(m)
+                elif isinstance(m, BatchNorm2d):
+                    constant_init(m, 1)
+            if self.dcn is not None:
+                for m in self.modules():
+                    if isinstance(m, Bottle2neck):
+                        for n in m.convs:
+                            if hasattr(n, 'conv_offset'):
+                                constant_init(n.conv_offset, 0)
+            if self.zero_init_residual:
+                for m in self.modules():
+                    if isinstance(m, Bottle2neck):
+                        constant_init(m.norm3, 0)
+        else:
+            raise TypeError('pretrained must be a str or None')
+
+    def forward(self, x):
+        # the block glue reads fp32 activations: keep the trainable trunk's
+        # outputs written in bf16 mode too (layers.trunk_c8_scope off)
+        prev, Y._TRUNK_C8[0] = Y._TRUNK_C8[0], False
+        try:
+            return super().forward(x)
+        finally:
+            Y._TRUNK_C8[0] = prev
+
+    def _c8_only(self):
+        return False
+
+    def _frozen_c8_stages(self):
+        return 0
