@@ -1527,6 +1527,45 @@ int ld_coco_accumulate(int num_records, const float* rec_score, const int32_t* r
                        double* scores, void* workspace, size_t workspace_bytes,
                        ld_stream_t stream);
 
+/* ---- AP landscape / teacher-student discrepancy (landscape.hip) ---------------
+ * The reference's AP_landscape tool (detectors/single_stage.py:113-121,
+ * apis/test.py:105-177) on the level-concatenated (N, C, P) fp32 tensors the
+ * head towers consume (ld_pack_levels); `lv` lists the levels, whose H * W sum
+ * to P.  Bad arguments (null pointers, K out of range, levels that do not fill
+ * P, sizes <= 0) return LD_EINVAL before any launch.  No float atomics: two
+ * calls on the same input give the same bits.
+ *
+ * ld_levels_mix: out[k * n + i] = coefs[2k] * own[i] + coefs[2k + 1] * other[i]
+ * for the n elements of two tensors and 1 <= K <= LD_LEVELS_MIX_MAX_K grid
+ * points (coefs: HOST, K pairs); out is (K, n), grid point major.  Two fp32
+ * multiplies and one fp32 add in that order, never fused.  One launch; every
+ * input element is read once. */
+#define LD_LEVELS_MIX_MAX_K 16
+int ld_levels_mix(const float* own, const float* other, long long n, int K,
+                  const float* coefs, float* out, ld_stream_t stream);
+
+/* out[n * num_levels + l] = sum over the positions p of level l of
+ * (sum over c of |t[n, c, p] - s[n, c, p]|) / C (DEVICE float64): the
+ * reference's abs(t - s).mean(1).sum() of one level and image.  The difference
+ * and its absolute value are fp32, every sum is float64.  workspace: 8-byte
+ * aligned, ld_levels_abs_err_workspace_bytes (0: bad arguments). */
+size_t ld_levels_abs_err_workspace_bytes(const ld_levels_t* lv, int N, int C, int P);
+int ld_levels_abs_err(const ld_levels_t* lv, const float* t, const float* s, int N, int C,
+                      int P, double* out, void* workspace, size_t workspace_bytes,
+                      ld_stream_t stream);
+
+/* Pearson r of every row pair: a row is one (n, c) and the segment of one
+ * level.  Two passes in float64 (means, then the centred sums), r = Sxy /
+ * sqrt(Sxx * Syy).  A row with fewer than 2 positions, Sxx == 0 or Syy == 0 is
+ * degenerate (torch gives NaN there) and left out.  r_sum[n * num_levels + l]
+ * (DEVICE float64): the sum of r over the valid rows of (n, l);
+ * counts[2 * (n * num_levels + l)] (DEVICE int32) their number, [.. + 1] the
+ * number of degenerate rows.  workspace as for ld_levels_abs_err. */
+size_t ld_levels_pearson_workspace_bytes(const ld_levels_t* lv, int N, int C, int P);
+int ld_levels_pearson(const ld_levels_t* lv, const float* t, const float* s, int N, int C,
+                      int P, double* r_sum, int32_t* counts, void* workspace,
+                      size_t workspace_bytes, ld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,5 +37,7 @@ from .recall import (CocoProposalEvaluator,  # noqa: F401,E402
                      RecallAccumulator, coco_proposal_evaluate, eval_recalls,
                      plot_iou_recall, plot_num_recall, print_recall_summary,
                      set_recall_param)
+from .landscape import (FeatureLandscape,  # noqa: F401,E402
+                        TeacherStudentDiscrepancy, mix_levels)
 
 __version__ = '0.1.0'

@@ -37,6 +37,7 @@ PER_FILE = {
     'quality.hip': ['-ffp-contract=off'],
     'pipeline.hip': ['-ffp-contract=off'],
     'res2net.hip': ['-ffp-contract=off'],
+    'landscape.hip': ['-ffp-contract=off'],
 }
 
 

@@ -313,9 +313,31 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         the level-concatenated tensor, one launch per layer for all levels."""
         scales = getattr(self, 'scales', None)
         assert scales is None or len(feats) == len(scales)
-        x3, levels = self._pack(feats)
+        return self._trunk3(*self._pack(feats))
+
+    def _trunk3(self, x3, levels):
         return (_tower(self.cls_convs, x3, levels),
                 _tower(self.reg_convs, x3, levels), levels)
+
+    def forward_packed(self, x3, levels):
+        """``forward`` on a head input that is already level-concatenated:
+        ``x3`` (N, C, P) contiguous fp32 and its ``levels`` ((H, W), ...), as
+        ``layers.pack_levels`` returns them.  Nothing is packed or copied; the
+        outputs are those of ``forward`` on the level views of ``x3``."""
+        levels = tuple((int(h), int(w)) for h, w in levels)
+        scales = getattr(self, 'scales', None)
+        if scales is not None and len(levels) != len(scales):
+            raise ValueError(f'forward_packed: {len(levels)} levels for a head '
+                             f'of {len(scales)}')
+        if x3.dim() != 3 or x3.shape[1] != self.in_channels or \
+                x3.shape[2] != sum(h * w for h, w in levels):
+            raise ValueError(
+                f'forward_packed: input {tuple(x3.shape)} is not (N, '
+                f'{self.in_channels}, P) with P the positions of {levels}')
+        if not x3.is_contiguous():
+            raise ValueError('forward_packed: the input must be contiguous')
+        self._packed = None
+        return self._predict(*self._trunk3(x3, levels))
 
     def _scale(self, reg3, levels):
         """The per-level learnable Scale of the box branch."""
@@ -601,7 +623,9 @@ class GFLHead(_DenseHead):
     def forward(self, feats):
         """feats: tuple of per-level (N, C, H, W) -> (cls_scores, bbox_preds)
         lists (gfl_head.py:145-183)."""
-        cls_feat, reg_feat, levels = self._trunk(feats)
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
         cls3, _ = self.gfl_cls.forward3(cls_feat, levels)
         reg3, _ = self.gfl_reg.forward3(reg_feat, levels)
         reg3 = self._scale(reg3, levels)
@@ -823,7 +847,9 @@ class ATSSGFLHead(GFLHead):
 
     def forward(self, feats):
         """atss_gfl_head.py:139-183."""
-        cls_feat, reg_feat, levels = self._trunk(feats)
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
         cls3, _ = self.atss_cls.forward3(cls_feat, levels)
         reg3, _ = self.atss_reg.forward3(reg_feat, levels)
         ctr3, _ = self.atss_centerness.forward3(reg_feat, levels)
@@ -940,7 +966,9 @@ class FCOSGFLHead(_DenseHead):
 
     def forward(self, feats):
         """fcos_gfl_head.py:178-224."""
-        cls_feat, reg_feat, levels = self._trunk(feats)
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
         cls3, _ = self.conv_cls.forward3(cls_feat, levels)
         reg3, _ = self.conv_reg.forward3(reg_feat, levels)
         ctr3, _ = self.conv_centerness.forward3(reg_feat, levels)
@@ -1075,7 +1103,9 @@ class RetinaGFLHead(_DenseHead):
 
     def forward(self, feats):
         """retina_gfl_head.py:276-299."""
-        cls_feat, reg_feat, levels = self._trunk(feats)
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
         cls3, _ = self.atss_cls.forward3(cls_feat, levels)
         reg3, _ = self.atss_reg.forward3(reg_feat, levels)
         return Y.split_levels(cls3, levels), Y.split_levels(reg3, levels)
@@ -1225,7 +1255,9 @@ class GFocalHead(GFLHead):
     def forward(self, feats):
         """gfocal_head.py:160-217: GFLHead's forward, then the fused quality
         kernel."""
-        cls_feat, reg_feat, levels = self._trunk(feats)
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
         cls3, _ = self.gfl_cls.forward3(cls_feat, levels)
         reg3, _ = self.gfl_reg.forward3(reg_feat, levels)
         reg3 = self._scale(reg3, levels)
