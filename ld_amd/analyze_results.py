@@ -30,7 +30,8 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .evaluation import _f32, _i64
+from .eval_common import (as_boxes, eval_batch, eval_device,
+                          pack_det_gt_batch, results_to_lists)
 from .lossblock import workspace
 
 __all__ = ['bbox_map_eval', 'ImageMapAnalyzer', 'draw_gt_det_bboxes',
@@ -43,28 +44,13 @@ def default_iou_thrs():
         .5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
 
 
-def _device(device):
-    dev = torch.device(device) if device is not None else \
-        torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise L.LdError(f'analyze_results: device {dev} is not a HIP device '
-                        '(there is no CPU path)')
-    return dev
-
-
 def eval_image_map(batch, num_classes, iou_thrs, no_lds=False):
     """ld_eval_image_map on a packed batch (the dict ``evaluation.eval_tpfp``
     takes) -> device (map (I,) f64, ap (I, T, C) f32, has_gt (I, C) u8)."""
     lib = L.get_lib()
     dev = batch['det_off'].device
-    b = L.EvalBatchT()
-    for k in ('dets', 'det_labels', 'det_off', 'gts', 'gt_labels', 'gt_off',
-              'ign', 'ign_labels', 'ign_off'):
-        setattr(b, k, L.ptr(batch[k]).value)
-    I = b.num_imgs = batch['det_off'].numel() - 1
-    b.num_dets = batch['dets'].shape[0]
-    b.num_gts = batch['gts'].shape[0]
-    b.num_ign = batch['ign'].shape[0]
+    b = eval_batch(batch)
+    I = b.num_imgs
     T, C_ = len(iou_thrs), int(num_classes)
     thr = (L.C.c_double * T)(*[float(t) for t in iou_thrs])
     ap = torch.empty((I, T, C_), dtype=torch.float32, device=dev)
@@ -97,32 +83,9 @@ def rank_images(scores):
 
 
 def _results_to_lists(results, annotations, num_classes):
-    """The reference's list forms -> the per-image lists ``add`` takes."""
-    if len(results) != len(annotations):
-        raise ValueError('add_results: one annotation per image')
-    dets, labels, gb, gl, ib, il = [], [], [], [], [], []
-    for res, ann in zip(results, annotations):
-        if isinstance(res, tuple):  # (bbox, segm): analyze_results.py:33-34
-            res = res[0]
-        if len(res) != num_classes:
-            raise ValueError(f'add_results: {len(res)} class arrays, '
-                             f'expected {num_classes}')
-        rows = [np.asarray(r, dtype=np.float32).reshape(-1, 5) for r in res]
-        dets.append(np.concatenate(rows))
-        labels.append(np.concatenate([
-            np.full((r.shape[0], ), c, dtype=np.int64)
-            for c, r in enumerate(rows)]))
-        gb.append(np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4))
-        gl.append(np.asarray(ann['labels']).reshape(-1))
-        # get_cls_results (mean_ap.py:258-262): labels_ignore decides
-        if ann.get('labels_ignore', None) is not None:
-            ib.append(np.asarray(ann['bboxes_ignore'],
-                                 dtype=np.float32).reshape(-1, 4))
-            il.append(np.asarray(ann['labels_ignore']).reshape(-1))
-        else:
-            ib.append(np.zeros((0, 4), dtype=np.float32))
-            il.append(np.zeros((0, ), dtype=np.int64))
-    return dets, labels, gb, gl, ib, il
+    """The reference's list forms -> the per-image lists ``add`` takes; a
+    ``(bbox, segm)`` tuple stands for its bbox part."""
+    return results_to_lists(results, annotations, num_classes, bbox_segm=True)
 
 
 class ImageMapAnalyzer:
@@ -141,7 +104,7 @@ class ImageMapAnalyzer:
             raise ValueError(f'ImageMapAnalyzer: 1..{L.LD_EVAL_MAX_THRS} IoU '
                              f'thresholds, got {len(thrs)}')
         self.iou_thrs = thrs
-        self.device = _device(device)
+        self.device = eval_device(device, 'analyze_results')
         self._no_lds = False  # tests: every image through the workspace route
         self._map, self._ap, self._has_gt = [], [], []
 
@@ -154,50 +117,12 @@ class ImageMapAnalyzer:
         -- device tensors as ``get_bboxes`` / ``aug_test`` return them -- and
         GTs (g, 4) / (g,), optionally ignored GTs.  Packed as
         ``MapAccumulator.add`` packs them; one launch."""
-        B = len(det_bboxes)
-        if not (len(det_labels) == len(gt_bboxes) == len(gt_labels) == B):
-            raise ValueError('ImageMapAnalyzer.add: det_bboxes, det_labels, '
-                             'gt_bboxes and gt_labels need one entry per image')
-        if (gt_bboxes_ignore is None) != (gt_labels_ignore is None):
-            raise ValueError('ImageMapAnalyzer.add: gt_bboxes_ignore and '
-                             'gt_labels_ignore go together')
-        if gt_bboxes_ignore is not None and not \
-                len(gt_bboxes_ignore) == len(gt_labels_ignore) == B:
-            raise ValueError('ImageMapAnalyzer.add: one ignored-GT entry per '
-                             'image')
-        if B == 0:
+        batch = pack_det_gt_batch(
+            'ImageMapAnalyzer.add', ('det_bboxes', 'det_labels'), det_bboxes,
+            det_labels, gt_bboxes, gt_labels, gt_bboxes_ignore,
+            gt_labels_ignore, self.device)
+        if batch is None:
             return
-        dev = self.device
-        d = [_f32(x, dev, 5) for x in det_bboxes]
-        dl = [_i64(x, dev) for x in det_labels]
-        g = [_f32(x, dev, 4) for x in gt_bboxes]
-        gl = [_i64(x, dev) for x in gt_labels]
-        if gt_bboxes_ignore is None:
-            ig = [torch.zeros((0, 4), dtype=torch.float32, device=dev)] * B
-            il = [torch.zeros((0, ), dtype=torch.int64, device=dev)] * B
-        else:
-            ig = [_f32(x, dev, 4) for x in gt_bboxes_ignore]
-            il = [_i64(x, dev) for x in gt_labels_ignore]
-        for a, b, what in ((d, dl, 'detections'), (g, gl, 'GTs'),
-                           (ig, il, 'ignored GTs')):
-            for x, y in zip(a, b):
-                if x.shape[0] != y.shape[0]:
-                    raise ValueError(f'ImageMapAnalyzer.add: {what} and their '
-                                     'labels differ in length')
-
-        def pack(rows):
-            off = np.zeros(B + 1, dtype=np.int32)
-            off[1:] = np.cumsum([r.shape[0] for r in rows])
-            return torch.cat(rows).contiguous(), \
-                torch.from_numpy(off).to(dev)
-
-        batch = {}
-        batch['dets'], batch['det_off'] = pack(d)
-        batch['det_labels'] = torch.cat(dl).contiguous()
-        batch['gts'], batch['gt_off'] = pack(g)
-        batch['gt_labels'] = torch.cat(gl).contiguous()
-        batch['ign'], batch['ign_off'] = pack(ig)
-        batch['ign_labels'] = torch.cat(il).contiguous()
         m, ap, has_gt = eval_image_map(batch, self.num_classes, self.iou_thrs,
                                        self._no_lds)
         self._map.append(m)
@@ -285,10 +210,11 @@ def draw_gt_det_bboxes(img_u8_hwc, gt_bboxes, det_bboxes, score_thr=0,
     img = torch.as_tensor(img_u8_hwc)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise ValueError('draw_gt_det_bboxes: image must be (H, W, 3) uint8')
-    dev = img.device if img.device.type == 'cuda' else _device(None)
+    dev = img.device if img.device.type == 'cuda' else \
+        eval_device(None, 'analyze_results')
     out = img.to(dev).contiguous().clone()
-    g = _f32(gt_bboxes, dev, 4).contiguous()
-    d = _f32(det_bboxes, dev, 5).contiguous()
+    g = as_boxes(gt_bboxes, dev, 4).contiguous()
+    d = as_boxes(det_bboxes, dev, 5).contiguous()
     lib = L.get_lib()
     L.check(lib.ld_draw_boxes(
         L.ptr(out), out.shape[0], out.shape[1], L.ptr(g), g.shape[0], L.ptr(d),

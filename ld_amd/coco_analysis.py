@@ -32,6 +32,7 @@ import torch
 from . import lib as L
 from .coco_eval import (AREA_RNG, CocoGroundTruth, _CocoStream,
                         default_rec_thrs)
+from .eval_common import ADD_STEP, check_one_rank
 from .lossblock import workspace
 
 __all__ = ['CocoErrorAnalysis', 'coco_error_analysis', 'TYPES', 'AREA_NAMES']
@@ -182,7 +183,7 @@ class CocoErrorAnalysis(_CocoStream):
         rows 0-4 before the fill (-1 where a category and area have no
         non-ignored GT), ``aps`` (aps_table), ``rec_thrs`` and ``npig``
         (K, 4).  Images never added count as images without detections."""
-        self._check_one_rank()
+        check_one_rank('CocoErrorAnalysis.compute')
         npig = self._npig_all()
         precision, _, _ = self._accumulate(npig, len(self.iou_thrs) + 2)
         raw = precision.cpu().numpy()
@@ -297,9 +298,8 @@ def coco_error_analysis(results, gt, out_dir=None, types=('bbox', ),
     else:
         dets, labels = _results_from_arrays(results, gt)
     ev = CocoErrorAnalysis(gt, device)
-    step = 512
-    for i in range(0, len(dets), step):
-        j = min(len(dets), i + step)
+    for i in range(0, len(dets), ADD_STEP):
+        j = min(len(dets), i + ADD_STEP)
         ev.add(range(i, j), [torch.from_numpy(x) for x in dets[i:j]],
                [torch.from_numpy(x) for x in labels[i:j]])
     out = ev.compute()

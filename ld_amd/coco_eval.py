@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .eval_common import (ADD_STEP, RecordBuffers, as_boxes, as_labels,
+                          check_one_rank, eval_device, eval_logger, pack_rows)
 from .lossblock import workspace
 
 __all__ = ['CocoGroundTruth', 'CocoEvaluator', 'coco_evaluate']
@@ -50,14 +52,6 @@ def default_iou_thrs():
 def default_rec_thrs():
     return np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1,
                        endpoint=True)
-
-
-def _log(logger):
-    if isinstance(logger, logging.Logger):
-        return logger
-    if isinstance(logger, str) and logger != 'silent':
-        return logging.getLogger(logger)
-    return _LOG
 
 
 class CocoGroundTruth:
@@ -209,13 +203,6 @@ class CocoGroundTruth:
         return d
 
 
-def _f32(x, dev, last):
-    t = torch.as_tensor(x)
-    if t.numel() == 0:
-        t = t.reshape(0, last)
-    return t.to(device=dev, dtype=torch.float32).reshape(-1, last)
-
-
 class _CocoStream:
     """The streaming half that CocoEvaluator and CocoErrorAnalysis share:
     the label map, one record per detection kept on the device, ``add`` and
@@ -228,11 +215,7 @@ class _CocoStream:
         if len(gt.img_ids) == 0 or len(gt.cat_ids) == 0:
             raise ValueError(f'{name}: the ground truth has no images '
                              'or no categories')
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        if self.device.type != 'cuda':
-            raise L.LdError(f'{name}: device {self.device} is not a HIP '
-                            'device (there is no CPU path)')
+        self.device = eval_device(device, name)
         self.num_imgs = len(gt.img_ids)
         self.K = len(gt.sorted_cat_ids)
         self._img_rank = np.searchsorted(gt.sorted_img_ids,
@@ -244,43 +227,20 @@ class _CocoStream:
                                 device=self.device)
         self._seen = np.zeros(self.num_imgs, bool)
         self.num_dets = 0  # detection rows added (scored or not)
-        self._n = 0
-        self._buf = {}
-        for name, dt in (('score', torch.float32), ('cat', torch.int32),
-                         ('pos', torch.int32), ('match', torch.int64),
-                         ('ign', torch.int64)):
-            self._buf[name] = torch.empty(0, dtype=dt, device=self.device)
-
-    def _reserve(self, extra):
-        need = self._n + extra
-        cap = self._buf['score'].numel()
-        if need <= cap:
-            return
-        cap = max(need, 2 * cap, 1 << 12)
-        for name, old in self._buf.items():
-            new = torch.empty(cap, dtype=old.dtype, device=self.device)
-            new[:self._n] = old[:self._n]
-            self._buf[name] = new
+        self._rec = RecordBuffers(
+            dict(score=torch.float32, cat=torch.int32, pos=torch.int32,
+                 match=torch.int64, ign=torch.int64), self.device, 1 << 12)
 
     def _pack(self, indices, dets, labels):
         """One batch as the match kernels read it -> (dets (N, 5), labels,
         det_off, image ranks (device), per-image counts, N)."""
         dev = self.device
-        counts = [d.shape[0] for d in dets]
-        off = np.zeros(len(indices) + 1, np.int32)
-        off[1:] = np.cumsum(counts)
-        N = int(off[-1])
-        if N:
-            d = torch.cat(dets).contiguous()
-            lab = torch.cat(labels).contiguous()
-        else:
-            d = torch.zeros((0, 5), dtype=torch.float32, device=dev)
-            lab = torch.zeros(0, dtype=torch.int64, device=dev)
-        det_off = torch.from_numpy(off).to(dev)
+        d, det_off, counts = pack_rows(dets, dev, type(self).__name__)
+        lab = torch.cat(labels).contiguous()
         ranks = torch.from_numpy(
             self._img_rank[np.asarray(indices, np.int64)].astype(
                 np.int32)).to(dev)
-        return d, lab, det_off, ranks, counts, N
+        return d, lab, det_off, ranks, counts, d.shape[0]
 
     def add(self, indices, dets, labels):
         """One batch: ``indices`` (dataset indices into ``gt.img_ids``) and,
@@ -302,20 +262,18 @@ class _CocoStream:
         if len(np.unique(ix)) != B or self._seen[ix].any():
             raise ValueError(f'{name}.add: an image was added twice')
         dev = self.device
-        d = [_f32(x, dev, 5) for x in dets]
-        lab = [torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1)
-               for x in labels]
+        d = [as_boxes(x, dev, 5) for x in dets]
+        lab = [as_labels(x, dev) for x in labels]
         for x, y in zip(d, lab):
             if x.shape[0] != y.shape[0]:
                 raise ValueError(f'{name}.add: detections and labels '
                                  'differ in length')
         N = sum(x.shape[0] for x in d)
-        self._reserve(N)
-        lo, hi = self._n, self._n + N
-        rec = {k: v[lo:hi] for k, v in self._buf.items()}
-        self._match(indices, d, lab, self.npig, rec)
+        rec = self._rec
+        rec.reserve(N)
+        self._match(indices, d, lab, self.npig, rec.views(rec.n, rec.n + N))
         self._seen[ix] = True
-        self._n = hi
+        rec.n += N
         self.num_dets += N
 
     def records(self):
@@ -324,20 +282,11 @@ class _CocoStream:
         ``cat`` (category index, K when not scored), ``pos`` (image rank *
         maxDets[-1] + rank in its cell), ``score``, ``match`` / ``ign``
         (uint64 masks, bit t * A + a)."""
-        out = {k: v[:self._n].cpu().numpy() for k, v in self._buf.items()}
+        out = {k: v.cpu().numpy() for k, v in self._rec.views().items()}
         out['pos'] = out['pos'].view(np.uint32)
         out['match'] = out['match'].view(np.uint64)
         out['ign'] = out['ign'].view(np.uint64)
         return out
-
-    def _check_one_rank(self):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and \
-                dist.get_world_size() > 1:
-            raise NotImplementedError(
-                f'{type(self).__name__}.compute: results are not gathered '
-                f'across ranks (world size {dist.get_world_size()}); '
-                'evaluate on one rank, or gather the detections there first')
 
     def _npig_all(self):
         """npig with the images never added counted as images without
@@ -359,7 +308,8 @@ class _CocoStream:
         dev = self.device
         T, R, K = num_thrs, len(self.rec_thrs), self.K
         A, M = len(self.area_rng), len(self.max_dets)
-        need = lib.ld_coco_accumulate_workspace_bytes(self._n, K, T, A, M)
+        rec = self._rec
+        need = lib.ld_coco_accumulate_workspace_bytes(rec.n, K, T, A, M)
         if need == 0:
             raise L.LdError('ld_coco_accumulate_workspace_bytes: bad sizes')
         ws = workspace(dev, need, 'coco_accumulate')
@@ -370,9 +320,9 @@ class _CocoStream:
         md = (L.C.c_int32 * M)(*self.max_dets)
         rt = (L.C.c_double * R)(*self.rec_thrs.tolist())
         L.check(lib.ld_coco_accumulate(
-            self._n, L.ptr(self._buf['score']), L.ptr(self._buf['cat']),
-            L.ptr(self._buf['pos']), L.ptr(self._buf['match']),
-            L.ptr(self._buf['ign']), K, len(self.gt.sorted_img_ids), T, A, M,
+            rec.n, L.ptr(rec['score']), L.ptr(rec['cat']), L.ptr(rec['pos']),
+            L.ptr(rec['match']), L.ptr(rec['ign']), K,
+            len(self.gt.sorted_img_ids), T, A, M,
             L.C.cast(md, L.C.c_void_p), R, L.C.cast(rt, L.C.c_void_p),
             L.ptr(npig), L.ptr(precision), L.ptr(recall), L.ptr(scores),
             L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_coco_accumulate')
@@ -449,7 +399,7 @@ class CocoEvaluator(_CocoStream):
         (T, K, A, M) float64 as COCOeval.accumulate leaves them in
         ``eval``, ``npig`` (K, A) and ``stats`` (12,) from summarize.  Images
         never added count as images without detections."""
-        self._check_one_rank()
+        check_one_rank('CocoEvaluator.compute')
         npig = self._npig_all()
         precision, recall, scores = self._accumulate(npig, len(self.iou_thrs))
         out = dict(precision=precision.cpu().numpy(),
@@ -465,7 +415,7 @@ class CocoEvaluator(_CocoStream):
         metric='bbox': an OrderedDict of ``bbox_mAP``, ... rounded to 3
         places and ``bbox_mAP_copypaste``."""
         metrics, metric_items = check_metrics(metric, metric_items)
-        log = _log(logger)
+        log = eval_logger(logger, _LOG)
         eval_results = OrderedDict()
         for m in metrics:
             if self.num_dets == 0:  # loadRes([]) -> IndexError -> break
@@ -585,8 +535,7 @@ def coco_evaluate(results, gt, metric='bbox', logger=None, classwise=False,
         dets.append(torch.from_numpy(np.concatenate(rows)))
         labels.append(torch.from_numpy(np.concatenate(
             [np.full(len(r), c, np.int64) for c, r in enumerate(rows)])))
-    step = 512
-    for i in range(0, len(results), step):
-        ev.add(range(i, min(i + step, len(results))), dets[i:i + step],
-               labels[i:i + step])
+    for i in range(0, len(results), ADD_STEP):
+        ev.add(range(i, min(i + ADD_STEP, len(results))),
+               dets[i:i + ADD_STEP], labels[i:i + ADD_STEP])
     return ev.evaluate(metric, classwise, metric_items, logger)

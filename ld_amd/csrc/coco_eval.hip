@@ -65,9 +65,14 @@
 #include <algorithm>
 
 #include "../../include/ld_hip.h"
+#include "eval_common.h"
 #include "ld_launch.h"
 
 namespace {
+
+using ldeval::block_excl_scan;
+using ldeval::desc_key;
+using ldeval::find_img;
 
 constexpr int kWave = 64;
 constexpr int kLdsTile = 2048;  // doubles: 16 KiB IoU tile per match workgroup
@@ -76,10 +81,6 @@ constexpr int kSlots = 16;      // workgroups (global tiles) of the big-cell pat
 constexpr int kThreads = 256;
 constexpr int kItems = 8;
 constexpr int kTile = kThreads * kItems;  // records per accumulate tile
-constexpr int kRadixBits = 8;
-constexpr int kBins = 1 << kRadixBits;
-constexpr int kSortItems = 16;
-constexpr int kSortTile = kThreads * kSortItems;
 constexpr int kMaxLanes = 64 * LD_COCO_MAX_MAXDETS;  // (t, a) <= 64 times maxDets
 constexpr uint32_t kFlagCrowd = 1u << 8;
 constexpr uint32_t kFlagIdNz = 1u << 9;  // annotation id != 0
@@ -96,16 +97,6 @@ struct AccParams {
   int max_dets[LD_COCO_MAX_MAXDETS];
   int T, A, M, R, K, L, n, nt, max_det;
 };
-
-__device__ __forceinline__ int find_img(const int32_t* off, int num_imgs, int i) {
-  int lo = 0, hi = num_imgs - 1;  // last b with off[b] <= i
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ int det_cat(const ld_coco_batch_t& b, int j) {
   const int64_t lab = b.labels[j];
@@ -130,13 +121,6 @@ __device__ __forceinline__ void det_xywh(const float* p, double* o) {
   o[1] = (double)p[1];
   o[2] = (double)p[2] - (double)p[0];
   o[3] = (double)p[3] - (double)p[1];
-}
-
-// descending fp32 score as an ascending unsigned key (NaN-free inputs)
-__device__ __forceinline__ uint32_t desc_key(float s) {
-  uint32_t u = __float_as_uint(s == 0.0f ? 0.0f : s);  // -0 ties +0
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
 }
 
 __global__ void coco_rank_kernel(ld_coco_batch_t b, MatchParams p, int32_t* order,
@@ -420,47 +404,6 @@ __global__ void acc_keys_kernel(int n, int K, const float* score, const int32_t*
   val[i] = (uint32_t)i;
 }
 
-__device__ __forceinline__ int digit_of(uint64_t hi, uint32_t lo, int pass, int lo_passes) {
-  return pass < lo_passes ? (int)((lo >> (pass * kRadixBits)) & (kBins - 1))
-                          : (int)((hi >> ((pass - lo_passes) * kRadixBits)) & (kBins - 1));
-}
-
-__global__ __launch_bounds__(kThreads) void acc_hist_kernel(const uint64_t* hi,
-                                                           const uint32_t* lo, int n,
-                                                           int pass, int lo_passes,
-                                                           int nb, int32_t* hist) {
-  __shared__ int h[kBins];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int base = blockIdx.x * kSortTile;
-  for (int c = 0; c < kSortItems; ++c) {
-    const int i = base + c * kThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[digit_of(hi[i], lo[i], pass, lo_passes)], 1);
-  }
-  __syncthreads();
-  hist[threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive prefix sum of a 256-thread block; *total gets the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  int pre = 0, tot = 0;
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < w) pre += sh[k];
-    tot += sh[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + x - v;
-}
-
 // max over the LATER threads of the block (exclusive suffix max); -1 if none
 __device__ __forceinline__ double block_excl_suffix_max(double v, double* sh) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -487,77 +430,6 @@ __device__ __forceinline__ double block_max(double v, double* sh) {
   for (int q = 1; q < kThreads / 64; ++q) t = fmax(t, sh[q]);
   __syncthreads();
   return t;
-}
-
-// in place exclusive scan of m ints, one workgroup
-__global__ __launch_bounds__(kThreads) void acc_excl_scan_kernel(int32_t* data, int m) {
-  __shared__ int sh[kThreads / 64];
-  int carry = 0;
-  for (int base = 0; base < m; base += kSortTile) {
-    const int i0 = base + threadIdx.x * kSortItems;
-    int v[kSortItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kSortItems; ++k) {
-      v[k] = (i0 + k < m) ? data[i0 + k] : 0;
-      s += v[k];
-    }
-    int tot;
-    int run = carry + block_excl_scan(s, sh, &tot);
-#pragma unroll
-    for (int k = 0; k < kSortItems; ++k)
-      if (i0 + k < m) {
-        data[i0 + k] = run;
-        run += v[k];
-      }
-    carry += tot;
-  }
-}
-
-// stable scatter: element order = (chunk, wave, lane), ranks inside a wave from
-// the ballot match mask keep equal digits in input order
-__global__ __launch_bounds__(kThreads) void acc_scatter_kernel(
-    const uint64_t* hin, const uint32_t* lin, const uint32_t* vin, uint64_t* hout,
-    uint32_t* lout, uint32_t* vout, int n, int pass, int lo_passes, int nb,
-    const int32_t* hist) {
-  __shared__ int base[kBins];
-  __shared__ int wcnt[kThreads / 64][kBins];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  base[tid] = hist[tid * nb + blockIdx.x];
-  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (int c = 0; c < kSortItems; ++c) {
-    const int i = blockIdx.x * kSortTile + c * kThreads + tid;
-    const bool valid = i < n;
-    for (int k = 0; k < kThreads / 64; ++k) wcnt[k][tid] = 0;
-    __syncthreads();
-    const uint64_t h = valid ? hin[i] : 0ull;
-    const uint32_t l = valid ? lin[i] : 0u, v = valid ? vin[i] : 0u;
-    const int dig = digit_of(h, l, pass, lo_passes);
-    uint64_t mask = __ballot(valid);
-#pragma unroll
-    for (int bt = 0; bt < kRadixBits; ++bt) {
-      const bool on = (dig >> bt) & 1;
-      const uint64_t m = __ballot(valid && on);
-      mask &= on ? m : ~m;
-    }
-    const int rank = __popcll(mask & lt);
-    if (valid && rank == 0) wcnt[w][dig] = __popcll(mask);
-    __syncthreads();
-    int run = base[tid];
-    for (int k = 0; k < kThreads / 64; ++k) {
-      const int x = wcnt[k][tid];
-      wcnt[k][tid] = run;
-      run += x;
-    }
-    base[tid] = run;
-    __syncthreads();
-    if (valid) {
-      const int dst = wcnt[w][dig] + rank;
-      hout[dst] = h;
-      lout[dst] = l;
-      vout[dst] = v;
-    }
-    __syncthreads();
-  }
 }
 
 // one workgroup: seg_start[k] (first sorted record of category >= k, k <= K)
@@ -850,25 +722,18 @@ __global__ __launch_bounds__(kThreads) void acc_final_kernel(
   }
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct MatchPlan {
   size_t order, big, slots, total;
 };
 
 MatchPlan match_plan(int num_dets, int max_d, int max_cell_gts) {
   MatchPlan o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = off;
-    off += align_up(bytes);
-    return at;
-  };
-  o.order = take((size_t)num_dets * 4);
-  o.big = take(((size_t)num_dets + 1) * 4);
+  ldeval::Carver ws;
+  o.order = ws.take((size_t)num_dets * 4);
+  o.big = ws.take(((size_t)num_dets + 1) * 4);
   const bool may_spill = max_cell_gts > kLdsG || (long long)max_d * max_cell_gts > kLdsTile;
-  o.slots = take(may_spill ? (size_t)kSlots * max_d * max_cell_gts * 8 : 0);
-  o.total = off;
+  o.slots = ws.take(may_spill ? (size_t)kSlots * max_d * max_cell_gts * 8 : 0);
+  o.total = ws.off;
   return o;
 }
 
@@ -879,27 +744,22 @@ struct AccPlan {
 
 AccPlan acc_plan(int n, int K, int L) {
   AccPlan o{};
-  o.nb = (n + kSortTile - 1) / kSortTile;
+  o.nb = ldeval::sort_tiles(n);
   o.nt = (n + kTile - 1) / kTile + K;  // tiles never straddle categories
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = off;
-    off += align_up(bytes);
-    return at;
-  };
-  o.hi0 = take((size_t)n * 8);
-  o.hi1 = take((size_t)n * 8);
-  o.lo0 = take((size_t)n * 4);
-  o.lo1 = take((size_t)n * 4);
-  o.val0 = take((size_t)n * 4);
-  o.val1 = take((size_t)n * 4);
-  o.hist = take((size_t)kBins * o.nb * 4);
-  o.seg = take(((size_t)K + 1) * 4);
-  o.toff = take(((size_t)K + 1) * 4);
-  o.ctp = take((size_t)L * o.nt * 4);
-  o.cfp = take((size_t)L * o.nt * 4);
-  o.tmax = take((size_t)L * o.nt * 8);
-  o.total = off;
+  ldeval::Carver ws;
+  o.hi0 = ws.take((size_t)n * 8);
+  o.hi1 = ws.take((size_t)n * 8);
+  o.lo0 = ws.take((size_t)n * 4);
+  o.lo1 = ws.take((size_t)n * 4);
+  o.val0 = ws.take((size_t)n * 4);
+  o.val1 = ws.take((size_t)n * 4);
+  o.hist = ws.take((size_t)ldeval::kBins * o.nb * 4);
+  o.seg = ws.take(((size_t)K + 1) * 4);
+  o.toff = ws.take(((size_t)K + 1) * 4);
+  o.ctp = ws.take((size_t)L * o.nt * 4);
+  o.cfp = ws.take((size_t)L * o.nt * 4);
+  o.tmax = ws.take((size_t)L * o.nt * 8);
+  o.total = ws.off;
   return o;
 }
 
@@ -1105,9 +965,10 @@ int ld_coco_accumulate(int num_records, const float* rec_score, const int32_t* r
   if (workspace_bytes < o.total || (o.total && !workspace)) return LD_ENOSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  uint64_t* hi[2] = {(uint64_t*)(ws + o.hi0), (uint64_t*)(ws + o.hi1)};
-  uint32_t* lo[2] = {(uint32_t*)(ws + o.lo0), (uint32_t*)(ws + o.lo1)};
-  uint32_t* val[2] = {(uint32_t*)(ws + o.val0), (uint32_t*)(ws + o.val1)};
+  const ldeval::SortKeys<true> keys[2] = {
+      {(uint64_t*)(ws + o.hi0), (uint32_t*)(ws + o.lo0)},
+      {(uint64_t*)(ws + o.hi1), (uint32_t*)(ws + o.lo1)}};
+  uint32_t* const val[2] = {(uint32_t*)(ws + o.val0), (uint32_t*)(ws + o.val1)};
   int32_t* hist = (int32_t*)(ws + o.hist);
   int32_t* seg = (int32_t*)(ws + o.seg);
   int32_t* toff = (int32_t*)(ws + o.toff);
@@ -1120,42 +981,32 @@ int ld_coco_accumulate(int num_records, const float* rec_score, const int32_t* r
   int cur = 0;
   if (n > 0) {
     LD_LAUNCH(acc_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, K,
-              rec_score, rec_cat, rec_pos, hi[0], lo[0], val[0]);
+              rec_score, rec_cat, rec_pos, keys[0].hi, keys[0].lo, val[0]);
+    constexpr int kRadixBits = ldeval::kRadixBits;
     const int lo_passes =
         (bits_for((unsigned long long)num_all_imgs * max_det) + kRadixBits - 1) / kRadixBits;
     const int hi_passes = (32 + bits_for((unsigned long long)K + 1) + kRadixBits - 1) /
                           kRadixBits;
-    for (int pass = 0; pass < lo_passes + hi_passes; ++pass) {
-      LD_LAUNCH(acc_hist_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-                (const uint64_t*)hi[cur], (const uint32_t*)lo[cur], n, pass, lo_passes,
-                o.nb, hist);
-      LD_LAUNCH(acc_excl_scan_kernel, dim3(1), dim3(kThreads), 0, stream, hist,
-                kBins * o.nb);
-      LD_LAUNCH(acc_scatter_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-                (const uint64_t*)hi[cur], (const uint32_t*)lo[cur],
-                (const uint32_t*)val[cur], hi[cur ^ 1], lo[cur ^ 1], val[cur ^ 1], n, pass,
-                lo_passes, o.nb, (const int32_t*)hist);
-      cur ^= 1;
-    }
+    cur = ldeval::radix_sort(keys, val, n, lo_passes, hi_passes, hist, stream);
   }
   LD_LAUNCH(acc_segments_kernel, dim3(1), dim3(kThreads), 0, stream,
-            (const uint64_t*)hi[cur], n, K, seg, toff);
+            (const uint64_t*)keys[cur].hi, n, K, seg, toff);
   if (n > 0) {
     LD_LAUNCH(acc_count_kernel, dim3(o.nt), dim3(kThreads), 0, stream, p,
-              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)lo[cur],
+              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)keys[cur].lo,
               (const uint32_t*)val[cur], rec_match, rec_ign, ctp, cfp);
   }
   LD_LAUNCH(acc_prefix_kernel, dim3(1), dim3(kThreads), 0, stream, p, (const int32_t*)seg,
             (const int32_t*)toff, npig, ctp, cfp, recall);
   if (n > 0) {
     LD_LAUNCH(acc_max_kernel, dim3(o.nt), dim3(kThreads), 0, stream, p,
-              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)lo[cur],
+              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)keys[cur].lo,
               (const uint32_t*)val[cur], rec_match, rec_ign, (const int32_t*)ctp,
               (const int32_t*)cfp, tmax);
     LD_LAUNCH(acc_suffix_kernel, dim3(1), dim3(kThreads), 0, stream, p,
               (const int32_t*)toff, tmax);
     LD_LAUNCH(acc_final_kernel, dim3(o.nt), dim3(kThreads), 0, stream, p,
-              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)lo[cur],
+              (const int32_t*)seg, (const int32_t*)toff, (const uint32_t*)keys[cur].lo,
               (const uint32_t*)val[cur], rec_score, rec_match, rec_ign,
               (const int32_t*)ctp, (const int32_t*)cfp, (const double*)tmax, npig,
               precision, scores);

@@ -34,19 +34,22 @@
 #include <stdint.h>
 
 #include "../../include/ld_hip.h"
+#include "eval_common.h"
 #include "eval_iou.h"
 #include "ld_launch.h"
 
 namespace {
 
+using ldeval::block_excl_scan;
 using ldeval::box_area;
+using ldeval::desc_key;
+using ldeval::excl_scan_kernel;
+using ldeval::find_img;
 using ldeval::iou_ref;
 
-constexpr int kThreads = 256;  // 4 waves of 64
-constexpr int kItems = 16;
-constexpr int kTile = kThreads * kItems;
-constexpr int kRadixBits = 8;
-constexpr int kBins = 1 << kRadixBits;
+constexpr int kThreads = ldeval::kScanThreads;  // 4 waves of 64
+constexpr int kItems = ldeval::kScanItems;
+constexpr int kTile = ldeval::kScanTile;  // the sort's tile as well
 constexpr int kTpShift = 0;   // TP of scale k: bit k
 constexpr int kFpShift = 16;  // FP of scale k: bit 16 + k
 
@@ -56,17 +59,6 @@ struct EvalParams {
   int C, S, T, has_ranges;
   int num_imgs, num_gts;
 };
-
-__device__ __forceinline__ int find_img(const int32_t* off, int num_imgs, int i) {
-  // last b with off[b] <= i (images may be empty)
-  int lo = 0, hi = num_imgs - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
 
 __global__ void eval_match_kernel(ld_eval_batch_t b, EvalParams p, float* iou_max,
                                   int* argmax) {
@@ -154,13 +146,6 @@ __global__ void eval_count_gts_kernel(ld_eval_batch_t b, EvalParams p, int32_t* 
 }
 
 // ------------------------------------------------------------ sort ------
-// descending score as an ascending unsigned key (NaN-free inputs assumed)
-__device__ __forceinline__ uint32_t desc_key(float s) {
-  uint32_t u = __float_as_uint(s == 0.0f ? 0.0f : s);  // -0 ties +0
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ~u;
-}
-
 __global__ void eval_keys_kernel(int n, const float* score, const int32_t* seg,
                                  const uint32_t* bits, int num_segs, uint64_t* keys,
                                  uint32_t* vals) {
@@ -169,111 +154,6 @@ __global__ void eval_keys_kernel(int n, const float* score, const int32_t* seg,
   uint32_t s = (uint32_t)min(max(seg[i], 0), num_segs);
   keys[i] = ((uint64_t)s << 32) | desc_key(score[i]);
   vals[i] = bits[i];
-}
-
-__global__ __launch_bounds__(kThreads) void radix_hist_kernel(const uint64_t* keys, int n,
-                                                             int shift, int nb,
-                                                             int32_t* hist) {
-  __shared__ int h[kBins];
-  h[threadIdx.x] = 0;
-  __syncthreads();
-  const int base = blockIdx.x * kTile;
-  for (int c = 0; c < kItems; ++c) {
-    int i = base + c * kThreads + threadIdx.x;
-    if (i < n) atomicAdd(&h[(keys[i] >> shift) & (kBins - 1)], 1);
-  }
-  __syncthreads();
-  hist[threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
-}
-
-// exclusive prefix sum of a 256-thread block; *total gets the block's sum
-__device__ __forceinline__ int block_excl_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    int y = __shfl_up(x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) sh[w] = x;
-  __syncthreads();
-  int pre = 0, tot = 0;
-  for (int k = 0; k < kThreads / 64; ++k) {
-    if (k < w) pre += sh[k];
-    tot += sh[k];
-  }
-  __syncthreads();
-  *total = tot;
-  return pre + x - v;
-}
-
-// in place exclusive scan of m ints, one workgroup per row (blockIdx.y)
-__global__ __launch_bounds__(kThreads) void excl_scan_kernel(int32_t* data, int m) {
-  __shared__ int sh[kThreads / 64];
-  int32_t* row = data + (size_t)blockIdx.y * m;
-  int carry = 0;
-  for (int base = 0; base < m; base += kTile) {
-    const int i0 = base + threadIdx.x * kItems;
-    int v[kItems], s = 0;
-#pragma unroll
-    for (int k = 0; k < kItems; ++k) {
-      v[k] = (i0 + k < m) ? row[i0 + k] : 0;
-      s += v[k];
-    }
-    int tot;
-    int run = carry + block_excl_scan(s, sh, &tot);
-#pragma unroll
-    for (int k = 0; k < kItems; ++k)
-      if (i0 + k < m) {
-        row[i0 + k] = run;
-        run += v[k];
-      }
-    carry += tot;
-  }
-}
-
-// stable scatter: element order = (chunk, wave, lane), so ranks inside a wave
-// from the ballot match mask keep equal digits in input order
-__global__ __launch_bounds__(kThreads) void radix_scatter_kernel(
-    const uint64_t* kin, const uint32_t* vin, uint64_t* kout, uint32_t* vout, int n,
-    int shift, int nb, const int32_t* hist) {
-  __shared__ int base[kBins];
-  __shared__ int wcnt[kThreads / 64][kBins];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  base[tid] = hist[tid * nb + blockIdx.x];
-  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (int c = 0; c < kItems; ++c) {
-    const int i = blockIdx.x * kTile + c * kThreads + tid;
-    const bool valid = i < n;
-    for (int k = 0; k < kThreads / 64; ++k) wcnt[k][tid] = 0;
-    __syncthreads();
-    uint64_t key = valid ? kin[i] : 0ull;
-    uint32_t val = valid ? vin[i] : 0u;
-    const int dig = (int)((key >> shift) & (kBins - 1));
-    uint64_t mask = __ballot(valid);
-#pragma unroll
-    for (int bt = 0; bt < kRadixBits; ++bt) {
-      const bool on = (dig >> bt) & 1;
-      uint64_t m = __ballot(valid && on);
-      mask &= on ? m : ~m;
-    }
-    const int rank = __popcll(mask & lt);
-    if (valid && rank == 0) wcnt[w][dig] = __popcll(mask);
-    __syncthreads();
-    int run = base[tid];
-    for (int k = 0; k < kThreads / 64; ++k) {
-      int x = wcnt[k][tid];
-      wcnt[k][tid] = run;
-      run += x;
-    }
-    base[tid] = run;
-    __syncthreads();
-    if (valid) {
-      const int dst = wcnt[w][dig] + rank;
-      kout[dst] = key;
-      vout[dst] = val;
-    }
-    __syncthreads();
-  }
 }
 
 __global__ void seg_start_kernel(const uint64_t* keys, int n, int num_segs,
@@ -477,25 +357,18 @@ struct ApPlan {
   int nb;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 ApPlan ap_plan(int n, int S) {
   ApPlan o{};
-  o.nb = (n + kTile - 1) / kTile;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = off;
-    off += align_up(bytes);
-    return at;
-  };
-  o.keys0 = take((size_t)n * 8);
-  o.keys1 = take((size_t)n * 8);
-  o.vals0 = take((size_t)n * 4);
-  o.vals1 = take((size_t)n * 4);
-  o.hist = take((size_t)kBins * o.nb * 4);
-  o.bsum = take((size_t)2 * S * o.nb * 4);
-  o.cum = take((size_t)2 * S * n * 4);
-  o.total = off;
+  o.nb = ldeval::sort_tiles(n);
+  ldeval::Carver ws;
+  o.keys0 = ws.take((size_t)n * 8);
+  o.keys1 = ws.take((size_t)n * 8);
+  o.vals0 = ws.take((size_t)n * 4);
+  o.vals1 = ws.take((size_t)n * 4);
+  o.hist = ws.take((size_t)ldeval::kBins * o.nb * 4);
+  o.bsum = ws.take((size_t)2 * S * o.nb * 4);
+  o.cum = ws.take((size_t)2 * S * n * 4);
+  o.total = ws.off;
   return o;
 }
 
@@ -525,7 +398,7 @@ extern "C" {
 
 size_t ld_eval_tpfp_workspace_bytes(int num_dets) {
   if (num_dets < 0) return 0;
-  return align_up((size_t)num_dets * 4) * 2 + 256;
+  return ldeval::align_up((size_t)num_dets * 4) * 2 + 256;
 }
 
 int ld_eval_tpfp(const ld_eval_batch_t* b, int num_classes, int num_scales,
@@ -554,7 +427,7 @@ int ld_eval_tpfp(const ld_eval_batch_t* b, int num_classes, int num_scales,
   hipStream_t stream = (hipStream_t)stream_;
   const int N = b->num_dets;
   float* iou_max = (float*)workspace;
-  int* argmax = (int*)((char*)workspace + align_up((size_t)N * 4));
+  int* argmax = (int*)((char*)workspace + ldeval::align_up((size_t)N * 4));
   if (b->num_gts > 0)
     LD_LAUNCH(eval_count_gts_kernel, dim3((b->num_gts + 255) / 256), dim3(256), 0, stream,
               *b, p, num_gts);
@@ -593,39 +466,32 @@ int ld_eval_ap(int num_records, const float* rec_score, const int32_t* rec_seg,
   const int S = num_scales, C = num_classes, num_segs = num_thrs * num_classes;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  uint64_t* keys[2] = {(uint64_t*)(ws + o.keys0), (uint64_t*)(ws + o.keys1)};
-  uint32_t* vals[2] = {(uint32_t*)(ws + o.vals0), (uint32_t*)(ws + o.vals1)};
+  const ldeval::SortKeys<false> keys[2] = {{(uint64_t*)(ws + o.keys0)},
+                                           {(uint64_t*)(ws + o.keys1)}};
+  uint32_t* const vals[2] = {(uint32_t*)(ws + o.vals0), (uint32_t*)(ws + o.vals1)};
   int32_t* hist = (int32_t*)(ws + o.hist);
   int32_t* bsum = (int32_t*)(ws + o.bsum);
   int32_t* cum = (int32_t*)(ws + o.cum);
   int cur = 0;
   if (n > 0) {
     LD_LAUNCH(eval_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, rec_score,
-              rec_seg, rec_bits, num_segs, keys[0], vals[0]);
+              rec_seg, rec_bits, num_segs, keys[0].hi, vals[0]);
     int seg_bits = 0;
     while ((1 << seg_bits) <= num_segs) ++seg_bits;  // num_segs itself: the sentinel
-    const int passes = (32 + seg_bits + kRadixBits - 1) / kRadixBits;
-    for (int pass = 0; pass < passes; ++pass) {
-      const int shift = pass * kRadixBits;
-      LD_LAUNCH(radix_hist_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-                (const uint64_t*)keys[cur], n, shift, o.nb, hist);
-      LD_LAUNCH(excl_scan_kernel, dim3(1), dim3(kThreads), 0, stream, hist, kBins * o.nb);
-      LD_LAUNCH(radix_scatter_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-                (const uint64_t*)keys[cur], (const uint32_t*)vals[cur], keys[cur ^ 1],
-                vals[cur ^ 1], n, shift, o.nb, (const int32_t*)hist);
-      cur ^= 1;
-    }
+    const int passes = (32 + seg_bits + ldeval::kRadixBits - 1) / ldeval::kRadixBits;
+    cur = ldeval::radix_sort(keys, vals, n, 0, passes, hist, stream);
   }
   LD_LAUNCH(seg_start_kernel, dim3((num_segs + 1 + 255) / 256), dim3(256), 0, stream,
-            (const uint64_t*)keys[cur], n, num_segs, seg_start);
+            (const uint64_t*)keys[cur].hi, n, num_segs, seg_start);
   if (n > 0) {
     LD_LAUNCH(bit_count_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
               (const uint32_t*)vals[cur], n, S, o.nb, bsum);
-    LD_LAUNCH(excl_scan_kernel, dim3(1, 2 * S), dim3(kThreads), 0, stream, bsum, o.nb);
+    LD_LAUNCH(excl_scan_kernel<int32_t>, dim3(1, 2 * S), dim3(kThreads), 0, stream, bsum,
+              o.nb);
     LD_LAUNCH(bit_scan_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
               (const uint32_t*)vals[cur], n, S, o.nb, (const int32_t*)bsum, cum);
     LD_LAUNCH(pr_kernel, dim3((n * S + 255) / 256), dim3(256), 0, stream,
-              (const uint64_t*)keys[cur], n, S, C, num_segs, (const int32_t*)seg_start,
+              (const uint64_t*)keys[cur].hi, n, S, C, num_segs, (const int32_t*)seg_start,
               (const int32_t*)cum, num_gts, recall, precision);
   }
   LD_LAUNCH(ap_kernel, dim3(num_segs * S), dim3(kThreads), 0, stream, n, S, num_segs,
@@ -649,21 +515,14 @@ int ld_rank_images(int num_imgs, const double* scores, int32_t* order, double* s
   if (workspace_bytes < o.total || !workspace) return LD_ENOSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)workspace;
-  uint64_t* keys[2] = {(uint64_t*)(ws + o.keys0), (uint64_t*)(ws + o.keys1)};
-  uint32_t* vals[2] = {(uint32_t*)(ws + o.vals0), (uint32_t*)(ws + o.vals1)};
+  const ldeval::SortKeys<false> keys[2] = {{(uint64_t*)(ws + o.keys0)},
+                                           {(uint64_t*)(ws + o.keys1)}};
+  uint32_t* const vals[2] = {(uint32_t*)(ws + o.vals0), (uint32_t*)(ws + o.vals1)};
   int32_t* hist = (int32_t*)(ws + o.hist);
   LD_LAUNCH(rank_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, scores,
-            keys[0], vals[0]);
-  int cur = 0;
-  for (int shift = 0; shift < 64; shift += kRadixBits) {
-    LD_LAUNCH(radix_hist_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-              (const uint64_t*)keys[cur], n, shift, o.nb, hist);
-    LD_LAUNCH(excl_scan_kernel, dim3(1), dim3(kThreads), 0, stream, hist, kBins * o.nb);
-    LD_LAUNCH(radix_scatter_kernel, dim3(o.nb), dim3(kThreads), 0, stream,
-              (const uint64_t*)keys[cur], (const uint32_t*)vals[cur], keys[cur ^ 1],
-              vals[cur ^ 1], n, shift, o.nb, (const int32_t*)hist);
-    cur ^= 1;
-  }
+            keys[0].hi, vals[0]);
+  const int cur =
+      ldeval::radix_sort(keys, vals, n, 0, 64 / ldeval::kRadixBits, hist, stream);
   LD_LAUNCH(rank_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n,
             (const uint32_t*)vals[cur], scores, order, sorted);
   return (int)hipGetLastError();

@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "../../include/ld_hip.h"
+#include "eval_common.h"
 #include "eval_iou.h"
 #include "ld_launch.h"
 
@@ -123,25 +124,18 @@ struct ImgPlan {
   size_t iou, arg, prev, order, prec, ctp, term, total;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 ImgPlan img_plan(int num_dets, int num_imgs) {
   ImgPlan o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = off;
-    off += align_up(bytes);
-    return at;
-  };
+  ldeval::Carver ws;
   const size_t N = (size_t)num_dets;
-  o.iou = take(N * 4);
-  o.arg = take(N * 4);
-  o.prev = take(N * 4);
-  o.order = take(N * 4);
-  o.prec = take(N * 4 * kWaves);
-  o.ctp = take(N * 4 * kWaves);
-  o.term = take((N + (size_t)num_imgs) * 8 * kWaves);  // one closing step per class
-  o.total = off;
+  o.iou = ws.take(N * 4);
+  o.arg = ws.take(N * 4);
+  o.prev = ws.take(N * 4);
+  o.order = ws.take(N * 4);
+  o.prec = ws.take(N * 4 * kWaves);
+  o.ctp = ws.take(N * 4 * kWaves);
+  o.term = ws.take((N + (size_t)num_imgs) * 8 * kWaves);  // one closing step per class
+  o.total = ws.off;
   return o;
 }
 

@@ -1,6 +1,6 @@
-// The IoU of the mAP evaluation (eval.hip, eval_image.hip): bbox_overlaps.py in
-// fp32, in the reference's op order.  Include only from files compiled with
-// -ffp-contract=off.
+// The fp32 IoU of the evaluation family (eval.hip, eval_image.hip, recall.hip):
+// bbox_overlaps.py in the reference's op order.  Include only from files compiled
+// with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 

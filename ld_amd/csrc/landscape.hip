@@ -41,6 +41,7 @@
 #include <stdint.h>
 
 #include "../../include/ld_hip.h"
+#include "eval_common.h"
 #include "ld_launch.h"
 
 namespace {
@@ -264,8 +265,6 @@ __global__ __launch_bounds__(64) void levels_pearson_sum_kernel(const double* __
   }
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int abs_err_plan(Segs& sg, const ld_levels_t* lv, int N, int C, int P, int& slices) {
   if (N <= 0 || C <= 0) return LD_EINVAL;
   const int rc = fill_segs(sg, lv, P);
@@ -324,7 +323,7 @@ size_t ld_levels_abs_err_workspace_bytes(const ld_levels_t* lv, int N, int C, in
   Segs sg{};
   int slices = 0;
   if (abs_err_plan(sg, lv, N, C, P, slices)) return 0;
-  return align_up((size_t)N * slices * sg.total * sizeof(double)) + 256;
+  return ldeval::align_up((size_t)N * slices * sg.total * sizeof(double)) + 256;
 }
 
 int ld_levels_abs_err(const ld_levels_t* lv, const float* t, const float* s, int N, int C,
@@ -349,7 +348,7 @@ int ld_levels_abs_err(const ld_levels_t* lv, const float* t, const float* s, int
 size_t ld_levels_pearson_workspace_bytes(const ld_levels_t* lv, int N, int C, int P) {
   Segs sg{};
   if (pearson_plan(sg, lv, N, C, P)) return 0;
-  return align_up((size_t)N * sg.L * C * sizeof(double)) + 256;
+  return ldeval::align_up((size_t)N * sg.L * C * sizeof(double)) + 256;
 }
 
 int ld_levels_pearson(const ld_levels_t* lv, const float* t, const float* s, int N, int C,

@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "../../include/ld_hip.h"
+#include "eval_common.h"
 #include "eval_iou.h"
 #include "ld_launch.h"
 
@@ -42,6 +43,7 @@ namespace {
 
 using ldeval::box_area;
 using ldeval::iou_ref;
+using ldeval::order_key;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -60,32 +62,17 @@ struct RecallPlan {
   size_t tile, order, dead, rmax, rarg, rdead, total;
 };
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 RecallPlan recall_plan(long long num_props, long long num_gts, long long cap_k) {
   RecallPlan o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t at = off;
-    off += align_up(bytes);
-    return at;
-  };
-  o.tile = take((size_t)num_gts * (size_t)cap_k * 4);
-  o.order = take((size_t)num_props * 4);
-  o.dead = take((size_t)num_props);
-  o.rmax = take((size_t)num_gts * 4);
-  o.rarg = take((size_t)num_gts * 4);
-  o.rdead = take((size_t)num_gts);
-  o.total = off;
+  ldeval::Carver ws;
+  o.tile = ws.take((size_t)num_gts * (size_t)cap_k * 4);
+  o.order = ws.take((size_t)num_props * 4);
+  o.dead = ws.take((size_t)num_props);
+  o.rmax = ws.take((size_t)num_gts * 4);
+  o.rarg = ws.take((size_t)num_gts * 4);
+  o.rdead = ws.take((size_t)num_gts);
+  o.total = ws.off;
   return o;
-}
-
-// descending-score order as a strict total order: sign-flipped bits (0.0 and
-// -0.0 are one score; NaN sorts first, as argsort()[::-1] leaves it)
-__device__ __forceinline__ uint32_t score_key(float s) {
-  if (s == 0.0f) s = 0.0f;
-  const uint32_t u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 // maximum and lowest column holding it over the live columns [0, kp) of a row;
@@ -145,14 +132,14 @@ __global__ __launch_bounds__(kThreads) void recall_match_kernel(
     uint32_t* s_key = (uint32_t*)s_tile;
     for (int i0 = 0; i0 < K; i0 += kThreads) {
       const int i = i0 + tid;
-      const uint32_t ki = i < K ? score_key(pr[(size_t)i * 5 + 4]) : 0u;
+      const uint32_t ki = i < K ? order_key(pr[(size_t)i * 5 + 4]) : 0u;
       int pos = 0;
       for (int c0 = 0; c0 < K; c0 += kTile) {
         const int n = min(kTile, K - c0);
         if (i0 == 0 || K > kTile) {  // one chunk stays; more are staged again
           __syncthreads();
           for (int j = tid; j < n; j += kThreads)
-            s_key[j] = score_key(pr[(size_t)(c0 + j) * 5 + 4]);
+            s_key[j] = order_key(pr[(size_t)(c0 + j) * 5 + 4]);
           __syncthreads();
         }
         if (i < K)

@@ -21,6 +21,9 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .eval_common import (RecordBuffers, check_one_rank, eval_batch,
+                          eval_device, eval_logger, pack_det_gt_batch,
+                          results_to_lists)
 from .lossblock import workspace
 
 __all__ = ['eval_map', 'MapAccumulator']
@@ -39,17 +42,6 @@ def _refuse_tpfp(dataset, tpfp_fn):
             'does not implement')
 
 
-def _f32(x, dev, shape_last):
-    t = torch.as_tensor(x)
-    if t.numel() == 0:
-        t = t.reshape(0, shape_last)
-    return t.to(device=dev, dtype=torch.float32).reshape(-1, shape_last)
-
-
-def _i64(x, dev):
-    return torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1)
-
-
 def eval_tpfp(batch, num_classes, area_ranges, iou_thrs, rec_score, rec_seg,
               rec_bits, num_gts):
     """ld_eval_tpfp on packed device tensors (see include/ld_hip.h).
@@ -58,14 +50,7 @@ def eval_tpfp(batch, num_classes, area_ranges, iou_thrs, rec_score, rec_seg,
     fill (num_dets * len(iou_thrs) each)."""
     lib = L.get_lib()
     dev = batch['det_off'].device
-    b = L.EvalBatchT()
-    for k in ('dets', 'det_labels', 'det_off', 'gts', 'gt_labels', 'gt_off',
-              'ign', 'ign_labels', 'ign_off'):
-        setattr(b, k, L.ptr(batch[k]).value)
-    b.num_imgs = batch['det_off'].numel() - 1
-    b.num_dets = batch['dets'].shape[0]
-    b.num_gts = batch['gts'].shape[0]
-    b.num_ign = batch['ign'].shape[0]
+    b = eval_batch(batch)
     S = 1 if area_ranges is None else len(area_ranges)
     ar = None
     if area_ranges is not None:
@@ -138,31 +123,15 @@ class MapAccumulator:
             [(np.float32(rg[0]**2), np.float32(rg[1]**2))
              for rg in self.scale_ranges]
         self.dataset = dataset
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        if self.device.type != 'cuda':
-            raise L.LdError(f'MapAccumulator: device {self.device} is not a HIP '
-                            'device (there is no CPU path)')
+        self.device = eval_device(device, 'MapAccumulator')
         S = 1 if self.scale_ranges is None else len(self.scale_ranges)
         self.num_scales = S
         self.num_gts = torch.zeros(self.num_classes * S, dtype=torch.int32,
                                    device=self.device)
         self.num_imgs = 0
-        self._n = 0  # records written
-        self._score = torch.empty(0, dtype=torch.float32, device=self.device)
-        self._seg = torch.empty(0, dtype=torch.int32, device=self.device)
-        self._bits = torch.empty(0, dtype=torch.int32, device=self.device)
-
-    def _reserve(self, extra):
-        need = self._n + extra
-        if need <= self._score.numel():
-            return
-        cap = max(need, 2 * self._score.numel(), 1 << 12)
-        for name in ('_score', '_seg', '_bits'):
-            old = getattr(self, name)
-            new = torch.empty(cap, dtype=old.dtype, device=self.device)
-            new[:self._n] = old[:self._n]
-            setattr(self, name, new)
+        self._rec = RecordBuffers(
+            dict(score=torch.float32, seg=torch.int32, bits=torch.int32),
+            self.device, 1 << 12)
 
     def add(self, dets, labels, gt_bboxes, gt_labels, gt_bboxes_ignore=None,
             gt_labels_ignore=None):
@@ -171,88 +140,26 @@ class MapAccumulator:
         -- and GTs (g, 4) / (g,), optionally ignored GTs (k, 4) / (k,).  Boxes
         are compared in fp32.  Detection labels outside [0, num_classes) are
         not scored."""
-        B = len(dets)
-        if not (len(labels) == len(gt_bboxes) == len(gt_labels) == B):
-            raise ValueError('MapAccumulator.add: dets, labels, gt_bboxes and '
-                             'gt_labels need one entry per image')
-        if (gt_bboxes_ignore is None) != (gt_labels_ignore is None):
-            raise ValueError('MapAccumulator.add: gt_bboxes_ignore and '
-                             'gt_labels_ignore go together')
-        if gt_bboxes_ignore is not None and not \
-                len(gt_bboxes_ignore) == len(gt_labels_ignore) == B:
-            raise ValueError('MapAccumulator.add: one ignored-GT entry per '
-                             'image')
-        if B == 0:
+        batch = pack_det_gt_batch(
+            'MapAccumulator.add', ('dets', 'labels'), dets, labels, gt_bboxes,
+            gt_labels, gt_bboxes_ignore, gt_labels_ignore, self.device)
+        if batch is None:
             return
-        dev = self.device
-        d = [_f32(x, dev, 5) for x in dets]
-        dl = [_i64(x, dev) for x in labels]
-        g = [_f32(x, dev, 4) for x in gt_bboxes]
-        gl = [_i64(x, dev) for x in gt_labels]
-        if gt_bboxes_ignore is None:
-            ig = [torch.zeros((0, 4), dtype=torch.float32, device=dev)] * B
-            il = [torch.zeros((0, ), dtype=torch.int64, device=dev)] * B
-        else:
-            ig = [_f32(x, dev, 4) for x in gt_bboxes_ignore]
-            il = [_i64(x, dev) for x in gt_labels_ignore]
-        for a, b, what in ((d, dl, 'detections'), (g, gl, 'GTs'),
-                           (ig, il, 'ignored GTs')):
-            for x, y in zip(a, b):
-                if x.shape[0] != y.shape[0]:
-                    raise ValueError(f'MapAccumulator.add: {what} and their '
-                                     'labels differ in length')
-
-        def pack(rows):
-            off = np.zeros(B + 1, dtype=np.int32)
-            off[1:] = np.cumsum([r.shape[0] for r in rows])
-            return torch.cat(rows).contiguous(), \
-                torch.from_numpy(off).to(dev)
-
-        batch = {}
-        batch['dets'], batch['det_off'] = pack(d)
-        batch['det_labels'] = torch.cat(dl).contiguous()
-        batch['gts'], batch['gt_off'] = pack(g)
-        batch['gt_labels'] = torch.cat(gl).contiguous()
-        batch['ign'], batch['ign_off'] = pack(ig)
-        batch['ign_labels'] = torch.cat(il).contiguous()
-        N = batch['dets'].shape[0]
-        T = len(self.iou_thrs)
-        self._reserve(N * T)
-        lo, hi = self._n, self._n + N * T
+        rec = self._rec
+        R = batch['dets'].shape[0] * len(self.iou_thrs)
+        rec.reserve(R)
+        new = rec.views(rec.n, rec.n + R)
         eval_tpfp(batch, self.num_classes, self.area_ranges, self.iou_thrs,
-                  self._score[lo:hi], self._seg[lo:hi], self._bits[lo:hi],
-                  self.num_gts)
-        self._n = hi
-        self.num_imgs += B
+                  new['score'], new['seg'], new['bits'], self.num_gts)
+        rec.n += R
+        self.num_imgs += batch['det_off'].numel() - 1
 
     def add_results(self, det_results, annotations):
         """The reference's form: ``det_results[i][c]`` (k, 5) arrays per image
         and class, ``annotations[i]`` dicts of ``bboxes`` / ``labels`` and
         optional ``bboxes_ignore`` / ``labels_ignore`` (numpy or tensors)."""
-        if len(det_results) != len(annotations):
-            raise ValueError('add_results: one annotation per image')
-        dets, labels, gb, gl, ib, il = [], [], [], [], [], []
-        for res, ann in zip(det_results, annotations):
-            if len(res) != self.num_classes:
-                raise ValueError(f'add_results: {len(res)} class arrays, '
-                                 f'expected {self.num_classes}')
-            rows = [torch.as_tensor(np.asarray(r, dtype=np.float32)).reshape(
-                -1, 5) for r in res]
-            dets.append(torch.cat(rows))
-            labels.append(torch.cat([
-                torch.full((r.shape[0], ), c, dtype=torch.int64)
-                for c, r in enumerate(rows)]))
-            gb.append(np.asarray(ann['bboxes'], dtype=np.float32).reshape(-1, 4))
-            gl.append(np.asarray(ann['labels']).reshape(-1))
-            # get_cls_results (mean_ap.py:258-262): labels_ignore decides
-            if ann.get('labels_ignore', None) is not None:
-                ib.append(np.asarray(ann['bboxes_ignore'],
-                                     dtype=np.float32).reshape(-1, 4))
-                il.append(np.asarray(ann['labels_ignore']).reshape(-1))
-            else:
-                ib.append(np.zeros((0, 4), dtype=np.float32))
-                il.append(np.zeros((0, ), dtype=np.int64))
-        self.add(dets, labels, gb, gl, ib, il)
+        self.add(*results_to_lists(det_results, annotations,
+                                   self.num_classes))
 
     def records(self):
         """The TP/FP records written so far, in the order they were added
@@ -260,29 +167,25 @@ class MapAccumulator:
         innermost) -> host (threshold (R,), class (R,), score (R,), tp (S, R),
         fp (S, R)); class -1 marks a label outside [0, num_classes)."""
         C_, S = self.num_classes, self.num_scales
-        seg = self._seg[:self._n].cpu().numpy().astype(np.int64)
-        bits = self._bits[:self._n].cpu().numpy().view(np.uint32)
+        rec = self._rec.views()
+        seg = rec['seg'].cpu().numpy().astype(np.int64)
+        bits = rec['bits'].cpu().numpy().view(np.uint32)
         valid = seg < len(self.iou_thrs) * C_
         k = np.arange(S, dtype=np.uint32)[:, None]
         tp = ((bits[None] >> k) & 1).astype(np.uint8)
         fp = ((bits[None] >> (k + 16)) & 1).astype(np.uint8)
         return (np.where(valid, seg // C_, -1), np.where(valid, seg % C_, -1),
-                self._score[:self._n].cpu().numpy(), tp, fp)
+                rec['score'].cpu().numpy(), tp, fp)
 
     def compute(self, logger=None):
         """-> one ``(mean_ap, eval_results)`` per IoU threshold, shaped as the
         reference's ``eval_map`` returns them."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and \
-                dist.get_world_size() > 1:
-            raise NotImplementedError(
-                'MapAccumulator.compute: results are not gathered across '
-                f'ranks (world size {dist.get_world_size()}); evaluate on one '
-                'rank, or gather the detections there first')
+        check_one_rank('MapAccumulator.compute')
         T, C_, S = len(self.iou_thrs), self.num_classes, self.num_scales
+        rec = self._rec.views()
         seg_start, recall, precision, ap = eval_ap(
-            self._score[:self._n], self._seg[:self._n], self._bits[:self._n],
-            C_, T, S, self.num_gts, self.dataset == 'voc07')
+            rec['score'], rec['seg'], rec['bits'], C_, T, S, self.num_gts,
+            self.dataset == 'voc07')
         seg_start = seg_start.cpu().numpy().astype(np.int64)
         recall, precision = recall.cpu().numpy(), precision.cpu().numpy()
         ap = ap.cpu().numpy()
@@ -344,8 +247,7 @@ def _summary(mean_ap, eval_results, iou_thr, area_ranges, logger):
     """Plain-text stand-in for print_map_summary (mean_ap.py:405-470)."""
     if logger == 'silent':
         return
-    log = logger if isinstance(logger, logging.Logger) else \
-        logging.getLogger(logger) if isinstance(logger, str) else _LOG
+    log = eval_logger(logger, _LOG)
     S = 1 if area_ranges is None else len(area_ranges)
     lines = [f'mAP @ IoU {iou_thr}']
     for k in range(S):

@@ -40,6 +40,7 @@ import torch
 from . import lib as L
 from .coco_eval import (METRIC_NAMES, CocoEvaluator, CocoGroundTruth,
                         default_iou_thrs)
+from .eval_common import ADD_STEP, eval_device, eval_logger, pack_rows
 from .lossblock import workspace
 
 __all__ = ['set_recall_param', 'RecallAccumulator', 'eval_recalls',
@@ -66,23 +67,6 @@ def set_recall_param(proposal_nums, iou_thrs):
             _as_array(iou_thrs, float, np.array([0.5])))
 
 
-def _device(device):
-    dev = torch.device(device) if device is not None else \
-        torch.device('cuda', torch.cuda.current_device())
-    if dev.type != 'cuda':
-        raise L.LdError(f'recall: device {dev} is not a HIP device '
-                        '(there is no CPU path)')
-    return dev
-
-
-def _log(logger):
-    if isinstance(logger, logging.Logger):
-        return logger
-    if isinstance(logger, str) and logger != 'silent':
-        return logging.getLogger(logger)
-    return _LOG
-
-
 class RecallAccumulator:
     """Streaming ``eval_recalls``: ``add`` batches of images, then ``compute``
     / ``evaluate``.  ``proposal_nums`` and ``iou_thrs`` take what
@@ -107,7 +91,7 @@ class RecallAccumulator:
                              f'thresholds, got {thrs.size}')
         self.proposal_nums = nums.astype(np.int64)
         self.iou_thrs = thrs
-        self.device = _device(device)
+        self.device = eval_device(device, 'recall')
         self._no_lds = False  # tests: every image through the workspace route
         self.num_imgs = 0
         self.total_gt = 0
@@ -169,26 +153,17 @@ class RecallAccumulator:
                                  f'(n, 4), got {tuple(t.shape)}')
             gts.append(t.to(device=dev, dtype=torch.float32))
 
-        def pack(rows):
-            off = np.zeros(B + 1, dtype=np.int64)
-            off[1:] = np.cumsum([r.shape[0] for r in rows])
-            if off[-1] >= 2 ** 31:
-                raise L.LdError('RecallAccumulator.add: batch too large')
-            return torch.cat(rows).contiguous(), off
-
-        p, poff = pack(props)
-        g, goff = pack(gts)
-        N, G = int(poff[-1]), int(goff[-1])
+        p, poff_d, pcounts = pack_rows(props, dev, 'RecallAccumulator.add')
+        g, goff_d, gcounts = pack_rows(gts, dev, 'RecallAccumulator.add')
+        N, G = sum(pcounts), sum(gcounts)
         if G == 0:  # no row of the table belongs to these images
             self.num_imgs += B
             return
-        max_k = int(np.diff(poff).max())
+        max_k = max(pcounts)
         self._reserve(G)
         lib = L.get_lib()
         P = len(self.proposal_nums)
         nums = (L.C.c_int32 * P)(*self.proposal_nums.tolist())
-        poff_d = torch.from_numpy(poff.astype(np.int32)).to(dev)
-        goff_d = torch.from_numpy(goff.astype(np.int32)).to(dev)
         need = lib.ld_eval_recalls_workspace_bytes(
             N, G, max_k, int(self.proposal_nums[-1]))
         if need == 0:
@@ -251,9 +226,6 @@ class RecallAccumulator:
         return eval_results
 
 
-_ADD_STEP = 512  # images per launch of the list interfaces
-
-
 def eval_recalls(gts, proposals, proposal_nums=None, iou_thrs=0.5,
                  logger=None, device=None):
     """The reference's ``eval_recalls`` (recall.py:64-106) on the device:
@@ -262,8 +234,8 @@ def eval_recalls(gts, proposals, proposal_nums=None, iou_thrs=0.5,
     img_num = len(gts)
     assert img_num == len(proposals)
     acc = RecallAccumulator(proposal_nums, iou_thrs, device)
-    for i in range(0, img_num, _ADD_STEP):
-        acc.add(proposals[i:i + _ADD_STEP], gts[i:i + _ADD_STEP])
+    for i in range(0, img_num, ADD_STEP):
+        acc.add(proposals[i:i + ADD_STEP], gts[i:i + ADD_STEP])
     recalls = acc.compute()
     print_recall_summary(recalls, acc.proposal_nums, acc.iou_thrs,
                          logger=logger)
@@ -289,7 +261,7 @@ def print_recall_summary(recalls, proposal_nums, iou_thrs, row_idxs=None,
     text = '\n'.join(' '.join(cell.rjust(w) for cell, w in zip(line, widths))
                      for line in cells)
     if logger != 'silent':
-        _log(logger).info('\n' + text)
+        eval_logger(logger, _LOG).info('\n' + text)
     return text
 
 
@@ -408,7 +380,7 @@ class CocoProposalEvaluator:
         self.gt = gt
         self.proposal_nums = proposal_nums
         self.iou_thrs = default_iou_thrs() if iou_thrs is None else iou_thrs
-        self.device = _device(device)
+        self.device = eval_device(device, 'recall')
         self._fast = self._coco = None
         self._next = 0
         if 'proposal_fast' in self.metrics:
@@ -449,7 +421,7 @@ class CocoProposalEvaluator:
         ``AR@100 ... AR_l@1000``)."""
         if metric_items is not None and not isinstance(metric_items, list):
             metric_items = [metric_items]
-        log = _log(logger)
+        log = eval_logger(logger, _LOG)
         eval_results = OrderedDict()
         for m in self.metrics:
             if m == 'proposal_fast':
@@ -495,6 +467,6 @@ def coco_proposal_evaluate(results, gt, metric='proposal_fast',
                          f'for {len(gt.img_ids)} images')
     ev = CocoProposalEvaluator(gt, metric, proposal_nums, iou_thrs, device)
     dets = [_image_dets(r) for r in results]
-    for i in range(0, len(dets), _ADD_STEP):
-        ev.add(range(i, min(i + _ADD_STEP, len(dets))), dets[i:i + _ADD_STEP])
+    for i in range(0, len(dets), ADD_STEP):
+        ev.add(range(i, min(i + ADD_STEP, len(dets))), dets[i:i + ADD_STEP])
     return ev.evaluate(metric_items, logger)

@@ -100,7 +100,8 @@ def test_rank_images_is_stable():
     order, as sorted() on the reference's dict items does."""
     from ld_amd import analyze_results as A
     rng = np.random.RandomState(1)
-    for n in (1, 2, 255, 5000, 9000):
+    # 4096 is one tile of the sort: one tile exactly, one over, two tiles
+    for n in (1, 2, 255, 4095, 4096, 4097, 5000, 8192, 8193, 9000):
         s = rng.randint(0, 7, size=n) / 6.0
         s[::5] = -0.0
         order, out = A.rank_images(torch.from_numpy(s).cuda())
