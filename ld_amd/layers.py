@@ -257,6 +257,48 @@ def WGRAD_C8_ON():
         os.environ.get('LD_STUDENT_C8_ONLY', '1') == '1'
 
 
+def _switch(name, default='1'):
+    """A mutable on/off cell read from the environment once, at import."""
+    return [os.environ.get(name, default) == '1']
+
+
+_FUSE_CONV_BN = _switch('LD_FUSE_CONV_BN')  # conv + eval-BN as one node
+_PAD_DGRAD = _switch('LD_PAD_DGRAD')  # bf16 dgrad of a Cout % 16 != 0 conv
+_BN_BWD_C8 = _switch('LD_BN_BWD_C8')  # BN backward writes d(x)'s C8 image
+_BN_LEAN = _switch('LD_BN_LEAN')  # ConvBnActFn saves bf16 C8 images only
+_DRAW_C8_ONLY = _switch('LD_DRAW_C8_ONLY')  # no fp32 d(raw) in the fused nodes
+
+
+# ---- the C8 questions of a conv's backward, each asked in ONE place ----------
+# ConvBnActFn.forward builds its ``lean`` decision from the same predicates its
+# backward uses: the two cannot drift apart (a backward that expects a tensor
+# the forward never wrote is the ``_ld_unwritten`` hazard).
+def _wgrad_takes_c8(cin, cout):
+    """This conv's weight gradient takes both operands as C8 images
+    (ld_conv_bf16_wgrad_c8)."""
+    return _PRECISION[0] == 'bf16' and _C8[0] and _WGRAD_C8[0] and \
+        cin % 32 == 0 and cout % 32 == 0
+
+
+def _draw_only_c8(cin, cout, need_x):
+    """d(raw) of a fused conv + norm node exists only as its C8 image: both
+    conv gradients read that image, the fp32 copy would have no reader."""
+    return _DRAW_C8_ONLY[0] and _wgrad_takes_c8(cin, cout) and \
+        (not need_x or _use_bf16(cout))
+
+
+def _bn_c8_covers(N, P, vec=4):
+    """The C8 BN backward covers an N x P map (at most 256 rows of 64 threads
+    x ``vec`` positions per channel)."""
+    return _BN_BWD_C8[0] and N * ((P // vec + 63) // 64) <= 256
+
+
+def _bn_lean_geometry(N, cin, cout, P):
+    """ConvBnActFn may keep its saved activations as bf16 C8 images only."""
+    return _BN_LEAN[0] and _wgrad_takes_c8(cin, cout) and P % 2 == 0 and \
+        _bn_c8_covers(N, P, 4 if P % 4 == 0 else 2)
+
+
 def _use_c8(reduction_channels, ksize=3, stride=1, J=1 << 30, x=None):
     """Whether a conv takes the C8 image of its activation operand.  The GEMM
     itself is faster with it everywhere (profiles/r02_kernels_c8.json: head
@@ -827,6 +869,32 @@ def _emit(p):
 DIRECT_GRADS = [True]
 
 
+def _grad_outs(params, needs, alloc, fresh_all=False):
+    """Where one backward launch writes the gradients of its parameter group.
+    Returns (outs, direct).  ``direct``: every gradient is needed and every
+    parameter has an arena slice -- ``outs`` are the slices and the kernel
+    ACCUMULATES.  Otherwise ``outs`` are ``alloc(p)`` for the needed ones (for
+    all with ``fresh_all``: a kernel that writes both regardless), None for the
+    rest, the kernel OVERWRITES and autograd gets them.  A group with slices on
+    some parameters only is not direct: nothing is emitted for it."""
+    if all(needs):
+        outs = [_sink(p) for p in params]
+        if all([s is not None for s in outs]):
+            return outs, True
+    return [alloc(p) if fresh_all or need else None
+            for p, need in zip(params, needs)], False
+
+
+def _grad_done(params, outs, direct):
+    """After the launch: what autograd gets for ``_grad_outs``' tensors -- one
+    ``_emit`` per parameter and Nones when they went into the arena."""
+    if not direct:
+        return outs
+    for p in params:
+        _emit(p)
+    return (None, ) * len(params)
+
+
 # ---- weight gradients off the backward critical path (round 3) --------------
 # In backward only the DATA gradient of a conv feeds the next layer; its WEIGHT
 # gradient is needed by the optimizer (and the bucket's all-reduce) alone.  With
@@ -916,6 +984,46 @@ def _defer_buffer(owner, attr, nbytes, device):
 
 
 _DEFER_CAPTURE_KEEP = []  # buffers created during a hipGraph capture (process lifetime)
+
+
+def _defer_flush_owner(queue, key, sink, join_device):
+    """A parameter used twice in one graph: while a job whose ``key`` field is
+    ``sink`` is still queued its partial buffer must not be overwritten --
+    flush first.  The flush also reduces the pending WEIGHT slabs, which the
+    side stream may still be writing: join it before."""
+    ptr = sink.data_ptr()
+    for j, _ in queue:
+        if getattr(j, key) == ptr:
+            wgrad_join(join_device)
+            flush_deferred()
+            return
+
+
+def _defer_partial(key, sink, owner, attr, nbytes, device):
+    """The partial buffer (owned by ``owner``) of a deferred norm / bias job
+    that will be keyed on ``sink``; the pending check comes first."""
+    _defer_flush_owner(_DEFER_B, key, sink, device)
+    return _defer_buffer(owner, attr, nbytes, device)
+
+
+def _defer_norm_job(partial, dgamma, dbeta, channels, nsplit, device):
+    """Queue the bucket-time finalisation of per-channel partials into the
+    arena slices ``dgamma`` (None: a conv bias job) and ``dbeta``."""
+    job = L.BnFinJobT()
+    job.partial = partial.data_ptr()
+    job.dgamma = None if dgamma is None else dgamma.data_ptr()
+    job.dbeta = dbeta.data_ptr()
+    job.C, job.nsplit, job.accumulate = channels, nsplit, 1
+    _DEFER_B.append((job, device))
+    DEFER_STATS['bn_jobs'] += 1
+
+
+def _defer_wgrad_job(job, sink, device):
+    """Queue the bucket-time sum of the slabs ld_conv_wgrad_partial described
+    in ``job`` into the arena slice ``sink``."""
+    job.dw, job.accumulate = sink.data_ptr(), 1
+    _DEFER_W.append((job, device))
+    DEFER_STATS['wgrad_jobs'] += 1
 
 
 def _defer_table(jobs, blocks_of, device):
@@ -1269,16 +1377,18 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
     dy8 = isinstance(dy, C8Act)
     cin = d.Cin
     st = L.stream_ptr(dy.device)
-    sink = _sink(pw)
-    dw = sink if sink is not None else torch.empty_like(w)
+    # one parameter: direct whenever it has an arena slice (accumulate = 1)
+    (dw, ), direct = _grad_outs((pw, ), (True, ), lambda p: torch.empty_like(w))
     need = lib.ld_conv_wgrad_workspace_bytes(C.byref(d))
-    ws = None if sink is not None and _DEFER_ON[0] else \
-        workspace(dy.device, need, 'wgrad')
+    # with a gradient arena only the split partials are computed here; their
+    # sum runs once per bucket (flush_deferred)
+    defer = direct and _DEFER_ON[0]
+    ws = None if defer else workspace(dy.device, need, 'wgrad')
     bf16 = _PRECISION[0] == 'bf16' and cin >= 16
     family = 2 if c8w else 1 if bf16 else 0
     fam = _FAMILIES[family]
     wgrad = getattr(lib, fam.wgrad)
-    side = _wgrad_side_for(sink, dy.device)
+    side = _wgrad_side_for(dw if direct else None, dy.device)
     if family == 0:
         # explicit tuning writes its result with accumulate = 0: into a
         # scratch dW, never into the gradient arena
@@ -1290,19 +1400,13 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
                 C.byref(d), L.ptr(x3), L.ptr(dy),
                 L.ptr(torch.empty_like(w)), L.ptr(tws), tws.numel(), st)
         _tune_once('wgrad', d, (), _tune_wgrad)
-    # with a gradient arena only the split partials are computed here; their
-    # sum runs once per bucket (flush_deferred)
-    defer = sink is not None and _DEFER_ON[0]
-    if defer and any(j.dw == sink.data_ptr() for j, _ in _DEFER_W):
-        # a weight used twice: its slabs are still pending, possibly on the
-        # side stream
-        wgrad_join()
-        flush_deferred()
+    if defer:  # (joins the side stream of every device)
+        _defer_flush_owner(_DEFER_W, 'dw', dw, None)
 
     def _launch(ws_, stream_ptr):
         if not defer:
             L.check(wgrad(C.byref(d), L.ptr(xw), L.ptr(dyw), L.ptr(dw),
-                          0 if sink is None else 1, L.ptr(ws_),
+                          1 if direct else 0, L.ptr(ws_),
                           ws_.numel(), stream_ptr), 'ld_conv_wgrad')
             return
         slabs = _defer_buffer(pw, '_ld_slabs', need, dy.device)
@@ -1311,9 +1415,7 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
             C.byref(d), family, L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
             slabs.numel(), C.byref(job), stream_ptr),
             'ld_conv_wgrad_partial')
-        job.dw, job.accumulate = sink.data_ptr(), 1
-        _DEFER_W.append((job, dy.device))
-        DEFER_STATS['wgrad_jobs'] += 1
+        _defer_wgrad_job(job, dw, dy.device)
 
     with _timed('conv_wgrad' + fam.timed, d):
         # operand images are produced on the main stream (cached ones cost
@@ -1321,48 +1423,31 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
         xw, dyw = ((x3.buf if x8 is not None else to_c8(x3)),
                    dy.buf if dy8 else to_c8(dy)) if c8w else (x3, dy)
         _wgrad_dispatch(_launch, side, ws, need, defer, (xw, dyw), dy.device)
-    if sink is not None:
-        _emit(pw)
-        return None
-    return dw
+    return _grad_done((pw, ), (dw, ), direct)[0]
 
 
 def _conv_bias_grad(lib, dy, d, pb):
     """The bias gradient of _conv_backward; None: into the gradient arena."""
     N, cout = d.N, d.Cout
     st = L.stream_ptr(dy.device)
-    sink = _sink(pb)
-    if sink is not None and _DEFER_ON[0]:
+    # one parameter: direct whenever it has an arena slice
+    (db, ), direct = _grad_outs((pb, ), (True, ), lambda p: torch.empty(
+        cout, dtype=torch.float32, device=dy.device))
+    if direct and _DEFER_ON[0]:
         # per-channel partial sums now, finalised with the bucket's norm
         # gradients (ld_bn_bwd_finalize_batch, a job without dgamma)
-        if any(j.dbeta == sink.data_ptr() for j, _ in _DEFER_B):
-            # flush_deferred also reduces the pending WEIGHT slabs, which the
-            # side stream may still be writing (ADVICE r5)
-            wgrad_join(dy.device)
-            flush_deferred()
         ns = lib.ld_bias_grad_nsplit(N, cout, dy.shape[2])
-        part = _defer_buffer(pb, '_ld_bias_partial', cout * ns * 16,
-                             dy.device)
+        part = _defer_partial('dbeta', db, pb, '_ld_bias_partial',
+                              cout * ns * 16, dy.device)
         L.check(lib.ld_bias_grad_partial(L.ptr(dy), N, cout, dy.shape[2],
                                          L.ptr(part), part.numel(), st),
                 'ld_bias_grad_partial')
-        job = L.BnFinJobT()
-        job.partial, job.dgamma, job.dbeta = (part.data_ptr(), None,
-                                              sink.data_ptr())
-        job.C, job.nsplit, job.accumulate = cout, ns, 1
-        _DEFER_B.append((job, dy.device))
-        DEFER_STATS['bn_jobs'] += 1
-        _emit(pb)
-        return None
-    db = sink if sink is not None else \
-        torch.empty(cout, dtype=torch.float32, device=dy.device)
-    L.check(lib.ld_bias_grad(L.ptr(dy), N, cout, dy.shape[2],
-                             L.ptr(db), 0 if sink is None else 1, st),
-            'ld_bias_grad')
-    if sink is not None:
-        _emit(pb)
-        return None
-    return db
+        _defer_norm_job(part, None, db, cout, ns, dy.device)
+    else:
+        L.check(lib.ld_bias_grad(L.ptr(dy), N, cout, dy.shape[2],
+                                 L.ptr(db), 1 if direct else 0, st),
+                'ld_bias_grad')
+    return _grad_done((pb, ), (db, ), direct)[0]
 
 
 def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
@@ -1387,8 +1472,7 @@ def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
     # bf16 + C8: the weight gradient takes both operands as C8 images
     # (ld_conv_bf16_wgrad_c8); converting dy first lets the data gradient
     # below use the same image
-    c8w = need_w and _PRECISION[0] == 'bf16' and \
-        _C8[0] and _WGRAD_C8[0] and cin % 32 == 0 and cout % 32 == 0
+    c8w = need_w and _wgrad_takes_c8(cin, cout)
     if c8w and not dy8:
         to_c8(dy)
     if dy8 and ((need_w and not c8w) or (has_bias and need_b) or
@@ -1544,9 +1628,6 @@ class BnActFn(torch.autograd.Function):
                 fan_give(ctx.fan_res, dres), None)
 
 
-_BN_BWD_C8 = [os.environ.get('LD_BN_BWD_C8', '1') == '1']
-
-
 def _bn_act_backward(dy, x3, y, scale, mean, rstd, relu, params, need_x,
                      need_g, need_b, need_res, dx_c8_only=False, c8in=None):
     """Backward of eval-BN affine (+ residual) + ReLU (shared by BnActFn and the
@@ -1560,144 +1641,84 @@ def _bn_act_backward(dy, x3, y, scale, mean, rstd, relu, params, need_x,
     are the bf16 C8 images the forward wrote (ld_bn_act_backward_c8in)."""
     lib = L.get_lib()
     dy = dy.contiguous()
-    if c8in is not None:
-        return _bn_act_backward_c8in(dy, c8in, scale, mean, rstd, relu, params,
-                                     need_x, need_g, need_b, need_res,
-                                     dx_c8_only)
-    N, c, P = x3.shape
-    dx8_only = bool(dx_c8_only and need_x and _BN_BWD_C8[0] and
-                    N * ((P // 4 + 63) // 64) <= 256 and
-                    all(t is None or t.data_ptr() % 16 == 0 for t in (dy, y, x3))
-                    and _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
-                    P % 4 == 0)
-    dx = torch.empty_like(x3) if need_x and not dx8_only else None
-    dres = torch.empty_like(x3) if need_res else None
-    pg, pb = params
-    sg, sb = _sink(pg), _sink(pb)
-    direct = need_g and need_b and sg is not None and sb is not None
-    if direct:
-        dgamma, dbeta = sg, sb
+    dev = dy.device
+    lean = c8in is not None
+    if lean:
+        y, x3, (N, c, P) = c8in  # the images; the forward's gate covered N x P
+        if dy.data_ptr() % 16:  # fresh allocations are 512-byte aligned
+            dy = dy.clone()
+        dx8_only = bool(dx_c8_only)
+
+        def fresh():
+            return torch.empty((N, c, P), dtype=torch.float32, device=dev)
     else:
-        dgamma = torch.empty(c, dtype=torch.float32, device=x3.device) \
-            if need_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=x3.device) \
-            if need_b else None
+        N, c, P = x3.shape
+        dx8_only = bool(dx_c8_only and need_x and _bn_c8_covers(N, P) and
+                        all(t.data_ptr() % 16 == 0 for t in (dy, y, x3)) and
+                        _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
+                        P % 4 == 0)
+
+        def fresh():
+            return torch.empty_like(x3)
+    dx = fresh() if need_x and not dx8_only else None
+    dres = fresh() if need_res else None
+    # direct only when both gradients are needed and both have a slice;
+    # otherwise fresh tensors for the needed ones alone
+    (dgamma, dbeta), direct = _grad_outs(
+        params, (need_g, need_b),
+        lambda p: torch.empty(c, dtype=torch.float32, device=dev))
     need = lib.ld_bn_act_backward_workspace_bytes(N, c, P)
     defer = direct and _DEFER_ON[0]
-    if defer and any(j.dgamma == sg.data_ptr() for j, _ in _DEFER_B):
-        # a norm used twice: its partials are still pending.  The flush also
-        # reduces the pending weight slabs: wait for the side stream first
-        wgrad_join(x3.device)
-        flush_deferred()
-    ws = _defer_buffer(pg, '_ld_bn_partial', need, x3.device) if defer else \
-        workspace(x3.device, need, 'bn')
+    ws = _defer_partial('dgamma', dgamma, params[0], '_ld_bn_partial', need,
+                        dev) if defer else workspace(dev, need, 'bn')
     acc = L.LD_GRAD_DEFER if defer else 1 if direct else 0
     # bf16 mode: dx goes into the conv's C8 data- / weight-gradient kernels --
     # write its C8 image from this launch instead of a to_c8 launch per conv
-    dx_c8 = None
-    # every tensor ld_bn_act_backward_c8 takes 16 bytes at a time must be 16-byte
-    # aligned (a saved conv output or residual that is an offset view is not):
-    # otherwise the plain kernel + a to_c8 launch where needed (ADVICE r3)
-    al16 = all(t is None or t.data_ptr() % 16 == 0 for t in (dy, y, x3, dx, dres))
-    if dx8_only and not al16:  # (a fresh dres is always aligned; stay correct)
-        dx, dx8_only = torch.empty_like(x3), False
-        al16 = dx.data_ptr() % 16 == 0
-    if dx8_only:
-        dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=x3.device)
-    elif dx is not None and _BN_BWD_C8[0] and \
-            N * ((P // 4 + 63) // 64) <= 256 and al16:
-        dx_c8 = _c8_side_output(dx)
-    if dx_c8 is not None:
-        L.check(lib.ld_bn_act_backward_c8(
+    if lean:
+        dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=dev)
+    else:
+        # every tensor ld_bn_act_backward_c8 takes 16 bytes at a time must be
+        # 16-byte aligned (a saved conv output or residual that is an offset
+        # view is not): otherwise the plain kernel + a to_c8 launch where
+        # needed (ADVICE r3)
+        al16 = all(t is None or t.data_ptr() % 16 == 0
+                   for t in (dy, y, x3, dx, dres))
+        if dx8_only and not al16:  # (a fresh dres is always aligned; stay correct)
+            dx, dx8_only = torch.empty_like(x3), False
+            al16 = dx.data_ptr() % 16 == 0
+        if dx8_only:
+            dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=dev)
+        elif dx is not None and _bn_c8_covers(N, P) and al16:
+            dx_c8 = _c8_side_output(dx)
+        else:
+            dx_c8 = None
+    # which of the three kernels; also ld_bn_act_backward_nsplit's mode
+    mode = 2 if lean else 1 if dx_c8 is not None else 0
+    if mode:
+        fn, what = ((lib.ld_bn_act_backward_c8in, 'ld_bn_act_backward_c8in')
+                    if lean else
+                    (lib.ld_bn_act_backward_c8, 'ld_bn_act_backward_c8'))
+        L.check(fn(
             L.ptr(dy), L.ptr(y), L.ptr(x3), L.ptr(scale), L.ptr(mean),
             L.ptr(rstd), N, c, P, 1 if relu else 0, L.ptr(dx), L.ptr(dx_c8),
             L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), acc,
-            L.ptr(ws), ws.numel(), L.stream_ptr(x3.device)),
-            'ld_bn_act_backward_c8')
-        if dx8_only:
-            dx = C8Act(dx_c8, (N, c, P))
-        else:
-            _attach_c8(dx, dx_c8)
+            L.ptr(ws), ws.numel(), L.stream_ptr(dev)), what)
     else:
         L.check(lib.ld_bn_act_backward(
             L.ptr(dy), L.ptr(y), L.ptr(x3), L.ptr(scale), L.ptr(mean),
             L.ptr(rstd), N, c, P, 1 if relu else 0, L.ptr(dx),
             L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), acc,
-            L.ptr(ws), ws.numel(), L.stream_ptr(x3.device)),
+            L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
             'ld_bn_act_backward')
-    if defer:
-        job = L.BnFinJobT()
-        job.partial, job.dgamma, job.dbeta = (ws.data_ptr(), sg.data_ptr(),
-                                              sb.data_ptr())
-        job.C, job.accumulate = c, 1
-        job.nsplit = lib.ld_bn_act_backward_nsplit(
-            N, c, P, 1 if dx_c8 is not None else 0)
-        _DEFER_B.append((job, x3.device))
-        DEFER_STATS['bn_jobs'] += 1
-    if direct:
-        dgamma = dbeta = None
-        _emit(pg)
-        _emit(pb)
-    return dx, dres, dgamma, dbeta
-
-
-def _bn_act_backward_c8in(dy, c8in, scale, mean, rstd, relu, params, need_x,
-                          need_g, need_b, need_res, dx_c8_only):
-    """The lean BN (+ residual) + ReLU backward of bf16 mode: the saved output
-    and the saved conv result are bf16 C8 images (see _bn_act_backward)."""
-    lib = L.get_lib()
-    y_img, x_img, (N, c, P) = c8in
-    dev = dy.device
-    if dy.data_ptr() % 16:  # fresh allocations are 512-byte aligned
-        dy = dy.clone()
-    dx = None if dx_c8_only or not need_x else torch.empty(
-        (N, c, P), dtype=torch.float32, device=dev)
-    dres = torch.empty((N, c, P), dtype=torch.float32, device=dev) \
-        if need_res else None
-    dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=dev)
-    pg, pb = params
-    sg, sb = _sink(pg), _sink(pb)
-    direct = need_g and need_b and sg is not None and sb is not None
-    if direct:
-        dgamma, dbeta = sg, sb
-    else:
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev) \
-            if need_g else None
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev) \
-            if need_b else None
-    need = lib.ld_bn_act_backward_workspace_bytes(N, c, P)
-    defer = direct and _DEFER_ON[0]
-    if defer and any(j.dgamma == sg.data_ptr() for j, _ in _DEFER_B):
-        wgrad_join(dev)
-        flush_deferred()
-    ws = _defer_buffer(pg, '_ld_bn_partial', need, dev) if defer else \
-        workspace(dev, need, 'bn')
-    acc = L.LD_GRAD_DEFER if defer else 1 if direct else 0
-    L.check(lib.ld_bn_act_backward_c8in(
-        L.ptr(dy), L.ptr(y_img), L.ptr(x_img), L.ptr(scale), L.ptr(mean),
-        L.ptr(rstd), N, c, P, 1 if relu else 0, L.ptr(dx), L.ptr(dx_c8),
-        L.ptr(dres), L.ptr(dgamma), L.ptr(dbeta), acc, L.ptr(ws), ws.numel(),
-        L.stream_ptr(dev)), 'ld_bn_act_backward_c8in')
-    if dx is None and need_x:
-        dx = C8Act(dx_c8, (N, c, P))
-    elif dx is not None:
+    if dx is not None and dx_c8 is not None:
         _attach_c8(dx, dx_c8)
+    elif need_x and dx_c8 is not None:
+        dx = C8Act(dx_c8, (N, c, P))
     if defer:
-        job = L.BnFinJobT()
-        job.partial, job.dgamma, job.dbeta = (ws.data_ptr(), sg.data_ptr(),
-                                              sb.data_ptr())
-        job.C, job.accumulate = c, 1
-        job.nsplit = lib.ld_bn_act_backward_nsplit(N, c, P, 2)
-        _DEFER_B.append((job, dev))
-        DEFER_STATS['bn_jobs'] += 1
-    if direct:
-        dgamma = dbeta = None
-        _emit(pg)
-        _emit(pb)
+        _defer_norm_job(ws, dgamma, dbeta, c,
+                        lib.ld_bn_act_backward_nsplit(N, c, P, mode), dev)
+    dgamma, dbeta = _grad_done(params, (dgamma, dbeta), direct)
     return dx, dres, dgamma, dbeta
-
-
-_BN_LEAN = [os.environ.get('LD_BN_LEAN', '1') == '1']
 
 
 class ConvBnActFn(torch.autograd.Function):
@@ -1725,10 +1746,7 @@ class ConvBnActFn(torch.autograd.Function):
         # affine is kept as a bf16 C8 image (2 instead of 4 bytes per element,
         # written and read), and the backward takes the ReLU mask from the C8
         # image of z instead of reading z (round 6; LD_BN_LEAN=0: the fp32 form)
-        lean = _BN_LEAN[0] and _BN_BWD_C8[0] and \
-            _PRECISION[0] == 'bf16' and _C8[0] and _WGRAD_C8[0] and \
-            cin % 32 == 0 and cout % 32 == 0 and P % 2 == 0 and \
-            N * ((P // (4 if P % 4 == 0 else 2) + 63) // 64) <= 256 and \
+        lean = _bn_lean_geometry(N, cin, cout, P) and \
             (isinstance(x3, C8Act) or
              _use_c8(cin, kh, stride, N * P, x3))
         if lean and _TRUNK_C8[0]:
@@ -1782,9 +1800,7 @@ class ConvBnActFn(torch.autograd.Function):
         # bf16 mode: both conv gradients read the C8 image of d(raw); its fp32
         # copy is then never read -- do not write it
         cout, cin = w.shape[0], w.shape[1]
-        c8_dead = _DRAW_C8_ONLY[0] and _PRECISION[0] == 'bf16' and _C8[0] and \
-            _WGRAD_C8[0] and cin % 32 == 0 and cout % 32 == 0 and \
-            (not ng[0] or _use_bf16(cout))
+        c8_dead = _draw_only_c8(cin, cout, ng[0])
         if ctx.lean:
             draw, dres, dgamma, dbeta = _bn_act_backward(
                 dz, None, None, scale, mean, rstd, ctx.relu, (pg, pb),
@@ -1805,11 +1821,6 @@ class ConvBnActFn(torch.autograd.Function):
                                        else None)
         return (fan_give(ctx.fan, dx), dw, dgamma, dbeta, None, None, None,
                 dres, None, None, None, None)
-
-
-_FUSE_CONV_BN = [os.environ.get('LD_FUSE_CONV_BN', '1') == '1']
-_PAD_DGRAD = [os.environ.get('LD_PAD_DGRAD', '1') == '1']
-_DRAW_C8_ONLY = [os.environ.get('LD_DRAW_C8_ONLY', '1') == '1']
 
 
 def conv_bn_act(x3, w, gamma, beta, mean, var, eps, stride, pad, levels,
@@ -1990,14 +2001,12 @@ def _gn_backward(dy, x3, y, gamma, beta, stats, groups, levels, relu, params,
     dy = dy.contiguous()
     N, c, P = x3.shape
     lv = levels_desc(levels)
-    pg, pb = params
-    sg, sb = _sink(pg), _sink(pb)
-    direct = need_g and need_b and sg is not None and sb is not None
-    if direct:
-        dgamma, dbeta = sg, sb
-    else:
-        dgamma = torch.empty(c, dtype=torch.float32, device=x3.device)
-        dbeta = torch.empty(c, dtype=torch.float32, device=x3.device)
+    # not direct: the kernels write BOTH gradients whether needed or not, so
+    # both get a fresh tensor (fresh_all); acc = direct, GN never defers
+    (dgamma, dbeta), direct = _grad_outs(
+        params, (need_g, need_b),
+        lambda p: torch.empty(c, dtype=torch.float32, device=x3.device),
+        fresh_all=True)
     need = lib.ld_gn_backward_workspace_bytes(C.byref(lv), N, c)
     ws = workspace(x3.device, need, 'gn')
     aligned = all(t.data_ptr() % 16 == 0 for t in (dy, y, x3))
@@ -2038,10 +2047,7 @@ def _gn_backward(dy, x3, y, gamma, beta, stats, groups, levels, relu, params,
             1 if relu else 0, L.ptr(dx), L.ptr(dgamma), L.ptr(dbeta),
             1 if direct else 0, L.ptr(ws), ws.numel(),
             L.stream_ptr(x3.device)), 'ld_gn_backward')
-    if direct:
-        dgamma = dbeta = None
-        _emit(pg)
-        _emit(pb)
+    dgamma, dbeta = _grad_done(params, (dgamma, dbeta), direct)
     return dx, dgamma, dbeta
 
 
@@ -2124,9 +2130,7 @@ class ConvGnActFn(torch.autograd.Function):
         groups, out_levels, relu = ctx.gn
         ng = ctx.needs_input_grad
         cout, cin = w.shape[0], w.shape[1]
-        c8_dead = _DRAW_C8_ONLY[0] and _PRECISION[0] == 'bf16' and _C8[0] and \
-            _WGRAD_C8[0] and cin % 32 == 0 and cout % 32 == 0 and \
-            (not ng[0] or _use_bf16(cout))
+        c8_dead = _draw_only_c8(cin, cout, ng[0])
         draw, dgamma, dbeta = _gn_backward(
             dy, raw, y, gamma, beta, stats, groups, out_levels, relu, (pg, pb),
             ng[2], ng[3], dx_c8_only=c8_dead, need_lean=ctx.y_unwritten)
@@ -2467,22 +2471,16 @@ class ScaleLevelsFn(torch.autograd.Function):
         N, c, P = x3.shape
         lv = levels_desc(ctx.levels)
         dx = torch.empty_like(x3)
-        ps, = ctx.params
-        sink = _sink(ps) if ctx.needs_input_grad[1] else None
-        if sink is not None:
-            ds = sink
-        else:
-            ds = torch.empty_like(scales) if ctx.needs_input_grad[1] else None
+        # the arena slice is consulted only when the gradient is needed
+        (ds, ), direct = _grad_outs(ctx.params, ctx.needs_input_grad[1:2],
+                                    lambda p: torch.empty_like(scales))
         need = lib.ld_scale_levels_backward_workspace_bytes(C.byref(lv))
         ws = workspace(x3.device, need, 'scale_bwd')
         L.check(lib.ld_scale_levels_backward(
             C.byref(lv), L.ptr(dy), L.ptr(x3), L.ptr(scales), N * c, L.ptr(dx),
-            L.ptr(ds), 0 if sink is None else 1, L.ptr(ws), ws.numel(),
+            L.ptr(ds), 1 if direct else 0, L.ptr(ws), ws.numel(),
             L.stream_ptr(x3.device)), 'ld_scale_levels_backward')
-        if sink is not None:
-            ds = None
-            _emit(ps)
-        return dx, ds, None
+        return dx, _grad_done(ctx.params, (ds, ), direct)[0], None
 
 
 def scale_levels(x3, scales, levels):
@@ -2714,21 +2712,18 @@ def gconv_wgrad(x3, dy, w, groups, stride, pad, levels, pw=None):
     need = lib.ld_gconv_wgrad_workspace_floats(*geo)
     if not need:
         raise L.LdError(f'gconv_wgrad: bad geometry {geo}')
-    sink = _sink(pw)
-    dw = sink if sink is not None else torch.empty_like(w)
-    side = _wgrad_side_for(sink, dy.device)
+    # one parameter: direct whenever it has an arena slice (accumulate = 1)
+    (dw, ), direct = _grad_outs((pw, ), (True, ), lambda p: torch.empty_like(w))
+    side = _wgrad_side_for(dw if direct else None, dy.device)
     ws = workspace(dy.device, need * 4, 'gwgrad') if side is None else None
 
     def _launch(ws_, stream_ptr):
         L.check(lib.ld_gconv_wgrad(
-            L.ptr(x3), L.ptr(dy), L.ptr(dw), 0 if sink is None else 1,
+            L.ptr(x3), L.ptr(dy), L.ptr(dw), 1 if direct else 0,
             L.ptr(ws_), ws_.numel() // 4, *geo, stream_ptr), 'ld_gconv_wgrad')
 
     _wgrad_dispatch(_launch, side, ws, need * 4, False, (x3, dy), dy.device)
-    if sink is not None:
-        _emit(pw)
-        return None
-    return dw
+    return _grad_done((pw, ), (dw, ), direct)[0]
 
 
 class GroupedConvFn(torch.autograd.Function):
@@ -2820,12 +2815,8 @@ class QualityFn(torch.autograd.Function):
         g = g_cls_score.contiguous()
         g_cf = torch.empty_like(cls_feat3)
         g_reg = torch.empty_like(reg3)
-        sinks = [_sink(p) for p in ctx.params]
-        direct = all(s is not None for s in sinks)
-        if direct:
-            gp = sinks
-        else:
-            gp = [torch.empty_like(p) for p in ctx.params]
+        # all four parameters direct, or none (whatever autograd needs)
+        gp, direct = _grad_outs(ctx.params, (True, ) * 4, torch.empty_like)
         need = lib.ld_quality_backward_workspace_bytes(N, P)
         ws = workspace(reg3.device, need, 'quality_bwd')
         L.check(lib.ld_quality_backward(
@@ -2834,11 +2825,7 @@ class QualityFn(torch.autograd.Function):
             L.ptr(g_reg), L.ptr(gp[0]), L.ptr(gp[1]), L.ptr(gp[2]),
             L.ptr(gp[3]), 1 if direct else 0, L.ptr(ws), ws.numel(),
             L.stream_ptr(reg3.device)), 'ld_quality_backward')
-        if direct:
-            for p in ctx.params:
-                _emit(p)
-            gp = [None] * 4
-        return (g_reg, g_cf) + tuple(gp)
+        return (g_reg, g_cf) + tuple(_grad_done(ctx.params, gp, direct))
 
 
 def sgd_step(params_flat, grads_flat, momentum_flat, lr, momentum,

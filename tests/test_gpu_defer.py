@@ -228,3 +228,109 @@ def test_bias_grad_partial_equals_one_block_kernel():
         scale = float(exact.abs().max())
         assert float((o.double() - exact).abs().max()) <= 2e-7 * scale + 1e-9
         assert float((o - ref).abs().max()) <= 4e-7 * scale + 1e-9
+
+
+# ---- a parameter used twice in one graph: the "already pending" branch -------
+# One conv + BN pair applied to two inputs under a gradient arena.  The second
+# use finds the first one's deferred job still queued and must join the side
+# stream and flush before it overwrites the parameter's partial buffer.
+# N = 2, 32 -> 32 channels, 3 x 3: at 16 x 16 ld_conv_wgrad_partial already
+# reports 4 splits in all three kernel families, so the side did not have to
+# grow (_twice_check asserts >= 2)
+TWICE_HW = (16, 16)
+
+
+def _twice_splits(family, hw):
+    """ld_conv_wgrad_partial's split count for the pair's conv at side ``hw``."""
+    from ld_amd import layers as Y
+    from ld_amd import lib as L
+    dev = _dev()
+    lib = L.get_lib()
+    d, _ = Y.conv_desc(2, 32, 32, 3, 3, 1, 1, (hw, ))
+    x = torch.zeros(2, 32, d.Pin, device=dev)
+    dy = torch.zeros(2, 32, d.Pout, device=dev)
+    xin, dyin = (Y.to_c8(x), Y.to_c8(dy)) if family == 2 else (x, dy)
+    slabs = torch.empty(lib.ld_conv_wgrad_workspace_bytes(C.byref(d)),
+                        dtype=torch.uint8, device=dev)
+    job = L.WgradJobT()
+    L.check(lib.ld_conv_wgrad_partial(
+        C.byref(d), family, L.ptr(xin), L.ptr(dyin), L.ptr(slabs), slabs.numel(),
+        C.byref(job), L.stream_ptr(dev)), 'ld_conv_wgrad_partial')
+    torch.cuda.synchronize()
+    return job.splits
+
+
+def _twice(defer, precision, fused):
+    from ld_amd import layers as Y
+    from ld_amd.train import GradArena
+    dev = _dev()
+    prev_d, prev_p = Y._DEFER_ON[0], Y.get_precision()
+    Y._DEFER_ON[0] = defer
+    Y.set_precision(precision)
+    try:
+        g = torch.Generator().manual_seed(17)
+        N, c, (H, W) = 2, 32, TWICE_HW
+        lv = (TWICE_HW, )
+        w = (torch.randn(c, c, 3, 3, generator=g) * 0.05).to(dev).requires_grad_(True)
+        bias = torch.randn(c, generator=g).to(dev).requires_grad_(True)
+        gamma = (torch.rand(c, generator=g) + 0.5).to(dev).requires_grad_(True)
+        beta = torch.randn(c, generator=g).to(dev).requires_grad_(True)
+        mean = (torch.randn(c, generator=g) * 0.1).to(dev)
+        var = (torch.rand(c, generator=g) + 0.5).to(dev)
+        xs = [torch.randn(N, c, H * W, generator=g).to(dev).requires_grad_(True)
+              for _ in range(2)]
+        gos = [torch.randn(N, c, H * W, generator=g).to(dev) for _ in range(2)]
+        params = [w, gamma, beta] + ([] if fused else [bias])
+        arena = GradArena(params)
+        arena.zero_grad()
+        before = dict(Y.DEFER_STATS)
+        zs = []
+        for x in xs:
+            if fused:
+                Y.to_c8(x)  # an image on the input: the C8-operand conv is taken
+                z, _ = Y.conv_bn_act(x, w, gamma, beta, mean, var, 1e-5, 1, 1, lv)
+                assert z.grad_fn.lean  # the c8in launch is the one under test
+            else:
+                y, _ = Y.conv2d(x, w, bias, 1, 1, lv)
+                z = Y.bn_act(y, gamma, beta, mean, var, 1e-5)
+            zs.append(z)
+        torch.autograd.backward(zs, gos)
+        arena.finish()
+        torch.cuda.synchronize()
+        assert not Y.deferred_pending()
+        assert all(p._ld_pending == 0 for p in params)
+        stats = {k: Y.DEFER_STATS[k] - before[k] for k in before}
+        return [p._ld_grad.clone() for p in params], stats
+    finally:
+        Y._DEFER_ON[0] = prev_d
+        Y.set_precision(prev_p)
+
+
+def _twice_check(precision, fused):
+    assert _twice_splits(2 if precision == 'bf16' else 0, TWICE_HW) >= 2
+    g0, s0 = _twice(False, precision, fused)
+    g1, s1 = _twice(True, precision, fused)
+    assert s0['flushes'] == 0 and s0['wgrad_jobs'] == 0 and s0['bn_jobs'] == 0
+    # two weight jobs; two norm jobs (+ two bias jobs of the unfused pair)
+    assert s1['wgrad_jobs'] == 2 and s1['bn_jobs'] == (2 if fused else 4), s1
+    # more than the one final flush: the second use flushed the first one's jobs
+    assert s1['flushes'] > 1, s1
+    for name, a, b in zip(('dw', 'dgamma', 'dbeta', 'dbias'), g0, g1):
+        assert torch.isfinite(a).all() and float(a.abs().max()) > 0, name
+        print(name, 'max |deferred - per-layer| =', float((a - b).abs().max()))
+        assert torch.equal(a, b), name
+
+
+@pytest.mark.parametrize('precision', ['fp32', 'bf16'])
+def test_parameter_used_twice_flushes_its_pending_jobs(precision):
+    """conv (with bias) + BN applied twice: dw, dbias, dgamma and dbeta with
+    deferral are bit-identical to the per-layer launches.  In bf16 mode the
+    bias-carrying conv takes the C8 weight-gradient kernel (the BN backward hands
+    it an fp32 gradient with a C8 image attached), so the bias stays."""
+    _twice_check(precision, fused=False)
+
+
+def test_lean_conv_bn_used_twice_flushes_its_pending_jobs():
+    """The same with the lean ConvBnActFn of bf16 mode: the job flushed early
+    is the one ld_bn_act_backward_c8in's partials belong to."""
+    _twice_check('bf16', fused=True)
