@@ -21,8 +21,14 @@
 //             box-target / VLR / IM maps in level-major layout, i.e. already in
 //             the form `images_to_levels` would produce.
 // All integer results (labels, positive indices, masks) are bit-exact w.r.t.
-// the reference CPU path on tie-free inputs; fp32 op order follows the
-// reference (no FMA contraction in this file).
+// the reference CPU path; fp32 op order follows the reference (no FMA
+// contraction in this file).  Ties follow the reference's CPU rules and are
+// tested as such (tests/test_gpu_target_edges.py): equal IoUs at an anchor go
+// to the lowest GT index (ATSS and MaxIoU's arg-max), equal areas at an FCOS
+// point to the lowest GT index, a later GT overrides an earlier one in
+// MaxIoU's low-quality match.  Equal centre distances at the k-th place of the
+// top-k go to the lowest anchor index: torch.topk leaves that order
+// unspecified, so this rule is the project's definition (oracle/ld_oracle.py).
 #include <hip/hip_runtime.h>
 
 #include "ld_launch.h"
@@ -251,7 +257,8 @@ __global__ __launch_bounds__(kBlock) void atss_select_kernel(
 // (distance, then anchor index: the scan's order) pop the winners -- no block
 // barrier until the candidates of all levels are in LDS, from where the second
 // half (IoU threshold, 64-bit atomicMax publish) is the scan kernel's, verbatim.
-// Results are bit-identical to the scan (tests/test_gpu_atss.py runs both).
+// Results are bit-identical to the scan (tests/test_gpu_lossblock.py runs both and
+// compares them; tests/test_gpu_target_edges.py holds each to the oracle).
 constexpr int kWinR = 8;
 constexpr int kWinK = 5;  // ceil(17 * 17 / 64)
 

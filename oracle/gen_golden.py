@@ -3,7 +3,8 @@ REFERENCE CODE at /root/reference (unmodified, imported through
 oracle/ref_shim.py) on CPU in fp32.  Run from the repo root in the build
 container:
 
-    python oracle/gen_golden.py [--only kat,anchors,targets,lossblock,e2e,infer]
+    python oracle/gen_golden.py [--only kat,anchors,targets,lossblock,e2e,infer,
+                                        target_edges]
 
 The fixtures it writes are committed; the GPU box has no /root/reference and
 only ever reads the .npz files.  Inputs that can be regenerated from a seed
@@ -1717,6 +1718,128 @@ def gen_pipeline():
     print('pipeline.npz', len(out), 'arrays')
 
 
+def gen_target_edges():
+    """tests/_target_edges.py cases (ties, thresholds, GT-count edges) through
+    the reference's own assigners on CPU: ATSSAssigner.assign / get_vlr_region
+    (atss_assigner.py:33-298), MaxIoUAssigner.assign (max_iou_assigner.py) with
+    LDRetinaHead.get_vlr_region (ld_retina.py:483-608), and
+    LDFCOSHead._get_target_single (ld_fcos_head.py:261-353), each on one
+    image's valid anchors / points as the heads call them.  Stored: every case
+    on which the reference's rule is deterministic.  Not stored: images without
+    a GT box in the ATSS / VLR code (the reference crashes, quirk Q2; the
+    project defines all-background) and the top-k distance-tie cases, for
+    which only `info_*_ref_agrees` records whether torch.topk's unspecified
+    order among equals happened to match the oracle's rule."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _target_edges as E
+    import ld_oracle as O
+    from mmdet.core.bbox.assigners import ATSSAssigner, MaxIoUAssigner
+    d, stored = {}, []
+    T = torch.from_numpy
+    # ---- ATSS
+    for name, build in E.ATSS_CASES.items():
+        c = build()
+        per_level = O.grid_anchors(c['sizes'], tuple(c['strides']))
+        assigner = ATSSAssigner(topk=c['topk'])
+        agrees = []
+        for n, gts in enumerate(c['boxes']):
+            if len(gts) == 0:
+                continue
+            anc, nl, _ = E.inside_anchors(O, c, n, per_level)
+            args = (T(anc), nl, T(gts), None, T(c['labels'][n]))
+            ar = assigner.assign(*args)
+            vlr = assigner.get_vlr_region(*args)
+            if name in E.ATSS_TOPK_TIE_CASES:
+                gi, _ = O.atss_assign(anc, nl, gts, c['topk'])
+                agrees.append(bool(
+                    np.array_equal(gi, _np(ar.gt_inds)) and np.array_equal(
+                        O.vlr_region(anc, nl, gts, c['topk']), _np(vlr))))
+                continue
+            assert E.kth_ties(O, anc, nl, gts, c['topk']) == 0, (name, n)
+            d[f'atss_{name}_gt_inds_{n}'] = _np(ar.gt_inds).astype(np.int16)
+            d[f'atss_{name}_max_overlaps_{n}'] = _np(ar.max_overlaps)
+            d[f'atss_{name}_vlr_{n}'] = _np(vlr)
+        if name in E.ATSS_TOPK_TIE_CASES:
+            d[f'info_atss_{name}_ref_agrees'] = np.array(agrees)
+        else:
+            stored.append(f'atss_{name}')
+        print(f'  target_edges atss {name}: agrees={agrees}')
+    # ---- MaxIoU over the retina head's 9 anchors per cell; dense arrays over
+    # all anchors (gt_inds -1 / vlr 0 outside the valid region)
+    head = _ld_retina_head()
+    for name, build in E.MAXIOU_CASES.items():
+        c = build()
+        per_level = O.retina_grid_anchors(c['sizes'], tuple(c['strides']))
+        assigner = MaxIoUAssigner(ignore_iof_thr=-1, **c['assigner'])
+        for n, gts in enumerate(c['boxes']):
+            anc, nl, inside = E.inside_anchors(O, c, n, per_level)
+            ar = assigner.assign(T(anc), T(gts), None, T(c['labels'][n]))
+            gi = np.full(inside.shape[0], -1, np.int16)
+            gi[inside] = _np(ar.gt_inds)
+            d[f'maxiou_{name}_gt_inds_{n}'] = gi
+            if E.maxiou_vlr_is_stored(O, c, n):
+                vlr = np.zeros(inside.shape[0], np.float32)
+                vlr[inside] = _np(head.get_vlr_region(T(anc), nl, T(gts)))
+                d[f'maxiou_{name}_vlr_{n}'] = vlr
+        stored.append(f'maxiou_{name}')
+        print(f'  target_edges maxiou {name}')
+    # ---- FCOS, centre sampling off and on
+    head = _ld_fcos_head()
+    for name, build in E.FCOS_CASES.items():
+        c = build()
+        pts = head.get_points(c['sizes'], torch.float32, 'cpu')
+        rr = torch.cat([pts[i].new_tensor(head.regress_ranges[i])[None]
+                        .expand_as(pts[i]) for i in range(len(pts))])
+        for cs in (0, 1):
+            head.center_sampling = bool(cs)
+            for n, gts in enumerate(c['boxes']):
+                lab, bt = head._get_target_single(
+                    T(gts), T(c['labels'][n]), torch.cat(pts), rr,
+                    [p.size(0) for p in pts])
+                d[f'fcos_{name}_cs{cs}_labels_{n}'] = _np(lab).astype(np.int16)
+                d[f'fcos_{name}_cs{cs}_bbox_targets_{n}'] = _np(bt)
+        stored.append(f'fcos_{name}')
+        print(f'  target_edges fcos {name}')
+    d['cases'] = np.array(stored)
+    path = os.path.join(OUT, 'target_edges.npz')
+    np.savez_compressed(path, **d)
+    print('target_edges.npz', len(d), 'arrays', os.path.getsize(path), 'bytes')
+    _manifest('target_edges.npz', [
+        'Crafted target-assignment cases of `tests/_target_edges.py` run '
+        'through the reference\'s ATSSAssigner.assign / get_vlr_region, '
+        'MaxIoUAssigner.assign + LDRetinaHead.get_vlr_region and '
+        'LDFCOSHead._get_target_single on CPU '
+        '(`python oracle/gen_golden.py --only target_edges`).',
+        f'{len(d)} arrays, {os.path.getsize(path)} bytes; recorded outputs '
+        'only (gt_inds / labels as int16, IoUs and distances as float32).',
+        'Stored cases: ' + ', '.join(stored) + '.',
+        'Not stored: ATSS images without a GT box (reference quirk Q2) and '
+        'the top-k distance-tie cases ' + ', '.join(E.ATSS_TOPK_TIE_CASES) +
+        ', for which `info_atss_<case>_ref_agrees` (per image, '
+        'informational, never asserted) records whether torch.topk\'s order '
+        'among equal distances matched the oracle\'s lower-anchor-index '
+        'rule: ' + ', '.join(
+            f'{n}={d[f"info_atss_{n}_ref_agrees"].tolist()}'
+            for n in E.ATSS_TOPK_TIE_CASES) + '.',
+        'A MaxIoU image\'s `vlr` is stored only where no distance tie sits '
+        'at the 9th place of a level.'])
+
+
+def _manifest(fname, lines):
+    """Create or replace the `## fname` section of tests/golden/MANIFEST.md."""
+    path = os.path.join(OUT, 'MANIFEST.md')
+    head = ('# Stored test vectors\n\nOne section per fixture that records how '
+            'it was produced; written by `oracle/gen_golden.py`.\n')
+    text = open(path).read() if os.path.exists(path) else head
+    parts = text.split('\n## ')
+    keep = [parts[0].rstrip('\n')] + [
+        '## ' + p.rstrip('\n') for p in parts[1:]
+        if p.split('\n', 1)[0].strip() != fname]
+    keep.append('## ' + fname + '\n\n' + '\n\n'.join(lines))
+    with open(path, 'w') as f:
+        f.write('\n\n'.join(keep) + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--only', default='kat,anchors,targets,lossblock,e2e,infer,'
@@ -1780,6 +1903,8 @@ def main():
         gen_grad_truth64()
     if 'grad_samples' in only:
         gen_grad_samples([c for c in args.e2e_cases.split(',') if c])
+    if 'target_edges' in only:
+        gen_target_edges()
 
 
 if __name__ == '__main__':
