@@ -1422,6 +1422,32 @@ int ld_draw_boxes(uint8_t* img, int height, int width, const float* gt_boxes, in
                   const float* dets, int num_dets, float score_thr, int thickness,
                   uint32_t gt_color, uint32_t det_color, ld_stream_t stream);
 
+/* Paints text labels into img (DEVICE uint8, height x width x 3, in place) with
+ * a fixed font for ASCII 0x20-0x7E: 5 x 7 glyphs at columns 1-5, rows 1-7 of a
+ * 6 x 8 cell, the cell scaled by the integer `scale`.
+ *   text_bytes  DEVICE, num_labels slots of LD_LABEL_MAX_LEN bytes; label i
+ *               reads the first len_i bytes of slot i
+ *   desc        DEVICE int32 (num_labels, 4): x1, y1, len, unused.  len is
+ *               clamped to 0..LD_LABEL_MAX_LEN, x1 / y1 to +-2^30
+ * Label i is a filled bg_color rectangle of len * 6 * scale by 8 * scale pixels
+ * with the glyph pixels in fg_color; its top-left corner is (x1, y1 - 8 * scale)
+ * when that row is >= 0, else (x1, y1).  A byte outside the font draws as '?',
+ * len 0 draws nothing, pixels outside the image are dropped.  Where labels
+ * overlap every pixel ends as if they were painted in index order: each pixel
+ * takes the last label that covers it, so the result does not depend on
+ * scheduling.  Colors as ld_draw_boxes.  LD_EINVAL on negative sizes or
+ * scale < 1, LD_EUNSUPPORTED for scale > 1024; zero labels or pixels return 0
+ * at once. */
+#define LD_LABEL_MAX_LEN 64
+int ld_draw_labels(uint8_t* img, int height, int width, const uint8_t* text_bytes,
+                   const int32_t* desc, int num_labels, int scale, uint32_t fg_color,
+                   uint32_t bg_color, ld_stream_t stream);
+
+/* Row `row` (0-6, top first) of the glyph of character c (0x20-0x7E): five
+ * bits, bit 4 the leftmost column; -1 outside those ranges.  Host only: it
+ * reads the host copy of the table the kernel uses. */
+int ld_font_glyph(int c, int row);
+
 /* ---- proposal recall (recall.hip) -------------------------------------------
  * eval_recalls / _recalls of the reference (core/evaluation/recall.py:10-40,
  * 83-103).  One batch of images per ld_eval_recalls_match call: proposals

@@ -41,4 +41,11 @@ from .recall import (CocoProposalEvaluator,  # noqa: F401,E402
 from .landscape import (FeatureLandscape,  # noqa: F401,E402
                         TeacherStudentDiscrepancy, mix_levels)
 
+from .datasets import (DATASETS, CocoDataset,  # noqa: F401,E402
+                       ConcatDataset, CustomDataset, RepeatDataset,
+                       VOCDataset, XMLDataset, build_dataset)
+from .dataloader import DeviceDataLoader, build_dataloader  # noqa: F401,E402
+from .apis import (inference_detector, init_detector,  # noqa: F401,E402
+                   single_gpu_test)
+
 __version__ = '0.1.0'

@@ -3,7 +3,7 @@
 for every image, the good / bad ``topk`` selection of
 ``ResultVisualizer.evaluate_and_show`` (89-134) and the box overlay of the
 images it saves -- run by eval_image.hip (``ld_eval_image_map``,
-``ld_draw_boxes``) and ``ld_rank_images`` of eval.hip.
+``ld_draw_boxes``, ``ld_draw_labels``) and ``ld_rank_images`` of eval.hip.
 
 ``ImageMapAnalyzer`` takes detections where the heads leave them (device
 ``(n, 5)`` + ``(n,)`` per image), scores every image of a batch in one launch
@@ -35,7 +35,7 @@ from .eval_common import (as_boxes, eval_batch, eval_device,
 from .lossblock import workspace
 
 __all__ = ['bbox_map_eval', 'ImageMapAnalyzer', 'draw_gt_det_bboxes',
-           'write_png', 'default_iou_thrs']
+           'draw_labels', 'label_texts', 'write_png', 'default_iou_thrs']
 
 
 def default_iou_thrs():
@@ -192,9 +192,64 @@ def _color(c):
     return c[0] | (c[1] << 8) | (c[2] << 16)
 
 
+def label_texts(det_bboxes, labels, class_names):
+    """The text the reference puts on a detection
+    (core/visualization/image.py:135-138): ``f'{class_name}|{score:.02f}'``,
+    ``f'cls {label}'`` for a label without a name."""
+    texts = []
+    for b, l in zip(np.asarray(det_bboxes, np.float32).reshape(-1, 5),
+                    np.asarray(labels).reshape(-1)):
+        name = class_names[int(l)] if class_names is not None and \
+            0 <= int(l) < len(class_names) else f'cls {int(l)}'
+        texts.append(f'{name}|{float(b[4]):.02f}')
+    return texts
+
+
+def draw_labels(img, texts, xy, scale=1, fg_color=(255, 255, 255),
+                bg_color=(0, 0, 0)):
+    """Paints text labels IN PLACE into a device (H, W, 3) uint8 tensor, in one
+    launch (``ld_draw_labels``).  ``texts[i]`` (str, or bytes) goes at the
+    integer corner ``xy[i] = (x1, y1)``: a filled ``bg_color`` rectangle of
+    ``len * 6 * scale`` by ``8 * scale`` pixels above ``y1`` (below it when that
+    would leave the image at the top), glyph pixels in ``fg_color``.  The font
+    is the fixed 5 x 7 table of ``ld_amd.font5x7`` (ASCII 0x20-0x7E; other bytes
+    draw as ``?``); a text is cut at ``font5x7.MAX_LEN`` bytes.  Later labels
+    paint over earlier ones.  -> ``img``."""
+    from . import font5x7 as F
+    L.require_device(img, torch.uint8, 'draw_labels image')
+    if img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+        raise ValueError('draw_labels: image must be contiguous (H, W, 3)')
+    xy = np.asarray(xy, np.int64).reshape(-1, 2)
+    n = len(texts)
+    if len(xy) != n:
+        raise ValueError(f'draw_labels: {n} texts but {len(xy)} corners')
+    if int(scale) < 1:
+        raise ValueError('draw_labels: scale must be >= 1')
+    if n == 0:
+        return img
+    text = np.zeros((n, F.MAX_LEN), np.uint8)
+    desc = np.zeros((n, 4), np.int32)
+    desc[:, :2] = np.clip(xy, -(1 << 30), 1 << 30)
+    for i, t in enumerate(texts):
+        raw = t if isinstance(t, (bytes, bytearray)) else \
+            str(t).encode('latin-1', 'replace')
+        raw = bytes(raw)[:F.MAX_LEN]
+        text[i, :len(raw)] = np.frombuffer(raw, np.uint8)
+        desc[i, 2] = len(raw)
+    dev = img.device
+    dtext = torch.from_numpy(text).to(dev)
+    ddesc = torch.from_numpy(desc).to(dev)
+    L.check(L.get_lib().ld_draw_labels(
+        L.ptr(img), img.shape[0], img.shape[1], L.ptr(dtext), L.ptr(ddesc), n,
+        int(scale), _color(fg_color), _color(bg_color), L.stream_ptr(dev)),
+        'ld_draw_labels')
+    return img
+
+
 def draw_gt_det_bboxes(img_u8_hwc, gt_bboxes, det_bboxes, score_thr=0,
                        thickness=2, gt_color=(255, 102, 61),
-                       det_color=(72, 101, 241)):
+                       det_color=(72, 101, 241), class_names=None, labels=None,
+                       text_color=(255, 255, 255), font_scale=1):
     """The overlay of the reference's saved images, in one launch
     (``ld_draw_boxes``): rectangle outlines painted into a COPY of the (H, W,
     3) uint8 image, the GT boxes (g, 4) first, then the detections (m, 5) with
@@ -204,9 +259,14 @@ def draw_gt_det_bboxes(img_u8_hwc, gt_bboxes, det_bboxes, score_thr=0,
     falls outside the image is dropped.  Colors go to channels 0, 1, 2 in the
     order given.
 
-    Class names and score text are NOT drawn: the reference renders them with
-    matplotlib, which this package does not depend on.  -> device uint8
-    tensor."""
+    With ``labels`` (m,), the class index of every detection, the kept
+    detections also get their text ``f'{class_name}|{score:.02f}'``
+    (``class_names`` a sequence; ``cls {label}`` without one) at the truncated
+    (x1, y1) of their box, through ``draw_labels``: ``text_color`` on a
+    ``det_color`` ground, in a fixed 5 x 7 font scaled by ``font_scale`` (the
+    reference renders text with matplotlib, which this package does not depend
+    on, so the glyphs differ from its).  Without ``labels`` no text is drawn.
+    -> device uint8 tensor."""
     img = torch.as_tensor(img_u8_hwc)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise ValueError('draw_gt_det_bboxes: image must be (H, W, 3) uint8')
@@ -220,7 +280,21 @@ def draw_gt_det_bboxes(img_u8_hwc, gt_bboxes, det_bboxes, score_thr=0,
         L.ptr(out), out.shape[0], out.shape[1], L.ptr(g), g.shape[0], L.ptr(d),
         d.shape[0], float(score_thr), int(thickness), _color(gt_color),
         _color(det_color), L.stream_ptr(dev)), 'ld_draw_boxes')
-    return out
+    if labels is None:
+        if class_names is not None:
+            raise ValueError('draw_gt_det_bboxes: class_names needs labels')
+        return out
+    dn = d.cpu().numpy()
+    lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor)
+                     else labels).reshape(-1)
+    if len(lab) != len(dn):
+        raise ValueError(f'draw_gt_det_bboxes: {len(dn)} detections but '
+                         f'{len(lab)} labels')
+    keep = dn[:, 4] >= np.float32(score_thr)  # the kernel's rule
+    dn, lab = dn[keep], lab[keep]
+    return draw_labels(out, label_texts(dn, lab, class_names),
+                       dn[:, :2].astype(np.int32), font_scale, text_color,
+                       det_color)
 
 
 def write_png(path, img_u8_hwc):

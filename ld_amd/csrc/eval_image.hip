@@ -1,6 +1,7 @@
 // Per-image mAP on gfx950: the reference's bbox_map_eval
 // (tools/analysis_tools/analyze_results.py:13-45) for every image of a batch in
-// one launch, and the box painter of its good / bad image dumps.
+// one launch, and the box and label painters of its good / bad image dumps and
+// of show_result.
 //
 // Replaces (reference file:line)
 //   bbox_map_eval: eval_map of a one-image dataset at every IoU threshold,
@@ -39,6 +40,7 @@
 #include "../../include/ld_hip.h"
 #include "eval_common.h"
 #include "eval_iou.h"
+#include "font5x7.h"
 #include "ld_launch.h"
 
 namespace {
@@ -420,6 +422,66 @@ __global__ __launch_bounds__(kThreads) void draw_boxes_kernel(uint8_t* img, Draw
   }
 }
 
+// ------------------------------------------------------------- labels -------
+constexpr int kFontChars = LD_FONT_LAST - LD_FONT_FIRST + 1;
+constexpr int kCellW = 6, kCellH = 8;  // glyph at columns 1-5, rows 1-7
+constexpr int kMaxScale = 1 << 10;     // keeps every extent below inside int32
+
+const uint8_t kFontHost[kFontChars * LD_FONT_ROWS] = {LD_FONT5X7_TABLE};
+__constant__ uint8_t kFont[kFontChars * LD_FONT_ROWS] = {LD_FONT5X7_TABLE};
+
+struct LabelParams {
+  int H, W, num_labels, scale;
+  uint32_t fg, bg;
+};
+
+// One thread per pixel.  Every pixel finds the LAST label whose rectangle
+// covers it and takes that label's colour there, which is what painting the
+// labels in index order leaves; nothing depends on the order threads run in.
+__global__ __launch_bounds__(kThreads) void draw_labels_kernel(uint8_t* img, LabelParams p,
+                                                              const uint8_t* text,
+                                                              const int32_t* desc) {
+  __shared__ int s_lab[kThreads][3];  // x0, y0, width in pixels
+  const int tid = threadIdx.x;
+  const long long pix = (long long)blockIdx.x * kThreads + tid;
+  const bool inside = pix < (long long)p.H * p.W;
+  const int y = inside ? (int)(pix / p.W) : 0, x = inside ? (int)(pix - (long long)y * p.W) : 0;
+  const int ch = kCellH * p.scale;
+  int best = -1, bx = 0, by = 0;
+  for (int base = 0; base < p.num_labels; base += kThreads) {
+    __syncthreads();
+    const int k = base + tid;
+    if (k < p.num_labels) {
+      const int32_t* d = desc + (size_t)k * 4;
+      const int lim = 1 << 30;
+      const int x1 = min(max(d[0], -lim), lim), y1 = min(max(d[1], -lim), lim);
+      const int len = min(max(d[2], 0), LD_LABEL_MAX_LEN);
+      s_lab[tid][0] = x1;
+      s_lab[tid][1] = y1 - ch >= 0 ? y1 - ch : y1;  // above the box, else inside it
+      s_lab[tid][2] = len * kCellW * p.scale;
+    }
+    __syncthreads();
+    const int cnt = min(kThreads, p.num_labels - base);
+    for (int q = 0; q < cnt; ++q) {
+      const int x0 = s_lab[q][0], y0 = s_lab[q][1], w = s_lab[q][2];
+      // x0 + w and y0 + ch stay below 2^30 + 2^19: no overflow
+      if (x >= x0 && x < x0 + w && y >= y0 && y < y0 + ch) best = base + q, bx = x0, by = y0;
+    }
+  }
+  if (!inside || best < 0) return;
+  const int cx = (x - bx) / p.scale, cy = (y - by) / p.scale;  // cy < kCellH
+  const int gx = cx % kCellW;
+  int c = text[(size_t)best * LD_LABEL_MAX_LEN + cx / kCellW];  // cx / 6 < len <= MAX_LEN
+  if (c < LD_FONT_FIRST || c > LD_FONT_LAST) c = '?';
+  const bool on = gx >= 1 && cy >= 1 &&
+                  ((kFont[(c - LD_FONT_FIRST) * LD_FONT_ROWS + cy - 1] >> (kCellW - 1 - gx)) & 1);
+  const uint32_t col = on ? p.fg : p.bg;
+  uint8_t* px = img + (size_t)pix * 3;
+  px[0] = (uint8_t)(col & 255u);
+  px[1] = (uint8_t)((col >> 8) & 255u);
+  px[2] = (uint8_t)((col >> 16) & 255u);
+}
+
 }  // namespace
 
 extern "C" {
@@ -470,6 +532,25 @@ int ld_draw_boxes(uint8_t* img, int height, int width, const float* gt_boxes, in
   DrawParams p{height, width, num_gts, num_dets, thickness, score_thr, gt_color, det_color};
   LD_LAUNCH(draw_boxes_kernel, dim3((unsigned)((pixels + kThreads - 1) / kThreads)),
             dim3(kThreads), 0, (hipStream_t)stream_, img, p, gt_boxes, dets);
+  return (int)hipGetLastError();
+}
+
+int ld_font_glyph(int c, int row) {
+  if (c < LD_FONT_FIRST || c > LD_FONT_LAST || row < 0 || row >= LD_FONT_ROWS) return -1;
+  return kFontHost[(c - LD_FONT_FIRST) * LD_FONT_ROWS + row];
+}
+
+int ld_draw_labels(uint8_t* img, int height, int width, const uint8_t* text_bytes,
+                   const int32_t* desc, int num_labels, int scale, uint32_t fg_color,
+                   uint32_t bg_color, ld_stream_t stream_) {
+  if (height < 0 || width < 0 || num_labels < 0 || scale < 1) return LD_EINVAL;
+  const long long pixels = (long long)height * width;
+  if (pixels == 0 || num_labels == 0) return 0;
+  if (!img || !text_bytes || !desc) return LD_EINVAL;
+  if (pixels >= (1ll << 31) || scale > kMaxScale) return LD_EUNSUPPORTED;
+  LabelParams p{height, width, num_labels, scale, fg_color, bg_color};
+  LD_LAUNCH(draw_labels_kernel, dim3((unsigned)((pixels + kThreads - 1) / kThreads)),
+            dim3(kThreads), 0, (hipStream_t)stream_, img, p, text_bytes, desc);
   return (int)hipGetLastError();
 }
 

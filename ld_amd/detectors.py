@@ -98,25 +98,32 @@ class SingleStageDetector(nn.Module):
         return self.bbox_head.forward_train(x, img_metas, gt_bboxes, gt_labels,
                                             gt_bboxes_ignore)
 
-    def simple_test(self, img, img_metas, rescale=False):
+    def simple_test(self, img, img_metas, rescale=False,
+                    return_device_dets=False):
         """single_stage.py:98-129: features -> head -> get_bboxes (one device
-        call, ld_get_bboxes) -> per-class numpy arrays."""
+        call, ld_get_bboxes) -> per-class numpy arrays.  With
+        ``return_device_dets`` -> ``(results, [(dets (k, 5), labels (k,)),
+        ...])``: also every image's device tensors as get_bboxes returns them,
+        which a streaming evaluator takes without a host round trip."""
         from .core import bbox2result
         x = self.extract_feat(img)
         outs = self.bbox_head(x)
         bbox_list = self.bbox_head.get_bboxes(*outs, img_metas,
                                               rescale=rescale)
-        return [bbox2result(b, l, self.bbox_head.num_classes)
-                for b, l in bbox_list]
+        results = [bbox2result(b, l, self.bbox_head.num_classes)
+                   for b, l in bbox_list]
+        return (results, list(bbox_list)) if return_device_dets else results
 
     def extract_feats(self, imgs):
         """base.py:67-71: features of every test-time view."""
         return [self.extract_feat(img) for img in imgs]
 
-    def aug_test(self, imgs, img_metas, rescale=False):
+    def aug_test(self, imgs, img_metas, rescale=False,
+                 return_device_dets=False):
         """single_stage.py:131-160: features of every view -> the head's
         aug_test (per-view get_bboxes(with_nms=False) + one device merge-NMS)
-        -> ``[bbox_results]`` of the one image."""
+        -> ``[bbox_results]`` of the one image; with ``return_device_dets``
+        ``([bbox_results], [(dets, labels)])`` as ``simple_test``."""
         if not hasattr(self.bbox_head, 'aug_test'):
             raise NotImplementedError(
                 f'{type(self.bbox_head).__name__} does not support test-time '
@@ -128,7 +135,13 @@ class SingleStageDetector(nn.Module):
                     'image 0 of each view only (dense_test_mixins.py:71), '
                     f'got a view batch of {img.shape[0]}')
         feats = self.extract_feats(imgs)
-        return [self.bbox_head.aug_test(feats, img_metas, rescale=rescale)]
+        if not return_device_dets:
+            return [self.bbox_head.aug_test(feats, img_metas,
+                                            rescale=rescale)]
+        result, dets = self.bbox_head.aug_test(feats, img_metas,
+                                               rescale=rescale,
+                                               return_device_dets=True)
+        return [result], [dets]
 
     def forward_test(self, imgs, img_metas, **kwargs):
         """base.py:120-167: outer lists = test-time augmentations."""
@@ -151,6 +164,43 @@ class SingleStageDetector(nn.Module):
             return self.forward_train(img, img_metas, **kwargs)
         with torch.no_grad():
             return self.forward_test(img, img_metas, **kwargs)
+
+    def show_result(self, img, result, score_thr=0.3, out_file=None,
+                    class_names=None, bbox_color=(72, 101, 241),
+                    text_color=(255, 255, 255), thickness=2, font_scale=1):
+        """base.py:270-355 without a window: ``result`` (per-class (k, 5)
+        arrays, or a ``(bbox, segm)`` tuple whose bbox part is used) drawn over
+        ``img`` (a path, or a BGR (H, W, 3) uint8 array) on the device --
+        outlines by ``ld_draw_boxes``, each kept detection's
+        ``f'{class_name}|{score:.02f}'`` by ``ld_draw_labels``.  Kept means
+        ``score > score_thr`` when ``score_thr > 0``, else every detection
+        (core/visualization/image.py:81-84).  ``class_names`` defaults to
+        ``self.CLASSES``.  Colors are BGR like the image.  With ``out_file`` a
+        PNG is written (RGB, ``write_png``).  -> the drawn BGR image, numpy."""
+        import numpy as np
+        from . import analyze_results as A
+        if isinstance(img, str):
+            from .dataloader import imread
+            img = imread(img)
+        bbox_result = result[0] if isinstance(result, tuple) else result
+        bboxes = np.vstack(bbox_result).astype(np.float32).reshape(-1, 5)
+        labels = np.concatenate([np.full(b.shape[0], i, dtype=np.int32)
+                                 for i, b in enumerate(bbox_result)])
+        if score_thr > 0:
+            keep = bboxes[:, 4] > score_thr
+            bboxes, labels = bboxes[keep], labels[keep]
+        if class_names is None:
+            class_names = getattr(self, 'CLASSES', None)
+        out = A.draw_gt_det_bboxes(
+            img, np.zeros((0, 4), np.float32), bboxes, score_thr=-np.inf,
+            thickness=thickness, det_color=bbox_color,
+            class_names=class_names, labels=labels, text_color=text_color,
+            font_scale=font_scale).cpu().numpy()
+        if out_file is not None:
+            os.makedirs(os.path.dirname(os.path.abspath(out_file)),
+                        exist_ok=True)
+            A.write_png(out_file, out[:, :, ::-1])
+        return out
 
     def _parse_losses(self, losses):
         """base.py:185-218.  Same keys and values; computed on the device in

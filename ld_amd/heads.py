@@ -207,10 +207,13 @@ class BBoxTestMixin:
     device call (ld_aug_merge_nms) maps every view back to the original image,
     merges them view-major and runs multiclass_nms over the merged set."""
 
-    def aug_test(self, feats, img_metas, rescale=False):
+    def aug_test(self, feats, img_metas, rescale=False,
+                 return_device_dets=False):
         """``feats``: per view the FPN levels of ONE image; ``img_metas``: per
         view a one-element list of metas (img_shape, scale_factor, flip,
-        flip_direction).  -> bbox2result per-class arrays of the image."""
+        flip_direction).  -> bbox2result per-class arrays of the image; with
+        ``return_device_dets`` ``(arrays, (dets (k, 5), labels (k,)))``, the
+        merged device detections beside them."""
         from .core import bbox2result
         cfg = self.test_cfg
         if cfg is None:
@@ -245,7 +248,8 @@ class BBoxTestMixin:
             views, score_thr=get('score_thr'), iou_thr=nms['iou_threshold'],
             max_per_img=get('max_per_img'), voting=voting, rescale=rescale,
             num_classes=self.cls_out_channels)
-        return bbox2result(dets, labels, self.num_classes)
+        result = bbox2result(dets, labels, self.num_classes)
+        return (result, (dets, labels)) if return_device_dets else result
 
 
 ATSS_LOSS_KEYS = ['loss_cls', 'loss_bbox', 'loss_ld', 'loss_ld_neg',

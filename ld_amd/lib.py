@@ -260,7 +260,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -397,6 +397,9 @@ SIGNATURES = {
     'ld_rank_images': (C.c_int, [_i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_draw_boxes': (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _f32,
                                 _i32, C.c_uint32, C.c_uint32, _vp]),
+    'ld_draw_labels': (C.c_int, [_vp, _i32, _i32, _vp, _vp, _i32, _i32,
+                                 C.c_uint32, C.c_uint32, _vp]),
+    'ld_font_glyph': (C.c_int, [_i32, _i32]),
     'ld_eval_recalls_workspace_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'ld_eval_recalls_match': (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i32,
                                         _i32, _i32, _i32, _vp, _i32, _vp,

@@ -109,7 +109,8 @@ class DevicePipeline:
     (k,) annotations; returns the dict the detector's ``forward_train`` takes:
     ``img`` (N, 3, Hpad, Wpad) fp32 on the device, ``img_metas`` (the keys of
     Collect's default meta_keys that the heads read), ``gt_bboxes`` /
-    ``gt_labels`` lists of device tensors.
+    ``gt_labels`` lists of device tensors, and ``gt_bboxes_ignore`` when the
+    optional ``gt_bboxes_ignore=`` is given (transformed like ``gt_bboxes``).
     """
 
     def __init__(self, img_scale=(1333, 800), keep_ratio=True, flip_ratio=0.5,
@@ -279,7 +280,7 @@ class DevicePipeline:
 
     # -- the batch ------------------------------------------------------------
     def __call__(self, images, gt_bboxes=None, gt_labels=None, rng=np.random,
-                 plans=None, stream=None):
+                 plans=None, stream=None, gt_bboxes_ignore=None):
         from . import lib as L
         lib = L.get_lib()  # raises when the HIP library is missing
         if self.device.type != 'cuda':
@@ -338,6 +339,11 @@ class DevicePipeline:
                 torch.from_numpy(self.transform_boxes(b, p)).to(
                     self.device, non_blocking=True)
                 for b, p in zip(gt_bboxes, plans)]
+        if gt_bboxes_ignore is not None:  # transformed like gt_bboxes
+            result['gt_bboxes_ignore'] = [
+                torch.from_numpy(self.transform_boxes(b, p)).to(
+                    self.device, non_blocking=True)
+                for b, p in zip(gt_bboxes_ignore, plans)]
         if gt_labels is not None:
             result['gt_labels'] = [
                 torch.as_tensor(np.asarray(l, np.int64)).to(

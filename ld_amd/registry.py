@@ -10,7 +10,7 @@ import inspect
 
 __all__ = [
     'Registry', 'build_from_cfg', 'BACKBONES', 'NECKS', 'HEADS', 'LOSSES',
-    'DETECTORS', 'BBOX_ASSIGNERS', 'BBOX_SAMPLERS', 'BBOX_CODERS',
+    'DETECTORS', 'DATASETS', 'BBOX_ASSIGNERS', 'BBOX_SAMPLERS', 'BBOX_CODERS',
     'ANCHOR_GENERATORS', 'IOU_CALCULATORS', 'build_backbone', 'build_neck',
     'build_head', 'build_loss', 'build_detector', 'build_assigner',
     'build_sampler', 'build_bbox_coder', 'build_anchor_generator',
@@ -108,6 +108,7 @@ BBOX_SAMPLERS = Registry('bbox_sampler')
 BBOX_CODERS = Registry('bbox_coder')
 ANCHOR_GENERATORS = Registry('Anchor generator')
 IOU_CALCULATORS = Registry('IoU calculator')
+DATASETS = Registry('dataset')  # mmdet/datasets/builder.py:22
 
 
 def build(cfg, registry, default_args=None):

@@ -7,10 +7,17 @@ step, restated for ``SGDTrainer`` / ``AutoStepper``.
     EpochRunner(trainer, cfg, work_dir).run(lambda epoch: batches_of(epoch))
 
 ``make_epoch_batches(epoch)`` returns the epoch's device batches (dicts of
-``img``, ``img_metas``, ``gt_bboxes``, ``gt_labels``): datasets, image loading
-and evaluation stay with the caller.  Config keys read: ``runner.max_epochs``
-(or the older ``total_epochs``), ``log_config.interval``,
-``checkpoint_config.interval`` and ``resume_from``.
+``img``, ``img_metas``, ``gt_bboxes``, ``gt_labels``); a
+``dataloader.DeviceDataLoader`` over a ``datasets`` dataset is one.  Config
+keys read: ``runner.max_epochs`` (or the older ``total_epochs``),
+``log_config.interval``, ``checkpoint_config.interval`` and ``resume_from``.
+
+``val=(loader, dataset, eval_cfg)`` is mmdet's ``EvalHook``: after every
+``eval_cfg['interval']`` (default 1) epochs ``apis.single_gpu_test`` runs over
+the test-mode ``loader`` and ``dataset.evaluate(results, **eval_cfg)`` (without
+``interval``) gives the metrics, appended to the log as one ``mode='val'``
+line (``epoch``, ``iter``, ``lr`` and the metrics).  Without ``val`` nothing
+changes.
 
 Every ``log_config.interval`` iterations one JSON line goes to
 ``work_dir/train.log.json``: ``mode, epoch, iter`` (1-based within the epoch,
@@ -41,7 +48,7 @@ def _get(cfg, key, default=None):
 
 class EpochRunner:
 
-    def __init__(self, trainer_or_stepper, cfg, work_dir):
+    def __init__(self, trainer_or_stepper, cfg, work_dir, val=None):
         self.stepper = trainer_or_stepper
         self.trainer = getattr(trainer_or_stepper, 'trainer', trainer_or_stepper)
         self.cfg = cfg
@@ -54,6 +61,29 @@ class EpochRunner:
         self.resume_from = _get(cfg, 'resume_from')
         self.log_path = os.path.join(self.work_dir, 'train.log.json')
         os.makedirs(self.work_dir, exist_ok=True)
+        self.val = val
+        self.val_records = []
+        if val is not None:
+            self.val_interval = int(_get(val[2], 'interval', 1))
+
+    def validate(self, epoch_done):
+        """One evaluation pass -> the ``mode='val'`` record it logged."""
+        from .apis import single_gpu_test
+        loader, dataset, eval_cfg = self.val
+        kw = {k: v for k, v in dict(eval_cfg or {}).items() if k != 'interval'}
+        model = self.trainer.model
+        was_training = model.training
+        results = single_gpu_test(model, loader)
+        model.train(was_training)
+        metrics = dataset.evaluate(results, **kw)
+        rec = dict(mode='val', epoch=epoch_done, iter=len(loader),
+                   lr=float(self.trainer.lr))
+        rec.update({k: (v if isinstance(v, str) else float(v))
+                    for k, v in metrics.items()})
+        with open(self.log_path, 'a') as f:
+            f.write(json.dumps(rec) + '\n')
+        self.val_records.append(rec)
+        return rec
 
     def _log(self, epoch, inner, out):
         rec = dict(mode='train', epoch=epoch + 1, iter=inner + 1,
@@ -81,6 +111,8 @@ class EpochRunner:
     def _end_epoch(self, epoch):
         if (epoch + 1) % self.ckpt_interval == 0:
             self.save(epoch + 1)
+        if self.val is not None and (epoch + 1) % self.val_interval == 0:
+            self.validate(epoch + 1)
 
     def run(self, make_epoch_batches, max_epochs=None):
         """Train from ``trainer.epoch`` (after ``resume_from``, if set) to
