@@ -312,10 +312,7 @@ class DeformConv2dPack(nn.Module):
         if self.deform_groups != 1 or self.dilation != (1, 1):
             raise NotImplementedError(
                 'trainable DCN: deform_groups = 1 and no dilation are built')
-        if isinstance(x3, Y.C8Act) or Y._unwritten(x3):
-            raise NotImplementedError(
-                'trainable DCN needs its input in fp32; this one exists only as '
-                'a C8 image (C8Act / trunk_c8_scope)')
+        Y._fp32_readable(x3, 'trainable DCN input')
         if len(levels) != 1:
             raise NotImplementedError('DCN on level-concatenated tensors')
         (h, w), = levels

@@ -121,13 +121,6 @@ def bump_param_generation():
     _PARAM_GEN[0] += 1
 
 
-def _dev_f32(t, name):
-    L.require_device(t, torch.float32, name)
-    if not t.is_contiguous():
-        raise L.LdError(f'{name} must be contiguous')
-    return t
-
-
 def out_size(h, k, s, p):
     return (h + 2 * p - k) // s + 1
 
@@ -272,7 +265,7 @@ _DRAW_C8_ONLY = _switch('LD_DRAW_C8_ONLY')  # no fp32 d(raw) in the fused nodes
 # ---- the C8 questions of a conv's backward, each asked in ONE place ----------
 # ConvBnActFn.forward builds its ``lean`` decision from the same predicates its
 # backward uses: the two cannot drift apart (a backward that expects a tensor
-# the forward never wrote is the ``_ld_unwritten`` hazard).
+# the forward never wrote is the image-only placeholder hazard).
 def _wgrad_takes_c8(cin, cout):
     """This conv's weight gradient takes both operands as C8 images
     (ld_conv_bf16_wgrad_c8)."""
@@ -321,7 +314,27 @@ if _C8_ALL:
     _C8[0] = True
 
 
+# ---------------------------------------------------------------------------
+# activation forms: begin
+# ---------------------------------------------------------------------------
+# In bf16 mode an (N, C, P) activation exists in one of three forms:
+#   fp32          a plain tensor;
+#   fp32 + image  the same, with its bf16 C8 image (N, C/8, P, 8) cached on it
+#                 under (version, data_ptr) by the producer's own launch or by the
+#                 first conv that wanted it;
+#   image-only    no fp32 values: a ``C8Act`` (not a tensor: frozen chains under
+#                 no_grad) or a PLACEHOLDER, the never-written fp32 tensor autograd
+#                 needs as a node's output, carrying the image (trunk_c8_scope).
+# Only this section touches the two tensor attributes or chooses between an image
+# and a conversion.  Everything below asks ``_dev_f32`` / ``_fp32_readable`` for an
+# fp32 operand (image-only is refused there: nobody reads the unwritten memory)
+# and ``_c8_operand`` for a C8 one.
+class ImageOnlyError(L.LdError, NotImplementedError):
+    """A consumer needs the fp32 values of an image-only activation."""
+
+
 def _c8_cached(x3):
+    """The cached C8 image of tensor ``x3``, or None."""
     hit = getattr(x3, '_ld_c8', None)
     if hit is None:
         # a reshape-view of the tensor the producer attached the image to (a stage
@@ -336,30 +349,112 @@ def _c8_cached(x3):
     return None
 
 
+def _attach_c8(t, buf):
+    """Cache image ``buf`` on ``t`` (None: forget the one it has)."""
+    try:
+        t._ld_c8 = ((t._version, t.data_ptr()), buf)
+    except AttributeError:
+        pass
+
+
+def _image_only_output(shape, image):
+    """The fp32 placeholder an autograd node returns for an output that exists
+    only as ``image``: allocated on the image's device, never written."""
+    t = torch.empty(tuple(shape), dtype=torch.float32, device=image.device)
+    _attach_c8(t, image)
+    t._ld_unwritten = True
+    return t
+
+
+def _unwritten(t):
+    """Whether ``t`` is an image-only placeholder or a view of one.  The views
+    split_levels / level_views and ``x3.view(n, c, h, w)`` hand out carry no
+    attribute of their own: they stay flagged through ``_base``."""
+    if not isinstance(t, torch.Tensor):
+        return False
+    if getattr(t, '_ld_unwritten', False):
+        return True
+    b = t._base
+    return b is not None and getattr(b, '_ld_unwritten', False)
+
+
+def _fp32_readable(t, name):
+    """``t``, or an ImageOnlyError when consumer ``name`` would read fp32 values
+    that do not exist."""
+    if isinstance(t, C8Act) or _unwritten(t):
+        raise ImageOnlyError(
+            f'{name}: this activation exists only as a C8 image (C8Act / '
+            'trunk_c8_scope) and this consumer reads its fp32 values')
+    return t
+
+
+def _dev_f32(t, name, image_ok=False):
+    """The validated fp32 operand ``t`` of consumer ``name``: readable (checked
+    first), on the device, fp32, contiguous.  ``image_ok``: the caller's kernel
+    takes ``_c8_operand(t)``, an image-only activation passes as it is."""
+    if isinstance(t, C8Act) or _unwritten(t):
+        return t if image_ok else _fp32_readable(t, name)
+    L.require_device(t, torch.float32, name)
+    if not t.is_contiguous():
+        raise L.LdError(f'{name} must be contiguous')
+    return t
+
+
 C8_STATS = dict(converted=0, reused=0)
 
 
 def to_c8(x3):
     """bf16 (N, C/8, P, 8) image of an fp32 (N, C, P) tensor (cached)."""
-    key = (x3._version, x3.data_ptr())
     img = _c8_cached(x3)
     if img is not None:
         C8_STATS['reused'] += 1
         return img
-    if _unwritten(x3):
-        raise L.LdError('to_c8: this activation exists only as a C8 image that '
-                        'is no longer attached to the tensor (trunk_c8_scope)')
+    _fp32_readable(x3, 'to_c8')  # a placeholder whose image is no longer attached
     C8_STATS['converted'] += 1
     N, Cc, P = x3.shape
     out = torch.empty(N * Cc * P, dtype=torch.bfloat16, device=x3.device)
     L.check(L.get_lib().ld_conv_to_c8(L.ptr(x3), N, Cc, P, L.ptr(out),
                                       L.stream_ptr(x3.device)),
             'ld_conv_to_c8')
-    try:
-        x3._ld_c8 = (key, out)
-    except AttributeError:
-        pass
+    _attach_c8(x3, out)
     return out
+
+
+def _c8_operand(x):
+    """The C8 image a conv-family kernel reads for activation ``x``: the buffer
+    of a C8Act, the cached image of a tensor, a conversion launch otherwise."""
+    return x.buf if isinstance(x, C8Act) else to_c8(x)
+
+
+def _residual_operands(r):
+    """(fp32 tensor, C8 image) of a conv epilogue's residual ``r``: the image
+    of an image-only activation, the validated tensor otherwise."""
+    if r is None:
+        return None, None
+    if isinstance(r, C8Act) or _unwritten(r):
+        return None, _c8_operand(r)
+    return _dev_f32(r, 'residual'), None
+
+
+def _c8_writable(c, P, vec=4, ptrs=()):
+    """Whether a norm / pack kernel can write the C8 image of a (c, P) map in
+    its own launch: bf16 mode with the C8 path on, whole 32-channel blocks,
+    ``vec`` positions per store (4: the norm kernels, 1: the level packers) and
+    every tensor the kernel takes 16 bytes at a time (``ptrs``) aligned."""
+    return _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and \
+        P % vec == 0 and all(p % 16 == 0 for p in ptrs)
+
+
+def _save_conv_input(ctx, x):
+    """Forward half of "keep the conv input for backward": returns what
+    save_for_backward holds for ``x`` (a C8Act is not a tensor: its image)."""
+    ctx.x8 = x if isinstance(x, C8Act) else None
+    return x if ctx.x8 is None else x.buf
+
+
+def _saved_conv_input(ctx, saved):
+    """Backward half: the activation ``_save_conv_input`` was given."""
+    return saved if ctx.x8 is None else ctx.x8
 
 
 class C8Act:
@@ -413,6 +508,13 @@ class C8Act:
         return self.buf.view(n, c // 8, -1, 8).permute(0, 1, 3, 2).reshape(
             self.shape).float()
 
+    def contiguous(self):
+        return self
+
+
+# ---------------------------------------------------------------------------
+# activation forms: end
+# ---------------------------------------------------------------------------
 
 # inside this scope the fused frozen conv+BN+ReLU launches keep only the C8
 # image of their output (resnet.ResNet.forward opens it for a frozen teacher)
@@ -439,13 +541,13 @@ def c8_only_available(channels):
 # Inside this scope (the KD detector opens it around the student's backbone in
 # bf16 mode) a lean ConvBnActFn keeps its output z ONLY as the bf16 C8 image: the
 # fp32 tensor autograd needs as the node's output is allocated but never written
-# (``_ld_unwritten``), every consumer on the step takes the image -- the next conv
+# (``_image_only_output``), every consumer on the step takes the image -- the next conv
 # as its operand, the next block's conv3 as its residual (ld_conv_epilogue_t.
 # residual_c8: the identity path is then bf16 from block to block, as in the
 # reference's fp16 mode, mmcv auto_fp16 on the backbone), the BN backward as its
-# ReLU mask, the neck's lateral convs as their operand.  A consumer that would read
-# the fp32 values raises (conv_forward_raw, to_c8, _conv_backward): no silent
-# garbage.  LD_TRUNK_C8=0 keeps the fp32 copy.
+# ReLU mask, the neck's lateral convs as their operand.  A consumer in this module
+# that would read the fp32 values raises (``_dev_f32``): no silent garbage.
+# LD_TRUNK_C8=0 keeps the fp32 copy.
 _TRUNK_C8 = [False]
 _TRUNK_C8_ON = [os.environ.get('LD_TRUNK_C8', '1') == '1']
 
@@ -458,17 +560,6 @@ class trunk_c8_scope:
 
     def __exit__(self, *exc):
         _TRUNK_C8[0] = self.prev
-
-
-def _unwritten(t):
-    """Whether ``t`` (or the tensor it is a reshape view of) is an fp32
-    placeholder whose values were never written (trunk_c8_scope)."""
-    if not isinstance(t, torch.Tensor):
-        return False
-    if getattr(t, '_ld_unwritten', False):
-        return True
-    b = t._base
-    return b is not None and getattr(b, '_ld_unwritten', False)
 
 
 def _register(reg, t):
@@ -732,13 +823,13 @@ _FAMILIES = (
 
 
 def _epilogue(bias=None, scale=None, shift=None, residual=None, relu=False,
-              y_c8=None):
+              y_c8=None, residual_c8=None):
     ep = L.ConvEpilogueT()
     ep.y_c8 = y_c8.data_ptr() if y_c8 is not None else None
     ep.residual_c8 = None
-    if isinstance(residual, C8Act):
-        L.keep(residual.buf)
-        ep.residual_c8, residual = residual.buf.data_ptr(), None
+    if residual_c8 is not None:
+        L.keep(residual_c8)
+        ep.residual_c8 = residual_c8.data_ptr()
     ep.y_raw = None
     ep.bias = bias.data_ptr() if bias is not None else None
     ep.scale = scale.data_ptr() if scale is not None else None
@@ -756,13 +847,7 @@ def conv_forward_raw(x3, w, stride, pad, levels, bias=None, scale=None,
     bf16 mode also write the C8 image of y from the epilogue (for a y that goes
     straight into another conv: the frozen conv+BN+ReLU chains).  ``c8_only``:
     write ONLY that image and return a C8Act.  x3 / residual may be C8Acts."""
-    lib = L.get_lib()
     in8 = isinstance(x3, C8Act)
-    if not in8:
-        _dev_f32(x3, 'conv input')
-    if _unwritten(residual):
-        # a trunk activation that exists only as its C8 image (trunk_c8_scope)
-        residual = C8Act(to_c8(residual), residual.shape)
     N, cin, P = x3.shape
     cout, cin_w, kh, kw = w.shape
     if cin_w != cin:
@@ -772,23 +857,26 @@ def conv_forward_raw(x3, w, stride, pad, levels, bias=None, scale=None,
         raise L.LdError(f'conv: input has {P} positions, levels say {d.Pin}')
     smallc = cin < 16
     bf16 = not smallc and _use_bf16(cin)
-    res8 = isinstance(residual, C8Act)
-    if (in8 or res8 or c8_only) and not (
+    has_res = residual is not None
+    if has_res:
+        assert tuple(residual.shape) == (N, cout, d.Pout)
+    # an image-only residual (C8Act, trunk_c8_scope placeholder) comes as res8
+    residual, res8 = _residual_operands(residual)
+    if (in8 or res8 is not None or c8_only) and not (
             bf16 and _C8[0] and cout % 32 == 0 and (not in8 or cin % 32 == 0)):
         raise L.LdError('conv: C8-only activations need bf16 mode, the C8 path '
                         'and channel counts that are multiples of 32')
+    c8 = in8 or (bf16 and _use_c8(cin, kh, stride, N * d.Pout, x3))
+    _dev_f32(x3, 'conv input', image_ok=c8)
+    lib = L.get_lib()
     wt_fwd, _ = weight_images(w, False, smallc, bf16)
     y3 = None if c8_only else torch.empty(
         (N, cout, d.Pout), dtype=torch.float32, device=x3.device)
-    if residual is not None:
-        if not res8:
-            _dev_f32(residual, 'residual')
-        assert tuple(residual.shape) == (N, cout, d.Pout)
     y_c8 = None
     if (emit_c8 or c8_only) and bf16 and _C8[0] and cout % 32 == 0:
         y_c8 = torch.empty(N * cout * d.Pout, dtype=torch.bfloat16,
                            device=x3.device)
-    ep = _epilogue(bias, scale, shift, residual, relu, y_c8)
+    ep = _epilogue(bias, scale, shift, residual, relu, y_c8, res8)
     if y_raw is not None:
         # second output: the conv result before the affine (ConvBnActFn)
         if smallc or c8_only or tuple(y_raw.shape) != (N, cout, d.Pout):
@@ -796,10 +884,6 @@ def conv_forward_raw(x3, w, stride, pad, levels, bias=None, scale=None,
                             'same shape')
         ep.y_raw = y_raw.data_ptr()
         L.keep(y_raw)
-    c8 = in8 or (bf16 and _use_c8(cin, kh, stride, N * d.Pout, x3))
-    if not c8 and _unwritten(x3):
-        raise L.LdError('conv: the input exists only as a C8 image '
-                        '(trunk_c8_scope) and this conv takes fp32 operands')
     if y_raw_c8 is not None:
         # the pre-affine result as a bf16 C8 image (ConvBnActFn, lean form)
         if not c8 or y_raw is not None or bias is not None or cout % 8 or \
@@ -813,14 +897,14 @@ def conv_forward_raw(x3, w, stride, pad, levels, bias=None, scale=None,
     # the small-channel stem has one entry point of its own and no tuner
     fn = lib.ld_conv_forward_smallc if smallc else getattr(lib, fam.forward)
     with _timed('conv_fwd' + fam.timed, d,
-                fused=(int(residual is not None), int(y_raw is not None))):
+                fused=(int(has_res), int(y_raw is not None))):
         # the conversion launch is part of the conv's measured time
-        xin = x3.buf if in8 else to_c8(x3) if c8 else x3
+        xin = _c8_operand(x3) if c8 else x3
         if not smallc:
             tune = getattr(lib, fam.tune_forward)
             _tune_once(fam.tune + 'forward', d,
-                       (bias is not None, scale is not None,
-                        residual is not None, bool(relu)),
+                       (bias is not None, scale is not None, has_res,
+                        bool(relu)),
                        lambda: tune(C.byref(d), L.ptr(xin), L.ptr(wt_fwd),
                                     C.byref(ep), L.ptr(y3),
                                     L.stream_ptr(x3.device)))
@@ -1292,7 +1376,7 @@ def _conv_dgrad(lib, w, dy, d, meta, addend):
         fam.tune_dgrad, fam.dgrad, fam.dgrad_acc))
     with _timed('conv_dgrad' + fam.timed, d,
                 fused=(int(addend is not None), 0)):
-        dyin = dy.buf if dy8 else to_c8(dy) if c8 else dy_x
+        dyin = _c8_operand(dy) if c8 else dy_x
         _tune_once(fam.tune + 'dgrad', d_x, (),
                    lambda: tune(C.byref(d_x), L.ptr(dyin),
                                 L.ptr(wt_bwd), L.ptr(dx), st))
@@ -1372,9 +1456,8 @@ def _wgrad_dispatch(launch, side, ws, need, defer, operands, device):
     _WGRAD_PENDING[0] = True
 
 
-def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
+def _conv_wgrad(lib, x3, w, dy, d, pw, c8w):
     """The weight gradient of _conv_backward; None: into the gradient arena."""
-    dy8 = isinstance(dy, C8Act)
     cin = d.Cin
     st = L.stream_ptr(dy.device)
     # one parameter: direct whenever it has an arena slice (accumulate = 1)
@@ -1420,8 +1503,7 @@ def _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w):
     with _timed('conv_wgrad' + fam.timed, d):
         # operand images are produced on the main stream (cached ones cost
         # nothing); the wgrad itself may go to the side stream
-        xw, dyw = ((x3.buf if x8 is not None else to_c8(x3)),
-                   dy.buf if dy8 else to_c8(dy)) if c8w else (x3, dy)
+        xw, dyw = (_c8_operand(x3), _c8_operand(dy)) if c8w else (x3, dy)
         _wgrad_dispatch(_launch, side, ws, need, defer, (xw, dyw), dy.device)
     return _grad_done((pw, ), (dw, ), direct)[0]
 
@@ -1453,45 +1535,40 @@ def _conv_bias_grad(lib, dy, d, pb):
 def _conv_backward(x3, x8, w, dy, meta, params, need_x, need_w, need_b,
                    addend=None):
     """Data / weight / bias gradients of a conv (shared by ConvFn and the fused
-    ConvBnActFn).  x3: the saved input tensor, or -- x8 given -- its C8Act.
+    ConvBnActFn).  x3: the conv's input activation in any form (``x8``, when
+    given, is that activation: the conv census replays the two-argument form).
     Returns (dx, dw, db); dw / db are None when they went straight into the
     gradient arena.  dy may be a C8Act (the BN backward wrote only the bf16 C8
     image of the conv's output gradient): then both gradients must be C8
     kernels, and the conv has no bias."""
-    lib = L.get_lib()
     if x8 is not None:
         x3 = x8
     stride, pad, levels, has_bias = meta
     dy8 = isinstance(dy, C8Act)
-    if not dy8:
-        dy = dy.contiguous()
+    dy = dy.contiguous()
     N, cin, _ = x3.shape
     cout, _, kh, kw = w.shape
     d, _ = conv_desc(N, cin, cout, kh, kw, stride, pad, levels)
     dx = dw = db = None
     # bf16 + C8: the weight gradient takes both operands as C8 images
-    # (ld_conv_bf16_wgrad_c8); converting dy first lets the data gradient
-    # below use the same image
+    # (ld_conv_bf16_wgrad_c8)
     c8w = need_w and _wgrad_takes_c8(cin, cout)
-    if c8w and not dy8:
-        to_c8(dy)
     if dy8 and ((need_w and not c8w) or (has_bias and need_b) or
                 (need_x and not _use_bf16(cout))):
         raise L.LdError('conv backward: a C8-only output gradient needs the C8 '
                         'data- and weight-gradient kernels and no bias')
-    if need_w and not c8w and _unwritten(x3):
-        raise L.LdError('conv backward: the saved input exists only as a C8 '
-                        'image (trunk_c8_scope); its weight gradient needs the '
-                        'C8 wgrad kernel')
-    if x8 is not None and not c8w:
-        raise L.LdError('a C8-only activation feeds this conv: its weight '
-                        'gradient needs the C8 wgrad kernel (bf16 mode, '
-                        'channel counts % 32 == 0, LD_WGRAD_C8 on)')
+    # only the C8 weight gradient (bf16 mode, channel counts % 32 == 0,
+    # LD_WGRAD_C8 on) can take an image-only input
+    if need_w:
+        _dev_f32(x3, 'conv backward: saved input', image_ok=c8w)
+    lib = L.get_lib()
+    if c8w:  # converting dy first lets the data gradient use the same image
+        _c8_operand(dy)
     pw, pb = params
     if need_x:
         dx = _conv_dgrad(lib, w, dy, d, meta, addend)
     if need_w:
-        dw = _conv_wgrad(lib, x3, x8, w, dy, d, pw, c8w)
+        dw = _conv_wgrad(lib, x3, w, dy, d, pw, c8w)
     if has_bias and need_b:
         db = _conv_bias_grad(lib, dy, d, pb)
     return dx, dw, db
@@ -1505,15 +1582,11 @@ class ConvFn(torch.autograd.Function):
         y3, out_levels = conv_forward_raw(x3, w, stride, pad, levels,
                                           bias=bias)
         # x3 may be a C8Act (bf16 mode: the output of the student's frozen,
-        # C8-only stages): not a tensor -- keep its bf16 image, no gradient
-        ctx.x8 = x3 if isinstance(x3, C8Act) else None
-        if ctx.x8 is not None:
-            ctx.save_for_backward(x3.buf, w)
-        else:
-            ctx.save_for_backward(x3, w)
+        # C8-only stages): no gradient, and no fan (fan_in skips non-tensors)
+        ctx.save_for_backward(_save_conv_input(ctx, x3), w)
         ctx.meta = (stride, pad, levels, bias is not None)
         ctx.params = (w, bias)
-        ctx.fan = fan_in(ctx, 0, x3) if ctx.x8 is None else None
+        ctx.fan = fan_in(ctx, 0, x3)
         _note_use(w, bias)
         return y3
 
@@ -1521,7 +1594,7 @@ class ConvFn(torch.autograd.Function):
     def backward(ctx, dy):
         x3, w = ctx.saved_tensors
         dx, dw, db = _conv_backward(
-            x3, ctx.x8, w, dy, ctx.meta, ctx.params,
+            _saved_conv_input(ctx, x3), None, w, dy, ctx.meta, ctx.params,
             ctx.needs_input_grad[0], ctx.needs_input_grad[1],
             ctx.needs_input_grad[2], addend=fan_take(ctx.fan))
         return fan_give(ctx.fan, dx), dw, db, None, None, None
@@ -1579,36 +1652,36 @@ def _bn_prepare(gamma, beta, mean, var, eps):
     return buf[0], buf[1], buf[2]
 
 
-def _bn_act_forward_launch(x3, residual, scale, shift, N, c, P, relu, y):
+def _bn_act_forward(x3, gamma, beta, mean, var, eps, residual, relu):
+    """y = relu?(BN_eval(x3) + residual): (y, scale, rstd).  bf16 mode: the C8
+    image of y comes out of the same launch where the geometry has one."""
     lib = L.get_lib()
-    aligned = x3.data_ptr() % 16 == 0 and (
-        residual is None or residual.data_ptr() % 16 == 0)
-    y_c8 = _c8_side_output(y) if aligned else None
-    if y_c8 is not None:
+    N, c, P = x3.shape
+    scale, shift, rstd = bn_prepare(gamma, beta, mean, var, eps)
+    y = torch.empty_like(x3)
+    if _c8_writable(c, P, ptrs=[t.data_ptr() for t in (x3, residual, y)
+                                if t is not None]):
+        y_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=x3.device)
         L.check(lib.ld_bn_act_forward_c8(
             L.ptr(x3), L.ptr(residual), L.ptr(scale), L.ptr(shift), N, c, P,
             1 if relu else 0, L.ptr(y), L.ptr(y_c8),
             L.stream_ptr(x3.device)), 'ld_bn_act_forward_c8')
         _attach_c8(y, y_c8)
-        return
-    L.check(lib.ld_bn_act_forward(L.ptr(x3), L.ptr(residual), L.ptr(scale),
-                                  L.ptr(shift), N, c, P, 1 if relu else 0,
-                                  L.ptr(y), L.stream_ptr(x3.device)),
+    else:
+        L.check(lib.ld_bn_act_forward(
+            L.ptr(x3), L.ptr(residual), L.ptr(scale), L.ptr(shift), N, c, P,
+            1 if relu else 0, L.ptr(y), L.stream_ptr(x3.device)),
             'ld_bn_act_forward')
+    return y, scale, rstd
 
 
 class BnActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, gamma, beta, mean, var, eps, residual, relu):
-        lib = L.get_lib()
-        _dev_f32(x3, 'bn input')
-        N, c, P = x3.shape
-        scale, shift, rstd = bn_prepare(gamma, beta, mean, var, eps)
-        y = torch.empty_like(x3)
-        if residual is not None:
-            _dev_f32(residual, 'bn residual')
-        _bn_act_forward_launch(x3, residual, scale, shift, N, c, P, relu, y)
+        # (bn_act validated x3 and the residual)
+        y, scale, rstd = _bn_act_forward(x3, gamma, beta, mean, var, eps,
+                                         residual, relu)
         ctx.save_for_backward(x3, y, scale, mean, rstd)
         ctx.relu = relu
         ctx.has_res = residual is not None
@@ -1654,9 +1727,8 @@ def _bn_act_backward(dy, x3, y, scale, mean, rstd, relu, params, need_x,
     else:
         N, c, P = x3.shape
         dx8_only = bool(dx_c8_only and need_x and _bn_c8_covers(N, P) and
-                        all(t.data_ptr() % 16 == 0 for t in (dy, y, x3)) and
-                        _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
-                        P % 4 == 0)
+                        _c8_writable(c, P, ptrs=[t.data_ptr()
+                                                 for t in (dy, y, x3)]))
 
         def fresh():
             return torch.empty_like(x3)
@@ -1686,12 +1758,10 @@ def _bn_act_backward(dy, x3, y, scale, mean, rstd, relu, params, need_x,
         if dx8_only and not al16:  # (a fresh dres is always aligned; stay correct)
             dx, dx8_only = torch.empty_like(x3), False
             al16 = dx.data_ptr() % 16 == 0
-        if dx8_only:
+        dx_c8 = None
+        if dx8_only or (dx is not None and _bn_c8_covers(N, P) and al16 and
+                        _c8_writable(c, P)):
             dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=dev)
-        elif dx is not None and _bn_c8_covers(N, P) and al16:
-            dx_c8 = _c8_side_output(dx)
-        else:
-            dx_c8 = None
     # which of the three kernels; also ld_bn_act_backward_nsplit's mode
     mode = 2 if lean else 1 if dx_c8 is not None else 0
     if mode:
@@ -1749,44 +1819,35 @@ class ConvBnActFn(torch.autograd.Function):
         lean = _bn_lean_geometry(N, cin, cout, P) and \
             (isinstance(x3, C8Act) or
              _use_c8(cin, kh, stride, N * P, x3))
-        if lean and _TRUNK_C8[0]:
-            # trunk_c8_scope: z only as its C8 image; the fp32 tensor returned to
-            # autograd is a placeholder nobody reads (see the scope's comment)
-            raw = torch.empty(N * cout * P, dtype=torch.bfloat16,
-                              device=w.device)
-            z8, _ = conv_forward_raw(x3, w, stride, pad, levels, scale=scale,
-                                     shift=shift, residual=residual, relu=relu,
-                                     c8_only=True, y_raw_c8=raw)
-            zimg = z8.buf
-            z = torch.empty((N, cout, P), dtype=torch.float32, device=w.device)
-            _attach_c8(z, zimg)
-            z._ld_unwritten = True
+        # trunk_c8_scope: z only as its C8 image; the fp32 tensor returned to
+        # autograd is a placeholder nobody reads (see the scope's comment)
+        scoped = lean and _TRUNK_C8[0]
+        raw = torch.empty(N * cout * P, dtype=torch.bfloat16, device=w.device) \
+            if lean else torch.empty((N, cout, P), dtype=torch.float32,
+                                     device=w.device)
+        z, _ = conv_forward_raw(x3, w, stride, pad, levels, scale=scale,
+                                shift=shift, residual=residual, relu=relu,
+                                emit_c8=not scoped, c8_only=scoped,
+                                y_raw=None if lean else raw,
+                                y_raw_c8=raw if lean else None)
+        if scoped:
+            zimg = _c8_operand(z)
+            z = _image_only_output(z.shape, zimg)
         elif lean:
-            raw = torch.empty(N * cout * P, dtype=torch.bfloat16,
-                              device=w.device)
-            z, _ = conv_forward_raw(x3, w, stride, pad, levels, scale=scale,
-                                    shift=shift, residual=residual, relu=relu,
-                                    emit_c8=True, y_raw_c8=raw)
             zimg = _c8_cached(z)
             if zimg is None:
                 raise L.LdError('ConvBnActFn: no C8 image on the output')
         else:
-            raw = torch.empty((N, cout, P), dtype=torch.float32,
-                              device=w.device)
-            z, _ = conv_forward_raw(x3, w, stride, pad, levels, scale=scale,
-                                    shift=shift, residual=residual, relu=relu,
-                                    emit_c8=True, y_raw=raw)
             zimg = z  # placeholder: same tensor, nothing extra is kept alive
         ctx.lean = lean
         ctx.oshape = (N, cout, P)
-        ctx.x8 = x3 if isinstance(x3, C8Act) else None
-        ctx.save_for_backward(x3.buf if ctx.x8 is not None else x3, w, raw, z,
-                              scale, mean, rstd, zimg)
+        ctx.save_for_backward(_save_conv_input(ctx, x3), w, raw, z, scale, mean,
+                              rstd, zimg)
         ctx.meta = (stride, pad, levels, False)
         ctx.relu = relu
         ctx.has_res = residual is not None
         ctx.params = (w, gamma, beta)
-        ctx.fan = fan_in(ctx, 0, x3) if ctx.x8 is None else None
+        ctx.fan = fan_in(ctx, 0, x3)
         ctx.fan_res = fan_in(ctx, 7, residual)
         _note_use(w, gamma, beta)
         return z
@@ -1815,8 +1876,8 @@ class ConvBnActFn(torch.autograd.Function):
         dres = fan_give(ctx.fan_res, dres)
         dx = dw = None
         if need_conv:
-            dx, dw, _ = _conv_backward(x3, ctx.x8, w, draw, ctx.meta,
-                                       (pw, None), ng[0], ng[1], False,
+            dx, dw, _ = _conv_backward(_saved_conv_input(ctx, x3), None, w, draw,
+                                       ctx.meta, (pw, None), ng[0], ng[1], False,
                                        addend=fan_take(ctx.fan) if ng[0]
                                        else None)
         return (fan_give(ctx.fan, dx), dw, dgamma, dbeta, None, None, None,
@@ -1839,16 +1900,14 @@ def conv_bn_act(x3, w, gamma, beta, mean, var, eps, stride, pad, levels,
 
 
 def bn_act(x3, gamma, beta, mean, var, eps, residual=None, relu=True):
+    _dev_f32(x3, 'bn input')
+    if residual is not None:
+        _dev_f32(residual, 'bn residual')
     if torch.is_grad_enabled() and (x3.requires_grad or gamma.requires_grad or
                                     (residual is not None and
                                      residual.requires_grad)):
         return BnActFn.apply(x3, gamma, beta, mean, var, eps, residual, relu)
-    lib = L.get_lib()
-    N, c, P = x3.shape
-    scale, shift, _ = bn_prepare(gamma, beta, mean, var, eps)
-    y = torch.empty_like(x3)
-    _bn_act_forward_launch(x3, residual, scale, shift, N, c, P, relu, y)
-    return y
+    return _bn_act_forward(x3, gamma, beta, mean, var, eps, residual, relu)[0]
 
 
 _RELU_CONSTS = {}
@@ -1924,7 +1983,8 @@ def bottleneck_c8_forward(x8, levels, convs, bns):
     with _timed('conv_fwd_bf16', None,
                 (2.0 * N * P * wsz, 4.0 * (N * cin * P + wsz), 4.0 * N * cin * P,
                  f'bottleneck {cin}>{mid}>{cin} N{N} P{P} L1')):
-        L.check(lib.ld_bottleneck_c8_forward(C.byref(b), L.ptr(x8.buf), L.ptr(y),
+        L.check(lib.ld_bottleneck_c8_forward(C.byref(b), L.ptr(_c8_operand(x8)),
+                                             L.ptr(y),
                                              L.stream_ptr(x8.device)),
                 'ld_bottleneck_c8_forward')
     return C8Act(y, (N, cin, P)), levels
@@ -1933,55 +1993,36 @@ def bottleneck_c8_forward(x8, levels, convs, bns):
 # ---------------------------------------------------------------------------
 # GroupNorm + ReLU on level-concatenated tensors
 # ---------------------------------------------------------------------------
-def _c8_side_output(t):
-    """bf16 mode: a producer kernel may write the C8 image of its fp32 output in
-    the same launch (the next conv then finds it cached on the tensor).  Returns
-    the buffer to fill, or None when the geometry does not allow it."""
-    N, c, P = t.shape
-    if not (_C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and P % 4 == 0
-            and t.data_ptr() % 16 == 0):
-        return None
-    return torch.empty(N * c * P, dtype=torch.bfloat16, device=t.device)
-
-
-def _attach_c8(t, buf):
-    try:
-        t._ld_c8 = ((t._version, t.data_ptr()), buf)
-    except AttributeError:
-        pass
-
-
-def _gn_forward_launch(lv, x3, gamma, beta, N, c, groups, eps, relu, y, stats):
-    """y = None: write ONLY the C8 image of the output (bf16 mode; returns the
-    image, or None when the geometry has no C8 form -- nothing was launched)."""
+def _gn_forward(x3, gamma, beta, groups, eps, levels, relu, image_only=False):
+    """GroupNorm (+ ReLU) of a level-concatenated tensor: (y, C8 image of y,
+    stats).  bf16 mode: the image comes out of the same launch where the
+    geometry has a C8 form (None otherwise); ``image_only``: y is then not
+    written at all and comes back as None."""
     lib = L.get_lib()
+    N, c, P = x3.shape
+    lv = levels_desc(levels)
+    stats = torch.empty((2, N, groups, len(levels)), dtype=torch.float32,
+                        device=x3.device)
     need = lib.ld_gn_forward_workspace_bytes(C.byref(lv), N, groups)
     ws = workspace(x3.device, need, 'gn_fwd')
-    if y is None:
-        if not (_C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
-                x3.shape[2] % 4 == 0 and x3.data_ptr() % 16 == 0):
-            return None
-        y_c8 = torch.empty(x3.numel(), dtype=torch.bfloat16, device=x3.device)
+    y = None if image_only and _c8_writable(c, P, ptrs=(x3.data_ptr(), )) \
+        else torch.empty_like(x3)
+    if _c8_writable(c, P, ptrs=[t.data_ptr() for t in (x3, y) if t is not None]):
+        img = torch.empty(x3.numel(), dtype=torch.bfloat16, device=x3.device)
         L.check(lib.ld_gn_forward_c8(
             C.byref(lv), L.ptr(x3), L.ptr(gamma), L.ptr(beta), N, c, groups,
-            eps, 1 if relu else 0, None, L.ptr(y_c8), L.ptr(stats[0]),
+            eps, 1 if relu else 0, L.ptr(y), L.ptr(img), L.ptr(stats[0]),
             L.ptr(stats[1]), L.ptr(ws), ws.numel(),
             L.stream_ptr(x3.device)), 'ld_gn_forward_c8')
-        return y_c8
-    y_c8 = _c8_side_output(y) if x3.data_ptr() % 16 == 0 else None
-    if y_c8 is not None:
-        L.check(lib.ld_gn_forward_c8(
-            C.byref(lv), L.ptr(x3), L.ptr(gamma), L.ptr(beta), N, c, groups,
-            eps, 1 if relu else 0, L.ptr(y), L.ptr(y_c8), L.ptr(stats[0]),
-            L.ptr(stats[1]), L.ptr(ws), ws.numel(),
-            L.stream_ptr(x3.device)), 'ld_gn_forward_c8')
-        _attach_c8(y, y_c8)
-        return
+        if y is not None:
+            _attach_c8(y, img)
+        return y, img, stats
     L.check(lib.ld_gn_forward(C.byref(lv), L.ptr(x3), L.ptr(gamma),
                               L.ptr(beta), N, c, groups, eps,
                               1 if relu else 0, L.ptr(y), L.ptr(stats[0]),
                               L.ptr(stats[1]), L.ptr(ws), ws.numel(),
                               L.stream_ptr(x3.device)), 'ld_gn_forward')
+    return y, None, stats
 
 
 _GN_LEAN = [os.environ.get('LD_GN_LEAN', '1') == '1']
@@ -2009,9 +2050,7 @@ def _gn_backward(dy, x3, y, gamma, beta, stats, groups, levels, relu, params,
         fresh_all=True)
     need = lib.ld_gn_backward_workspace_bytes(C.byref(lv), N, c)
     ws = workspace(x3.device, need, 'gn')
-    aligned = all(t.data_ptr() % 16 == 0 for t in (dy, y, x3))
-    c8_ok = aligned and _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and \
-        P % 4 == 0
+    c8_ok = _c8_writable(c, P, ptrs=[t.data_ptr() for t in (dy, y, x3)])
     lean = c8_ok and _GN_LEAN[0] and os.environ.get('LD_NN_OLD') != '1'
     if need_lean and not lean:
         raise L.LdError('GroupNorm backward: the forward kept y only as its C8 '
@@ -2020,7 +2059,7 @@ def _gn_backward(dy, x3, y, gamma, beta, stats, groups, levels, relu, params,
     dx8_only = bool(lean and dx_c8_only)
     dx = None if dx8_only else torch.empty_like(x3)
     dx_c8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=x3.device) \
-        if dx8_only else _c8_side_output(dx) if c8_ok else None
+        if dx8_only or (c8_ok and dx.data_ptr() % 16 == 0) else None
     if lean:
         L.check(lib.ld_gn_backward_c8_lean(
             C.byref(lv), L.ptr(dy), L.ptr(x3), L.ptr(gamma), L.ptr(beta),
@@ -2055,14 +2094,8 @@ class GnActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, gamma, beta, groups, eps, levels, relu):
-        _dev_f32(x3, 'gn input')
-        N, c, P = x3.shape
-        lv = levels_desc(levels)
-        y = torch.empty_like(x3)
-        stats = torch.empty((2, N, groups, len(levels)), dtype=torch.float32,
-                            device=x3.device)
-        _gn_forward_launch(lv, x3, gamma, beta, N, c, groups, eps, relu, y,
-                           stats)
+        # (gn_act validated x3)
+        y, _, stats = _gn_forward(x3, gamma, beta, groups, eps, levels, relu)
         ctx.save_for_backward(x3, y, gamma, beta, stats)
         ctx.meta = (groups, levels, relu)
         ctx.params = (gamma, beta)
@@ -2092,34 +2125,22 @@ class ConvGnActFn(torch.autograd.Function):
     def forward(ctx, x3, w, gamma, beta, groups, eps, stride, pad, levels, relu,
                 c8_out=False):
         raw, out_levels = conv_forward_raw(x3, w, stride, pad, levels)
-        N, c, P = raw.shape
-        lv = levels_desc(out_levels)
-        stats = torch.empty((2, N, groups, len(out_levels)),
-                            dtype=torch.float32, device=raw.device)
         # ``c8_out`` (the caller's next layer is another conv of the stack): the
         # lean backward does not read y and the next conv takes the C8 image --
-        # the fp32 output is then a placeholder that is never written
-        # (``_ld_unwritten``, see trunk_c8_scope)
-        img = None
-        if c8_out and _TRUNK_C8_ON[0] and _GN_YSKIP[0] and _GN_LEAN[0] and \
-                os.environ.get('LD_NN_OLD') != '1':
-            img = _gn_forward_launch(lv, raw, gamma, beta, N, c, groups, eps,
-                                     relu, None, stats)
-        y = torch.empty_like(raw)
-        if img is not None:
-            _attach_c8(y, img)
-            y._ld_unwritten = True
-        else:
-            _gn_forward_launch(lv, raw, gamma, beta, N, c, groups, eps, relu, y,
-                               stats)
-        ctx.y_unwritten = img is not None
-        ctx.x8 = x3 if isinstance(x3, C8Act) else None
-        ctx.save_for_backward(x3.buf if ctx.x8 is not None else x3, w, raw, y,
-                              gamma, beta, stats)
+        # the fp32 output is then an image-only placeholder (see trunk_c8_scope)
+        y, img, stats = _gn_forward(
+            raw, gamma, beta, groups, eps, out_levels, relu,
+            image_only=c8_out and _TRUNK_C8_ON[0] and _GN_YSKIP[0] and
+            _GN_LEAN[0] and os.environ.get('LD_NN_OLD') != '1')
+        ctx.y_unwritten = y is None
+        if y is None:
+            y = _image_only_output(raw.shape, img)
+        ctx.save_for_backward(_save_conv_input(ctx, x3), w, raw, y, gamma, beta,
+                              stats)
         ctx.meta = (stride, pad, levels, False)
         ctx.gn = (groups, out_levels, relu)
         ctx.params = (w, gamma, beta)
-        ctx.fan = fan_in(ctx, 0, x3) if ctx.x8 is None else None
+        ctx.fan = fan_in(ctx, 0, x3)
         _note_use(w, gamma, beta)
         return y
 
@@ -2136,8 +2157,8 @@ class ConvGnActFn(torch.autograd.Function):
             ng[2], ng[3], dx_c8_only=c8_dead, need_lean=ctx.y_unwritten)
         dx = dw = None
         if ng[0] or ng[1]:
-            dx, dw, _ = _conv_backward(x3, ctx.x8, w, draw, ctx.meta,
-                                       (pw, None), ng[0], ng[1], False,
+            dx, dw, _ = _conv_backward(_saved_conv_input(ctx, x3), None, w, draw,
+                                       ctx.meta, (pw, None), ng[0], ng[1], False,
                                        addend=fan_take(ctx.fan) if ng[0]
                                        else None)
         return (fan_give(ctx.fan, dx), dw, dgamma, dbeta, None, None, None,
@@ -2168,34 +2189,18 @@ def conv_gn_act(x3, w, gamma, beta, groups, eps, stride, pad, levels, relu=True,
         # norm -- no C8 image of it -- and, ``c8_only``, the layer's output
         # exists only as its C8 image (the next conv's operand)
         raw, _ = conv_forward_raw(x3, w, stride, pad, levels)
-        N, c, _ = raw.shape
-        lv = levels_desc(out_levels)
-        stats = torch.empty((2, N, groups, len(out_levels)),
-                            dtype=torch.float32, device=raw.device)
-        if c8_only:
-            img = _gn_forward_launch(lv, raw, gamma, beta, N, c, groups, eps,
-                                     relu, None, stats)
-            if img is not None:
-                return C8Act(img, raw.shape), out_levels
-        y = torch.empty_like(raw)
-        _gn_forward_launch(lv, raw, gamma, beta, N, c, groups, eps, relu, y,
-                           stats)
-        return y, out_levels
+        y, img, _ = _gn_forward(raw, gamma, beta, groups, eps, out_levels, relu,
+                                image_only=c8_only)
+        return (C8Act(img, raw.shape) if y is None else y), out_levels
     y3, out_levels = conv2d(x3, w, None, stride, pad, levels)
     return gn_act(y3, gamma, beta, groups, eps, out_levels, relu), out_levels
 
 
 def gn_act(x3, gamma, beta, groups, eps, levels, relu=True):
+    _dev_f32(x3, 'gn input')
     if torch.is_grad_enabled() and (x3.requires_grad or gamma.requires_grad):
         return GnActFn.apply(x3, gamma, beta, groups, eps, levels, relu)
-    lib = L.get_lib()
-    N, c, P = x3.shape
-    lv = levels_desc(levels)
-    y = torch.empty_like(x3)
-    stats = torch.empty((2, N, groups, len(levels)), dtype=torch.float32,
-                        device=x3.device)
-    _gn_forward_launch(lv, x3, gamma, beta, N, c, groups, eps, relu, y, stats)
-    return y
+    return _gn_forward(x3, gamma, beta, groups, eps, levels, relu)[0]
 
 
 # ---------------------------------------------------------------------------
@@ -2206,6 +2211,7 @@ def copy_into(dst, src):
     kernel launch of this library (ld_copy_d2d): inside a step that is captured, a
     torch copy is a hipMemcpyAsync, i.e. a 1-D memcpy graph node that a step list
     cannot re-issue (include/ld_hip.h "step lists")."""
+    _fp32_readable(src, 'copy_into source')
     if not (dst.is_cuda and src.is_cuda and dst.is_contiguous() and src.is_contiguous()
             and dst.dtype == src.dtype and dst.numel() == src.numel()):
         dst.copy_(src)
@@ -2218,11 +2224,11 @@ def copy_into(dst, src):
 
 def maxpool3x3s2(x4):
     """MaxPool2d(3, 2, 1), forward only (frozen stem)."""
-    lib = L.get_lib()
     _dev_f32(x4, 'maxpool input')
     if x4.requires_grad and torch.is_grad_enabled():
         raise L.LdError('maxpool3x3s2 has no backward (the stem is frozen: '
                         'frozen_stages >= 0 is required)')
+    lib = L.get_lib()
     N, c, h, w = x4.shape
     ho, wo = out_size(h, 3, 2, 1), out_size(w, 3, 2, 1)
     y = torch.empty((N, c, ho, wo), dtype=torch.float32, device=x4.device)
@@ -2265,9 +2271,6 @@ def _res2_gather(src, slice_, w, addend):
     if addend is not None and (tuple(addend.shape) != (N, w, P) or
                                not addend.is_contiguous()):
         raise L.LdError('res2 gather: addend shape mismatch')
-    if not src.is_contiguous() or _unwritten(src):
-        raise L.LdError('res2 gather: the input must be a written, contiguous '
-                        'fp32 tensor')
     y = torch.empty((N, w, P), dtype=torch.float32, device=src.device)
     L.check(L.get_lib().ld_res2_gather(L.ptr(src), L.ptr(addend), N, c, w,
                                        slice_, P, L.ptr(y),
@@ -2277,6 +2280,7 @@ def _res2_gather(src, slice_, w, addend):
 
 
 def _res2_concat(parts, t, w, hw, stride, mode):
+    _dev_f32(t, 'res2 concat tail')
     a, b, c = parts
     N = a.shape[0]
     h, w_ = hw
@@ -2288,9 +2292,7 @@ def _res2_concat(parts, t, w, hw, stride, mode):
     for p in parts:
         if tuple(p.shape) != (N, w, py) or not p.is_contiguous():
             raise L.LdError('res2 concat: part shape mismatch')
-    _dev_f32(t, 'res2 concat tail')
-    if t.shape[0] != N or t.shape[2] != pt or t.shape[1] < 4 * w or \
-            not t.is_contiguous() or _unwritten(t):
+    if t.shape[0] != N or t.shape[2] != pt or t.shape[1] < 4 * w:
         raise L.LdError('res2 concat: tail source shape mismatch')
     y = torch.empty((N, 4 * w, py), dtype=torch.float32, device=a.device)
     L.check(L.get_lib().ld_res2_concat(
@@ -2363,8 +2365,7 @@ def _avgpool_ceil(x3, hw, k, backward):
     N, c, P = x3.shape
     h, w = hw
     ho, wo = -(-h // k), -(-w // k)
-    if P != (ho * wo if backward else h * w) or not x3.is_contiguous() or \
-            _unwritten(x3):
+    if P != (ho * wo if backward else h * w):
         raise L.LdError('avgpool_ceil: shape mismatch')
     y = torch.empty((N, c, h * w if backward else ho * wo),
                     dtype=torch.float32, device=x3.device)
@@ -2405,9 +2406,9 @@ class UpsampleAddFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, fine, coarse):
+        _dev_f32(fine, 'upsample_add fine map')
+        _dev_f32(coarse, 'upsample_add coarse map')
         lib = L.get_lib()
-        _dev_f32(fine, 'fine')
-        _dev_f32(coarse, 'coarse')
         N, c, hf, wf = fine.shape
         hc, wc = coarse.shape[2:]
         out = torch.empty_like(fine)
@@ -2448,8 +2449,8 @@ class ScaleLevelsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, scales, levels):
+        _dev_f32(x3, 'scale_levels input')
         lib = L.get_lib()
-        _dev_f32(x3, 'scale input')
         N, c, P = x3.shape
         lv = levels_desc(levels)
         y = torch.empty_like(x3)
@@ -2491,9 +2492,9 @@ def deform_im2col(x3, off3, h, w, k, stride, pad, dilation):
     """(N, Cin, H*W) + offsets (N, 2*k*k, Hout*Wout) -> column tensor
     (N, Cin*k*k, Hout*Wout), no autograd (ld_deform_im2col; the differentiable
     form is deform_im2col_fn)."""
-    lib = L.get_lib()
     _dev_f32(x3, 'dcn input')
     _dev_f32(off3, 'dcn offset')
+    lib = L.get_lib()
     N, cin, P = x3.shape
     ho, wo = out_size(h, k, stride, pad), out_size(w, k, stride, pad)
     if P != h * w or off3.shape != (N, 2 * k * k, ho * wo):
@@ -2558,10 +2559,6 @@ class DeformIm2colFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, off3, h, w, k, stride, pad):
-        if isinstance(x3, C8Act) or _unwritten(x3):
-            raise NotImplementedError(
-                'deformable sampling needs the fp32 input; this one exists '
-                'only as a C8 image (C8Act / trunk_c8_scope)')
         col = deform_im2col(x3, off3, h, w, k, stride, pad, 1)
         ctx.save_for_backward(x3, off3)
         ctx.geo = (h, w, k, stride, pad)
@@ -2647,8 +2644,8 @@ def gconv_forward(x3, w, groups, stride, pad, levels, scale=None, shift=None,
                   relu=False):
     """Grouped conv forward (ld_gconv_forward), single level, forward only:
     (N, Cin, H*W) -> ((N, Cout, Ho*Wo), ((Ho, Wo),))."""
-    lib = L.get_lib()
     _dev_f32(x3, 'grouped conv input')
+    lib = L.get_lib()
     if len(levels) != 1:
         raise NotImplementedError('grouped conv on level-concatenated tensors')
     (h, wd), = levels
@@ -2732,10 +2729,7 @@ class GroupedConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x3, w, groups, stride, pad, levels):
-        if isinstance(x3, C8Act) or _unwritten(x3):
-            raise NotImplementedError(
-                'a trainable grouped conv needs its input in fp32; this one '
-                'exists only as a C8 image (C8Act / trunk_c8_scope)')
+        _fp32_readable(x3, 'trainable grouped conv input')
         if _PRECISION[0] == 'bf16':
             raise NotImplementedError(
                 'trainable grouped convs are fp32 only (bf16 mode is not built)')
@@ -2906,13 +2900,13 @@ def _level_ptrs(ts):
 
 
 def _pack_launch(feats, levels):
+    fs = [_dev_f32(f, 'level map') for f in feats]
     f0 = feats[0]
     N, c = int(f0.shape[0]), int(f0.shape[1])
     P = sum(h * w for h, w in levels)
     x3 = torch.empty((N, c, P), dtype=torch.float32, device=f0.device)
-    fs = [_dev_f32(f, 'level map') for f in feats]
     lv = levels_desc(levels)
-    if _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0:
+    if _c8_writable(c, P, vec=1):
         # bf16 mode: the C8 image of the packed tensor from the same launch (the
         # first tower convs read it)
         x8 = torch.empty(N * c * P, dtype=torch.bfloat16, device=f0.device)
@@ -2945,7 +2939,7 @@ class PackLevelsFn(torch.autograd.Function):
         outs = [torch.empty((N, c, h, w), dtype=torch.float32,
                             device=dx3.device) for h, w in ctx.levels]
         lv = levels_desc(ctx.levels)
-        if _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0:
+        if _c8_writable(c, dx3.shape[2], vec=1):
             # the level gradients feed the neck convs' C8 data / weight gradients
             o8 = [torch.empty(N * c * h * w, dtype=torch.bfloat16,
                               device=dx3.device) for h, w in ctx.levels]
@@ -2966,6 +2960,8 @@ class PackLevelsFn(torch.autograd.Function):
 def pack_levels(feats):
     """tuple of (N, C, H_l, W_l) -> (N, C, P) level-concatenated tensor."""
     levels = tuple((int(f.shape[2]), int(f.shape[3])) for f in feats)
+    for f in feats:  # also ahead of the two torch fall-backs below
+        _fp32_readable(f, 'pack_levels input')
     if len(feats) == 1:
         return feats[0].reshape(feats[0].shape[0], feats[0].shape[1], -1), levels
     if any(not f.is_contiguous() for f in feats):

@@ -702,7 +702,14 @@ def test_trunk_c8_scope_outputs_only_images(bf16_mode):
         torch.cuda.synchronize()
         outs.append((ia, ib, [v.grad.clone() for v in t]))
         if scoped:
-            b._ld_c8 = None  # the image is gone: nothing may fall back to fp32
+            one = torch.ones(1, device=dev)
+            for read in (lambda: Y.relu(b),
+                         lambda: Y.bn_act(b, t[5], t[6], mean, var, 1e-5),
+                         lambda: Y.scale_levels(b, one, lv),
+                         lambda: Y.pack_levels([b.view(N, C, H, W)])):
+                with pytest.raises(L.LdError, match='only as a C8 image'):
+                    read()
+            Y._attach_c8(b, None)  # the image is gone: nothing may fall back to fp32
             with pytest.raises(L.LdError, match='only as a C8 image'):
                 Y.to_c8(b)
     (ia0, ib0, g0), (ia1, ib1, g1) = outs
@@ -715,6 +722,35 @@ def test_trunk_c8_scope_outputs_only_images(bf16_mode):
     # measured 2.2 %; the whole-step effect is test_bf16_train_step_vs_fp32_golden's)
     for u, v in zip(g0, g1):
         assert float((u - v).norm()) <= 5e-2 * float(u.norm())
+
+
+def test_conv_gn_c8_out_placeholder_is_refused_by_fp32_readers(bf16_mode):
+    """ConvGnActFn with ``c8_only`` returns an image-only placeholder too (P = 308,
+    a multiple of 4: the geometry ld_gn_forward_c8 can write alone): gn_act refuses
+    it, the next tower layer takes the image, and the backward runs through both."""
+    from ld_amd import layers as Y
+    from ld_amd import lib as L
+    dev = _dev()
+    g = torch.Generator().manual_seed(23)
+    levels = ((12, 20), (6, 10), (2, 4))
+    P, C = sum(h * w for h, w in levels), 64
+    t = [v.to(dev).requires_grad_(True) for v in (
+        [torch.randn(2, C, P, generator=g)] + [
+            u for _ in range(2) for u in (
+                torch.randn(C, C, 3, 3, generator=g) * 0.05,
+                torch.rand(C, generator=g) + .5,
+                torch.randn(C, generator=g) * .3)])]
+    y, lv = Y.conv_gn_act(t[0], t[1], t[2], t[3], 32, 1e-5, 1, 1, levels,
+                          c8_only=True)
+    assert Y._unwritten(y)
+    with pytest.raises(L.LdError, match='only as a C8 image'):
+        Y.gn_act(y, t[5], t[6], 32, 1e-5, lv)
+    z, _ = Y.conv_gn_act(y, t[4], t[5], t[6], 32, 1e-5, 1, 1, lv)
+    z.backward(torch.randn(2, C, P, generator=g).to(dev))
+    torch.cuda.synchronize()
+    assert all(v.grad is not None and bool(torch.isfinite(v.grad).all())
+               for v in t)
+    assert float(t[1].grad.abs().max()) > 0 and float(t[0].grad.abs().max()) > 0
 
 
 def test_padded_data_gradient_for_68_output_channels(bf16_mode):

@@ -473,8 +473,7 @@ def test_trainable_dcn_refusals():
                  (1, 64, 42))
     with pytest.raises(NotImplementedError, match='C8'):
         m.forward3(c8, lv)
-    ghost = torch.empty(1, 64, 42, device=dev)
-    ghost._ld_unwritten = True  # what trunk_c8_scope leaves behind
+    ghost = Y._image_only_output((1, 64, 42), c8.buf)  # what trunk_c8_scope leaves
     with pytest.raises(NotImplementedError, match='C8'):
         m.forward3(ghost, lv)
     with pytest.raises(NotImplementedError, match='deform_groups'):

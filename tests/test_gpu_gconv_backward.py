@@ -564,8 +564,7 @@ def test_refusals_still_raise():
                  (1, 128, 42))
     with pytest.raises(NotImplementedError, match='C8'):
         m.forward3(c8, lv)
-    ghost = torch.empty(1, 128, 42, device=dev)
-    ghost._ld_unwritten = True
+    ghost = Y._image_only_output((1, 128, 42), c8.buf)
     with pytest.raises(NotImplementedError, match='C8'):
         m.forward3(ghost, lv)
     x3 = torch.randn(1, 128, 42, device=dev).requires_grad_(True)

@@ -144,3 +144,203 @@ def test_student_frozen_stages_run_c8_only_decision():
         assert unfrozen._frozen_c8_stages() == 0
     finally:
         Y.set_precision('fp32')
+
+
+# ---------------------------------------------------------------------------
+# activation forms (ld_amd.layers, "activation forms" section):
+# the image-only check precedes the device check, so CPU tensors suffice and no
+# library call is reached
+# ---------------------------------------------------------------------------
+_LV = ((3, 4), )
+
+
+def _placeholder():
+    like = torch.zeros(2, 32, 12)
+    return Y._image_only_output(like.shape,
+                                torch.zeros(like.numel(), dtype=torch.bfloat16))
+
+
+def _no_grad(fn):
+    def run(*a):
+        with torch.no_grad():
+            return fn(*a)
+    return run
+
+
+def _bn(p, grad):
+    one = torch.ones(32, requires_grad=grad)
+    return Y.bn_act(p, one, one, one, one, 1e-5)
+
+
+def _gn(p, grad):
+    one = torch.ones(32, requires_grad=grad)
+    return Y.gn_act(p, one, one, 4, 1e-5, _LV)
+
+
+def _conv_fp32(p):
+    assert Y.get_precision() == 'fp32'
+    return Y.conv2d(p, torch.zeros(32, 32, 3, 3), None, 1, 1, _LV)
+
+
+def _conv_backward_fp32(p):
+    w = torch.zeros(32, 32, 3, 3)
+    return Y._conv_backward(p, None, w, torch.zeros(2, 32, 12), (1, 1, _LV, False),
+                            (w, None), False, True, False)
+
+
+def _dcn_module(p):
+    from ld_amd.cnn import DeformConv2dPack
+    return DeformConv2dPack(32, 32, 3, padding=1).forward3_bn(p, _LV)
+
+
+def _lost_image(p):
+    Y._attach_c8(p, None)
+    return Y.to_c8(p)
+
+
+def _part():
+    return torch.zeros(2, 8, 12)
+
+
+READERS = [  # (the consumer's name in the message, a call that reads fp32 values)
+    ('bn input', lambda p: _bn(p, True)),
+    ('bn input', _no_grad(lambda p: _bn(p, False))),
+    ('bn input', Y.relu),
+    ('gn input', lambda p: _gn(p, True)),
+    ('gn input', _no_grad(lambda p: _gn(p, False))),
+    ('upsample_add fine map', lambda p: Y.upsample_add(p.view(2, 32, 3, 4),
+                                                   torch.zeros(2, 32, 2, 2))),
+    ('scale_levels input', lambda p: Y.scale_levels(p, torch.ones(1), _LV)),
+    ('maxpool input', lambda p: Y.maxpool3x3s2(p.view(2, 32, 3, 4))),
+    ('copy_into source', lambda p: Y.copy_into(torch.zeros(2, 32, 12), p)),
+    ('level map', lambda p: Y._pack_launch([p.view(2, 32, 3, 4)], _LV)),
+    # pack_levels: the single-level reshape, the non-contiguous torch.cat and the
+    # PackLevelsFn / _pack_launch branch
+    ('pack_levels input', lambda p: Y.pack_levels([p.view(2, 32, 3, 4)])),
+    ('pack_levels input', lambda p: Y.pack_levels(
+        [torch.zeros(2, 32, 3, 4), p.view(2, 32, 3, 4)[..., :2]])),
+    ('pack_levels input', lambda p: Y.pack_levels(
+        [torch.zeros(2, 32, 3, 4, requires_grad=True), p.view(2, 32, 3, 4)])),
+    ('avgpool input', lambda p: Y.avgpool_ceil(p, (3, 4), 2)),
+    ('res2 gather input', lambda p: Y._res2_gather(p, 0, 8, None)),
+    ('res2 concat tail', lambda p: Y._res2_concat(
+        (_part(), _part(), _part()), p, 8, (3, 4), 1, Y.RES2_TAIL_COPY)),
+    ('dcn input', lambda p: Y.deform_im2col_fn(
+        p, torch.zeros(2, 18, 12, requires_grad=True), 3, 4, 3, 1, 1)),
+    ('dcn input', _no_grad(lambda p: Y.deform_im2col_fn(
+        p, torch.zeros(2, 18, 12), 3, 4, 3, 1, 1))),
+    ('trainable grouped conv input', lambda p: Y.gconv2d(
+        p, torch.zeros(32, 1, 3, 3, requires_grad=True), 32, 1, 1, _LV)),
+    ('grouped conv input', _no_grad(lambda p: Y.gconv2d(
+        p, torch.zeros(32, 1, 3, 3), 32, 1, 1, _LV))),
+    ('trainable DCN input', _dcn_module),
+    ('conv input', _conv_fp32),
+    ('conv backward: saved input', _conv_backward_fp32),
+    ('to_c8', _lost_image),
+]
+
+
+@pytest.mark.parametrize('name,read', READERS,
+                         ids=[f'{i}-{n[0]}' for i, n in enumerate(READERS)])
+def test_every_fp32_reader_refuses_an_image_only_activation(name, read):
+    with pytest.raises(LdError, match='only as a C8 image') as e:
+        read(_placeholder())
+    assert str(e.value).startswith(name + ':')
+    # a C8Act is refused by the same guard, under the same name
+    with pytest.raises(LdError, match='only as a C8 image'):
+        Y._dev_f32(Y.C8Act(torch.zeros(768, dtype=torch.bfloat16), (2, 32, 12)),
+                   name)
+
+
+def test_views_of_a_placeholder_stay_flagged():
+    p = _placeholder()
+    v = p.view(2, 32, 3, 4)
+    assert Y._unwritten(p) and Y._unwritten(v)
+    assert Y._unwritten(v.reshape(2, 32, 12))
+    levels = ((2, 4), (2, 2))
+    assert all(Y._unwritten(t) for t in Y.split_levels(p, levels))
+    plain = torch.zeros(2, 32, 12)
+    cached = torch.zeros(2, 32, 12)
+    Y._attach_c8(cached, torch.zeros(768, dtype=torch.bfloat16))
+    for t in (plain, cached, plain.view(2, 32, 3, 4)):
+        assert not Y._unwritten(t)
+        assert Y._fp32_readable(t, 'reader') is t
+        # past the image-only check: what refuses a CPU tensor is the device check
+        with pytest.raises(LdError, match='only run on a HIP device'):
+            Y._dev_f32(t, 'reader')
+    assert Y._dev_f32(p, 'conv input', image_ok=True) is p
+
+
+def test_cached_image_follows_the_tensor_and_its_version():
+    x = torch.zeros(2, 32, 12)
+    img = torch.zeros(768, dtype=torch.bfloat16)
+    assert Y._c8_cached(x) is None
+    Y._attach_c8(x, img)
+    assert Y._c8_cached(x) is img
+    assert Y._c8_operand(x) is img  # no conversion launch
+    # a same-memory contiguous reshape view finds the image through its base
+    assert Y._c8_cached(x.view(2, 32, 3, 4)) is img
+    assert Y._c8_cached(x.view(2, 32, 3, 4).reshape(2, 32, 12)) is img
+    assert Y._c8_cached(x[:, :, :6]) is None and Y._c8_cached(x[1:]) is None
+    x.add_(1.0)  # an in-place write bumps the version: the image is stale
+    assert Y._c8_cached(x) is None
+    a = Y.C8Act(img, (2, 32, 12))
+    assert Y._c8_operand(a) is img
+    p = _placeholder()
+    assert Y._c8_operand(p) is Y._c8_cached(p)
+    Y._attach_c8(p, None)
+    assert Y._c8_cached(p) is None and Y._unwritten(p)
+
+
+@pytest.mark.parametrize('c8_on', [True, False])
+@pytest.mark.parametrize('mode', ['bf16', 'fp32'])
+def test_c8_writable_matches_the_five_spellings_it_replaced(mode, c8_on):
+    prev = Y._PRECISION[0]
+    try:
+        Y._PRECISION[0] = mode
+        Y.set_c8(c8_on)
+        _C8, _PRECISION = Y._C8, Y._PRECISION
+        for c in (16, 32, 48, 64):
+            for P in (6, 8):
+                for ptrs in ((4096, 8192, 512), (4096, 8196, 512), (4100, ) * 3):
+                    p0 = ptrs[0]
+                    side_output = bool(
+                        _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
+                        P % 4 == 0 and p0 % 16 == 0)
+                    gn_forward = bool(
+                        _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
+                        P % 4 == 0 and p0 % 16 == 0)
+                    aligned = all(p % 16 == 0 for p in ptrs)
+                    gn_backward = bool(
+                        aligned and _C8[0] and _PRECISION[0] == 'bf16' and
+                        c % 32 == 0 and P % 4 == 0)
+                    bn_backward = bool(
+                        all(p % 16 == 0 for p in ptrs) and
+                        _C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0 and
+                        P % 4 == 0)
+                    pack = bool(_C8[0] and _PRECISION[0] == 'bf16' and c % 32 == 0)
+                    assert bool(Y._c8_writable(c, P, ptrs=(p0, ))) == side_output
+                    assert bool(Y._c8_writable(c, P, ptrs=(p0, ))) == gn_forward
+                    assert bool(Y._c8_writable(c, P, ptrs=ptrs)) == gn_backward
+                    assert bool(Y._c8_writable(c, P, ptrs=list(ptrs))) == bn_backward
+                    assert bool(Y._c8_writable(c, P, vec=1)) == pack
+    finally:
+        Y._PRECISION[0] = prev
+        Y.set_c8(True)
+
+
+def test_only_the_forms_section_touches_the_tensor_attributes():
+    """Structural pin: the image / placeholder attributes are read and written
+    between the two "activation forms" markers of layers.py and nowhere else."""
+    import os
+    root = os.path.dirname(os.path.abspath(Y.__file__))
+    src = open(os.path.join(root, 'layers.py')).read()
+    begin, end = '# activation forms: begin', '# activation forms: end'
+    assert src.count(begin) == 1 and src.count(end) == 1
+    inside = src[src.index(begin):src.index(end)]
+    outside = src[:src.index(begin)] + src[src.index(end):]
+    for attr in ('_ld_c8', '_ld_unwritten'):
+        assert attr in inside
+        assert attr not in outside
+        for other in ('cnn.py', 'resnet.py'):
+            assert attr not in open(os.path.join(root, other)).read(), other
