@@ -34,30 +34,12 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_device.h"
 #include "conv_tune.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float floatx8 __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
-
-// Epilogue side output (a.y_c8): the bf16 channel-blocked (C8) image of y, for
-// the conv that consumes y next.  A lane holds rows rbase + 8g + {0..3} (g =
-// 0..3) of one position: four consecutive channels = one half of a 16-byte C8
-// row -> one 8-byte store; the two lane halves of a wave fill the row,
-// consecutive lanes consecutive positions (fully coalesced).
-
 inline int k8_blocks(int k) { return (k + 15) / 16 * 2; }  // 8-blocks per tap
-
-__device__ __forceinline__ uintx4 buf_load16(rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(uintx4,
-                            __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
 
 // ------------------------------------------------- forward/dgrad, streaming
 template <int TM, int TN, int WVM, int MODE, int D, int OCC, int KS>
@@ -256,110 +238,7 @@ __global__ __launch_bounds__(256, OCC) void conv_stream_bf16_kernel(ConvK a) {
     if (wave != 0) return;
     add(red);
   }
-
-  // ---- epilogue: direct stores, 32 consecutive positions per accumulator row
-  const bool has_res = a.residual != nullptr;
-  const bool res8 = a.res_c8 != nullptr;  // residual as a C8 image
-  const bool has_y = a.y != nullptr;      // fp32 output optional (C8-only nets)
-  const bool c8out = a.y_c8 != nullptr;
-  const bool relu = a.relu != 0;
-  const bool has_aff = a.scale != nullptr, has_bias = a.bias != nullptr;
-  // Loop order (round 3): row group g = 4 accumulator rows (one C8 half-row) x
-  // all TN column tiles; every load of a group -- affine, bias, fp32 / C8
-  // residual -- is issued before the group's first store.  The pointers of ConvK
-  // may alias as far as hipcc knows, so a residual load written between stores
-  // stays behind the previous store: the loop this replaces made up to 16
-  // dependent round trips per 32 x 32 tile, each waited for with vmcnt(0) (ISA
-  // reading; the 256 -> 1024 expansion convs ran at 1.2 TB/s).
-  size_t colbase[TN], c8base[TN];
-  bool jok[TN];
-  const int prow = MODE == 1 ? a.Pfull : a.Pout;
-  // per-channel operands through descriptors: an absent one has extent 0 and
-  // loads as 0 -- no flag-dependent branch inside a group's load phase
-  const rsrc_t r_sc = make_rsrc(a.scale, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_sh = make_rsrc(a.shift, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_bi = make_rsrc(a.bias, has_bias ? (unsigned)Cout * 4u : 0u);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int jc = n0 + j * 32 + l31;
-    jok[j] = jc < a.J;
-    const int n = jc / a.Pout;
-    int p = jc - n * a.Pout;
-    // C8 images (side output, residual) exist for MODE 0 only: compact p
-    c8base[j] = ((size_t)n * (Cout >> 3) * a.Pout + p) * 16;
-    if (MODE == 1 && jok[j]) {
-      int l, hc, wc;
-      locate_out(a.g, p, l, hc, wc);
-      p = a.foff[l] + (2 * hc + a.ph) * a.fW[l] + 2 * wc + a.pw;
-    }
-    colbase[j] = (size_t)n * Cout * prow + p;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int rbase = m0 + i * 32 + 4 * lk;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row0 = rbase + 8 * g;  // this lane's four rows: row0 .. row0 + 3
-      // byte offset of the lane's 8-byte half of its C8 row within an image
-      const size_t c8row = (size_t)(row0 >> 3) * a.Pout * 16 + (row0 & 4) * 2;
-      float sc[4], sh[4], bi[4], rv[TN][4];
-      uintx2 rraw[TN];
-      // group fence: the loads of this group stay behind the previous group's
-      // stores and none of them is consumed before all are issued
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned ro = (unsigned)(row0 + e) * 4u;  // >= Cout / absent: zeros
-        sc[e] = buf_load(r_sc, ro, 0);
-        sh[e] = buf_load(r_sh, ro, 0);
-        bi[e] = buf_load(r_bi, ro, 0);
-      }
-      if (has_res) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            rv[j][e] = (jok[j] && row0 + e < Cout)
-                           ? a.residual[colbase[j] + (size_t)(row0 + e) * prow]
-                           : 0.0f;
-      }
-      if (MODE == 0 && res8) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          rraw[j] = (jok[j] && row0 < Cout)
-                        ? *(const uintx2*)((const char*)a.res_c8 + c8base[j] + c8row)
-                        : uintx2{0u, 0u};
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (!jok[j]) continue;
-        floatx4_t q;
-        floatx4_t rq = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (MODE == 0 && res8)
-          rq = __builtin_convertvector(__builtin_bit_cast(bf16x4, rraw[j]), floatx4_t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const int row = row0 + e;
-          float v = 0.0f;
-          if (row < Cout) {
-            v = acc[i][j][r] * (has_aff ? sc[e] : 1.0f) + (sh[e] + bi[e]);
-            if (MODE == 0 && a.y_raw)
-              a.y_raw[colbase[j] + (size_t)row * prow] = acc[i][j][r];
-            if (has_res) v += rv[j][e];
-            if (MODE == 0 && res8) v += rq[e];
-            if (relu) v = fmaxf(v, 0.0f);
-            if (has_y) a.y[colbase[j] + (size_t)row * prow] = v;
-          }
-          q[e] = v;
-        }
-        // side output: this lane's four channels = half of a 16-byte C8 row
-        if (MODE == 0 && c8out && row0 < Cout)
-          *(uintx2*)((char*)a.y_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(q, bf16x4));
-      }
-    }
-  }
+  LD_C8_EPILOGUE(m0, n0, false);
 }
 
 // ---------------------------------------------- forward/dgrad, LDS-tiled --
@@ -546,110 +425,7 @@ __global__ __launch_bounds__(256, 2) void conv_tile_bf16_kernel(ConvK a) {
       compute(u & 1);
     }
   }
-
-  // ---- epilogue: direct stores, 32 consecutive positions per accumulator row
-  const bool has_res = a.residual != nullptr;
-  const bool res8 = a.res_c8 != nullptr;  // residual as a C8 image
-  const bool has_y = a.y != nullptr;      // fp32 output optional (C8-only nets)
-  const bool c8out = a.y_c8 != nullptr;
-  const bool relu = a.relu != 0;
-  const bool has_aff = a.scale != nullptr, has_bias = a.bias != nullptr;
-  // Loop order (round 3): row group g = 4 accumulator rows (one C8 half-row) x
-  // all TN column tiles; every load of a group -- affine, bias, fp32 / C8
-  // residual -- is issued before the group's first store.  The pointers of ConvK
-  // may alias as far as hipcc knows, so a residual load written between stores
-  // stays behind the previous store: the loop this replaces made up to 16
-  // dependent round trips per 32 x 32 tile, each waited for with vmcnt(0) (ISA
-  // reading; the 256 -> 1024 expansion convs ran at 1.2 TB/s).
-  size_t colbase[TN], c8base[TN];
-  bool jok[TN];
-  const int prow = MODE == 1 ? a.Pfull : a.Pout;
-  // per-channel operands through descriptors: an absent one has extent 0 and
-  // loads as 0 -- no flag-dependent branch inside a group's load phase
-  const rsrc_t r_sc = make_rsrc(a.scale, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_sh = make_rsrc(a.shift, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_bi = make_rsrc(a.bias, has_bias ? (unsigned)Cout * 4u : 0u);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int jc = n0 + wn * (BN / 2) + j * 32 + l31;
-    jok[j] = jc < a.J;
-    const int n = jc / a.Pout;
-    int p = jc - n * a.Pout;
-    // C8 images (side output, residual) exist for MODE 0 only: compact p
-    c8base[j] = ((size_t)n * (Cout >> 3) * a.Pout + p) * 16;
-    if (MODE == 1 && jok[j]) {
-      int l, hc, wc;
-      locate_out(a.g, p, l, hc, wc);
-      p = a.foff[l] + (2 * hc + a.ph) * a.fW[l] + 2 * wc + a.pw;
-    }
-    colbase[j] = (size_t)n * Cout * prow + p;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int rbase = m0 + wm * (BM / 2) + i * 32 + 4 * lk;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row0 = rbase + 8 * g;  // this lane's four rows: row0 .. row0 + 3
-      // byte offset of the lane's 8-byte half of its C8 row within an image
-      const size_t c8row = (size_t)(row0 >> 3) * a.Pout * 16 + (row0 & 4) * 2;
-      float sc[4], sh[4], bi[4], rv[TN][4];
-      uintx2 rraw[TN];
-      // group fence: the loads of this group stay behind the previous group's
-      // stores and none of them is consumed before all are issued
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned ro = (unsigned)(row0 + e) * 4u;  // >= Cout / absent: zeros
-        sc[e] = buf_load(r_sc, ro, 0);
-        sh[e] = buf_load(r_sh, ro, 0);
-        bi[e] = buf_load(r_bi, ro, 0);
-      }
-      if (has_res) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            rv[j][e] = (jok[j] && row0 + e < Cout)
-                           ? a.residual[colbase[j] + (size_t)(row0 + e) * prow]
-                           : 0.0f;
-      }
-      if (MODE == 0 && res8) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          rraw[j] = (jok[j] && row0 < Cout)
-                        ? *(const uintx2*)((const char*)a.res_c8 + c8base[j] + c8row)
-                        : uintx2{0u, 0u};
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (!jok[j]) continue;
-        floatx4_t q;
-        floatx4_t rq = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (MODE == 0 && res8)
-          rq = __builtin_convertvector(__builtin_bit_cast(bf16x4, rraw[j]), floatx4_t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const int row = row0 + e;
-          float v = 0.0f;
-          if (row < Cout) {
-            v = acc[i][j][r] * (has_aff ? sc[e] : 1.0f) + (sh[e] + bi[e]);
-            if (MODE == 0 && a.y_raw)
-              a.y_raw[colbase[j] + (size_t)row * prow] = acc[i][j][r];
-            if (has_res) v += rv[j][e];
-            if (MODE == 0 && res8) v += rq[e];
-            if (relu) v = fmaxf(v, 0.0f);
-            if (has_y) a.y[colbase[j] + (size_t)row * prow] = v;
-          }
-          q[e] = v;
-        }
-        // side output: this lane's four channels = half of a 16-byte C8 row
-        if (MODE == 0 && c8out && row0 < Cout)
-          *(uintx2*)((char*)a.y_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(q, bf16x4));
-      }
-    }
-  }
+  LD_C8_EPILOGUE(m0 + wm * (BM / 2), n0 + wn * (BN / 2), false);
 }
 
 // ------------------------------- forward/dgrad, LDS-tiled, bf16 C8 input --
@@ -843,118 +619,7 @@ __global__ __launch_bounds__(256, 2) void conv_tile_c8_kernel(ConvK a) {
       }
     }
   }
-
-  // ---- epilogue: direct stores, 32 consecutive positions per accumulator row
-  const bool has_res = a.residual != nullptr;
-  const bool res8 = a.res_c8 != nullptr;  // residual as a C8 image
-  const bool has_y = a.y != nullptr;      // fp32 output optional (C8-only nets)
-  const bool c8out = a.y_c8 != nullptr;
-  const bool relu = a.relu != 0;
-  const bool has_aff = a.scale != nullptr, has_bias = a.bias != nullptr;
-  // Loop order (round 3): row group g = 4 accumulator rows (one C8 half-row) x
-  // all TN column tiles; every load of a group -- affine, bias, fp32 / C8
-  // residual -- is issued before the group's first store.  The pointers of ConvK
-  // may alias as far as hipcc knows, so a residual load written between stores
-  // stays behind the previous store: the loop this replaces made up to 16
-  // dependent round trips per 32 x 32 tile, each waited for with vmcnt(0) (ISA
-  // reading; the 256 -> 1024 expansion convs ran at 1.2 TB/s).
-  size_t colbase[TN], c8base[TN];
-  bool jok[TN];
-  const int prow = MODE == 1 ? a.Pfull : a.Pout;
-  // per-channel operands through descriptors: an absent one has extent 0 and
-  // loads as 0 -- no flag-dependent branch inside a group's load phase
-  const rsrc_t r_sc = make_rsrc(a.scale, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_sh = make_rsrc(a.shift, has_aff ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_bi = make_rsrc(a.bias, has_bias ? (unsigned)Cout * 4u : 0u);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int jc = n0 + wn * (BN / 2) + j * 32 + l31;
-    jok[j] = jc < a.J;
-    const int n = jc / a.Pout;
-    int p = jc - n * a.Pout;
-    // C8 images (side output, residual) exist for MODE 0 only: compact p
-    c8base[j] = ((size_t)n * (Cout >> 3) * a.Pout + p) * 16;
-    if (MODE == 1 && jok[j]) {
-      int l, hc, wc;
-      locate_out(a.g, p, l, hc, wc);
-      p = a.foff[l] + (2 * hc + a.ph) * a.fW[l] + 2 * wc + a.pw;
-    }
-    colbase[j] = (size_t)n * Cout * prow + p;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int rbase = m0 + wm * (BM / 2) + i * 32 + 4 * lk;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row0 = rbase + 8 * g;  // this lane's four rows: row0 .. row0 + 3
-      // byte offset of the lane's 8-byte half of its C8 row within an image
-      const size_t c8row = (size_t)(row0 >> 3) * a.Pout * 16 + (row0 & 4) * 2;
-      float sc[4], sh[4], bi[4], rv[TN][4];
-      uintx2 rraw[TN];
-      // group fence: the loads of this group stay behind the previous group's
-      // stores and none of them is consumed before all are issued
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned ro = (unsigned)(row0 + e) * 4u;  // >= Cout / absent: zeros
-        sc[e] = buf_load(r_sc, ro, 0);
-        sh[e] = buf_load(r_sh, ro, 0);
-        bi[e] = buf_load(r_bi, ro, 0);
-      }
-      if (has_res) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            rv[j][e] = (jok[j] && row0 + e < Cout)
-                           ? a.residual[colbase[j] + (size_t)(row0 + e) * prow]
-                           : 0.0f;
-      }
-      if (MODE == 0 && res8) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          rraw[j] = (jok[j] && row0 < Cout)
-                        ? *(const uintx2*)((const char*)a.res_c8 + c8base[j] + c8row)
-                        : uintx2{0u, 0u};
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (!jok[j]) continue;
-        floatx4_t q;
-        floatx4_t rq = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (MODE == 0 && res8)
-          rq = __builtin_convertvector(__builtin_bit_cast(bf16x4, rraw[j]), floatx4_t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const int row = row0 + e;
-          float v = 0.0f;
-          if (row < Cout) {
-            v = acc[i][j][r] * (has_aff ? sc[e] : 1.0f) + (sh[e] + bi[e]);
-            if (MODE == 0 && a.y_raw)
-              a.y_raw[colbase[j] + (size_t)row * prow] = acc[i][j][r];
-            if (has_res) v += rv[j][e];
-            if (MODE == 0 && res8) v += rq[e];
-            if (relu) v = fmaxf(v, 0.0f);
-            if (has_y) a.y[colbase[j] + (size_t)row * prow] = v;
-          }
-          q[e] = v;
-        }
-        // side output: this lane's four channels = half of a 16-byte C8 row
-        if (MODE == 0 && c8out && row0 < Cout)
-          *(uintx2*)((char*)a.y_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(q, bf16x4));
-        // the conv result before the affine as a C8 image (round 6: what the BN
-        // backward reads for d(gamma); 2 instead of 4 bytes per element)
-        if (MODE == 0 && a.raw_c8 && row0 < Cout) {
-          const floatx4_t rw = {acc[i][j][4 * g], acc[i][j][4 * g + 1],
-                                acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-          *(uintx2*)((char*)a.raw_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(rw, bf16x4));
-        }
-      }
-    }
-  }
+  LD_C8_EPILOGUE(m0 + wm * (BM / 2), n0 + wn * (BN / 2), true);
 }
 
 // fp32 (N, C, P) -> bf16 channel-blocked (N, C/8, P, 8), round to nearest even.

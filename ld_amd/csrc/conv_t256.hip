@@ -29,7 +29,7 @@
 //     a lane then holds four consecutive positions of a channel; each 32 x 32 tile
 //     takes a turn through a wave-private LDS buffer so that a wave instruction
 //     stores eight whole 128-byte rows.  C8 outputs / C8 residuals / the stride-2
-//     data-gradient classes keep the 4-wave kernel's epilogue.
+//     data-gradient classes take the epilogue all bf16 kernels share (conv_device.h).
 // Measured (profiles/r06_t256_stamps.txt, r06_t256_head.json): head tower 256 -> 256
 // 3 x 3, J = 44 800: 680 -> 890 TFLOP/s; main loop 72 % MFMA-busy (the DMA costs 23 %
 // of it), epilogue at the HBM write rate, 234 tiles on 256 CUs.
@@ -40,15 +40,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "conv_common.h"
+#include "conv_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
-typedef unsigned uintx2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float floatx4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // 16 bytes per lane, global -> LDS at (wave-uniform dst) + lane * 16
@@ -358,10 +353,10 @@ __global__ __launch_bounds__(512) void conv_t256_c8_kernel(ConvK a) {
   LD_STAMP_VAL(10, w_bar);
 #endif
 
-  const rsrc_t r_sc = make_rsrc(a.scale, a.scale ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_sh = make_rsrc(a.shift, a.scale ? (unsigned)Cout * 4u : 0u);
-  const rsrc_t r_bi = make_rsrc(a.bias, a.bias ? (unsigned)Cout * 4u : 0u);
   if constexpr (SWAP) {
+    const rsrc_t r_sc = make_rsrc(a.scale, a.scale ? (unsigned)Cout * 4u : 0u);
+    const rsrc_t r_sh = make_rsrc(a.shift, a.scale ? (unsigned)Cout * 4u : 0u);
+    const rsrc_t r_bi = make_rsrc(a.bias, a.bias ? (unsigned)Cout * 4u : 0u);
     // ---- epilogue, swapped roles.  In registers a lane holds one channel x four
     // consecutive positions (x 4 groups x TM x TN tiles); stored like that, a wave
     // instruction would touch 64 different cache lines with 16 bytes each (measured:
@@ -454,99 +449,8 @@ __global__ __launch_bounds__(512) void conv_t256_c8_kernel(ConvK a) {
 #endif
     return;
   }
-  // ---- epilogue: direct stores, 32 consecutive positions per accumulator row
-  // (the loop order and the branch-free operand loads of conv_tile_c8_kernel)
-  const bool has_res = a.residual != nullptr;
-  const bool res8 = a.res_c8 != nullptr;
-  const bool has_y = a.y != nullptr;
-  const bool c8out = a.y_c8 != nullptr;
-  const bool relu = a.relu != 0;
-  const bool has_aff = a.scale != nullptr, has_bias = a.bias != nullptr;
-  size_t colbase[TN], c8base[TN];
-  bool jok[TN];
-  const int prow = MODE == 1 ? a.Pfull : a.Pout;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int jc = n0 + wn * WTN + j * 32 + l31;
-    jok[j] = jc < a.J;
-    const int n = jc / a.Pout;
-    int p = jc - n * a.Pout;
-    c8base[j] = ((size_t)n * (Cout >> 3) * a.Pout + p) * 16;
-    if (MODE == 1 && jok[j]) {
-      int l, hc, wc;
-      locate_out(a.g, p, l, hc, wc);
-      p = a.foff[l] + (2 * hc + a.ph) * a.fW[l] + 2 * wc + a.pw;
-    }
-    colbase[j] = (size_t)n * Cout * prow + p;
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int rbase = m0 + wm * WTM + i * 32 + 4 * lk;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int row0 = rbase + 8 * g;
-      const size_t c8row = (size_t)(row0 >> 3) * a.Pout * 16 + (row0 & 4) * 2;
-      float sc[4], sh[4], bi[4], rv[TN][4];
-      uintx2 rraw[TN];
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned ro = (unsigned)(row0 + e) * 4u;
-        sc[e] = buf_load(r_sc, ro, 0);
-        sh[e] = buf_load(r_sh, ro, 0);
-        bi[e] = buf_load(r_bi, ro, 0);
-      }
-      if (has_res) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            rv[j][e] = (jok[j] && row0 + e < Cout)
-                           ? a.residual[colbase[j] + (size_t)(row0 + e) * prow]
-                           : 0.0f;
-      }
-      if (MODE == 0 && res8) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          rraw[j] = (jok[j] && row0 < Cout)
-                        ? *(const uintx2*)((const char*)a.res_c8 + c8base[j] + c8row)
-                        : uintx2{0u, 0u};
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (!jok[j]) continue;
-        floatx4_t q;
-        floatx4_t rq = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (MODE == 0 && res8)
-          rq = __builtin_convertvector(__builtin_bit_cast(bf16x4, rraw[j]), floatx4_t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * g + e;
-          const int row = row0 + e;
-          float v = 0.0f;
-          if (row < Cout) {
-            v = acc[i][j][r] * (has_aff ? sc[e] : 1.0f) + (sh[e] + bi[e]);
-            if (MODE == 0 && a.y_raw)
-              a.y_raw[colbase[j] + (size_t)row * prow] = acc[i][j][r];
-            if (has_res) v += rv[j][e];
-            if (MODE == 0 && res8) v += rq[e];
-            if (relu) v = fmaxf(v, 0.0f);
-            if (has_y) a.y[colbase[j] + (size_t)row * prow] = v;
-          }
-          q[e] = v;
-        }
-        if (MODE == 0 && c8out && row0 < Cout)
-          *(uintx2*)((char*)a.y_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(q, bf16x4));
-        if (MODE == 0 && a.raw_c8 && row0 < Cout) {  // as in conv_tile_c8_kernel
-          const floatx4_t rw = {acc[i][j][4 * g], acc[i][j][4 * g + 1],
-                                acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-          *(uintx2*)((char*)a.raw_c8 + c8base[j] + c8row) =
-              __builtin_bit_cast(uintx2, __builtin_convertvector(rw, bf16x4));
-        }
-      }
-    }
-  }
+  // C8 outputs / C8 residuals / the stride-2 data-gradient classes
+  LD_C8_EPILOGUE(m0 + wm * WTM, n0 + wn * WTN, true);
 #ifdef LD_T256_STAMP
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   LD_STAMP(4);

@@ -449,6 +449,96 @@ def test_conv_c8_only_output_and_c8_residual(bf16_mode, monkeypatch):
         got.reshape(2, 48, -1)
 
 
+def test_bf16_forward_kernels_share_one_epilogue(bf16_mode, monkeypatch):
+    """The four bf16 forward / data-gradient kernels (streaming KS = 1 and KS = 4,
+    LDS-tiled, C8-tiled, 8-wave) on shapes that leave every tile ragged: N = 2 on
+    the pyramid ((13, 21), (7, 11)) gives J = 700, a multiple of neither 32 nor
+    64, and 72 output channels end inside a 32-row slab (72 % 8 == 0: C8 rows
+    stay whole, which is all the kernels ask; the launches go through the C ABI
+    because layers.conv_forward_raw hands out C8 images per 32 channels only).
+
+    Forward: 3x3 stride 1, 64 -> 72, scale + shift + fp32 residual + ReLU with
+    the C8 side output, then C8-only with the residual as a C8 image (the
+    residual is bf16-exact, so both launches do the same arithmetic).
+    Data gradient: 3x3 stride 2 pad 1, 64 -> 64 on the 13x21 level: the odd
+    extents give four parity classes of 77 / 70 / 66 / 60 positions.
+
+    Every result against the rounded-operand reference within the file's fp32
+    summation-order bound; the LDS-tiled, C8-tiled and 8-wave kernels bit for bit
+    against one another; every C8 image equal to a conversion of the fp32 result."""
+    import ctypes as C
+    from ld_amd import layers as Y
+    from ld_amd import lib as L
+    dev = _dev()
+    monkeypatch.setattr(Y, '_C8_ALL', True)
+    g = torch.Generator().manual_seed(17)
+    levels, N, cin, cout = ((13, 21), (7, 11)), 2, 64, 72
+    P = sum(h * w for h, w in levels)
+    x = torch.randn(N, cin, P, generator=g)
+    w = torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9)**0.5
+    scale = torch.rand(cout, generator=g) + 0.5
+    shift = torch.randn(cout, generator=g)
+    res = _bf16r(torch.randn(N, cout, P, generator=g))
+    ref = torch.relu(_ref_conv_levels(_bf16r(x), _bf16r(w), None, 1, 1, levels) *
+                     scale[None, :, None] + shift[None, :, None] + res)
+    # data gradient: dy (2, 64, 7 * 11) -> dx (2, 64, 13 * 21)
+    dlevels = (levels[0], )
+    xg = torch.randn(N, 64, 13 * 21, generator=g)
+    wg = torch.randn(64, 64, 3, 3, generator=g) / 24.0
+    go = torch.randn(N, 64, 7 * 11, generator=g)
+    xr = xg.clone().requires_grad_(True)
+    _ref_conv_levels(xr, _bf16r(wg), None, 2, 1, dlevels).backward(_bf16r(go))
+
+    x, w, scale, shift, res, xg, wg, go = (
+        t.to(dev) for t in (x, w, scale, shift, res, xg, wg, go))
+    res8 = Y.to_c8(res)
+    d, _ = Y.conv_desc(N, cin, cout, 3, 3, 1, 1, levels)
+    wt, _ = Y.weight_images(w, False, False, True)
+    lib = L.get_lib()
+
+    def forward(c8_in, residual, residual_c8, want_y):
+        y = torch.empty(N, cout, P, device=dev) if want_y else None
+        img = torch.empty(N * cout * P, dtype=torch.bfloat16, device=dev)
+        ep = Y._epilogue(None, scale, shift, residual, True, img, residual_c8)
+        fn = getattr(lib, Y._FAMILIES[2 if c8_in else 1].forward)
+        L.check(fn(C.byref(d), L.ptr(Y.to_c8(x) if c8_in else x), L.ptr(wt),
+                   C.byref(ep), L.ptr(y), L.stream_ptr(dev)), 'forward')
+        return y, img
+
+    def as_c8(y):
+        return y.to(torch.bfloat16).reshape(N, cout // 8, 8, P).permute(
+            0, 1, 3, 2).reshape(-1)
+
+    tiled = []
+    # (switch, shape, one of the three kernels that agree bit for bit)
+    for env, val, exact in (('LD_CONV_BF16_SHAPE', '1x1x2x4x1', False),
+                            ('LD_CONV_BF16_SHAPE', '2x1x1x4x4', False),
+                            ('LD_CONV_BF16_SHAPE', '4x2x0x32x2', True),
+                            ('LD_CONV_C8_SHAPE', '2x2x2', True),
+                            ('LD_CONV_C8_SHAPE', '4x8x8x64', True)):
+        c8_in = env == 'LD_CONV_C8_SHAPE'
+        monkeypatch.setenv(env, val)
+        y, img = forward(c8_in, res, None, True)
+        _, only = forward(c8_in, None, res8, False)
+        _close(y, ref, what=f'{val} fwd')
+        assert torch.equal(img, as_c8(y)), f'{val}: C8 side output'
+        assert torch.equal(only, as_c8(y)), f'{val}: C8-only output, C8 residual'
+        Y.set_c8(c8_in)
+        try:
+            xd = xg.clone().requires_grad_(True)
+            yd, _ = Y.conv2d(xd, wg, None, 2, 1, dlevels)
+            yd.backward(go)
+        finally:
+            Y.set_c8(True)
+        _close(xd.grad, xr.grad, what=f'{val} stride-2 dgrad')
+        if exact:
+            tiled.append((val, y, xd.grad))
+        monkeypatch.delenv(env)
+    for val, y, dx in tiled[1:]:
+        assert torch.equal(y, tiled[0][1]), f'{val} fwd vs the LDS-tiled kernel'
+        assert torch.equal(dx, tiled[0][2]), f'{val} dgrad vs the LDS-tiled kernel'
+
+
 def test_c8_only_needs_bf16_mode():
     """Outside bf16 mode a C8Act operand is refused, not silently converted."""
     from ld_amd import layers as Y
