@@ -1003,6 +1003,15 @@ size_t ld_grad_norm_workspace_bytes(void);
 int ld_grad_norm(const float* grads, size_t n, const float* hyper, float* out,
                  void* workspace, size_t workspace_bytes, ld_stream_t stream);
 
+/* Virtual ranks (SGDTrainer(virtual_ranks=W)): out[c] = (table[0][c] + table[1][c] +
+ * ... + table[W-1][c]) / W for c < n, rows row_stride floats apart (row_stride >= n).
+ * fp32, summed in ascending rank order, then ONE division: the value all_reduce(SUM)
+ * + div_(world) gives every rank of a W-process job.  One thread per column, no
+ * atomics: the same bits on every run.  Serves the 2 loss normalisers
+ * (ld_head.py:338-341, 362-365) and the logged values (base.py:211-214). */
+int ld_vrank_reduce(const float* table, int W, int n, size_t row_stride, float* out,
+                    ld_stream_t stream);
+
 /* ---- GFLv2 distribution-guided quality branch (config 5, R-V2) ----------------
  * GFocalHead.forward_single's tail (gfocal_head.py:201-217) for all levels and
  * images in one launch, on the level-concatenated (N, C, P) tensors:

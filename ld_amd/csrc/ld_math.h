@@ -11,6 +11,7 @@
 // (SURVEY.md K12), which an FMA contraction would break.
 #pragma once
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -30,6 +31,16 @@ struct Box {
 
 LD_HD float fmaxf_(float a, float b) { return a > b ? a : b; }
 LD_HD float fminf_(float a, float b) { return a < b ? a : b; }
+
+// Mean over W virtual ranks of one column of a (W, n) table (ld_vrank_reduce,
+// optim.hip): the fp32 sum in ASCENDING rank order, then one division by W -- what
+// all_reduce(SUM) followed by div_(world) leaves on every rank of a W-process job
+// (core/utils/dist_utils.py:63-69, base.py:211-214).  `col` points at row 0.
+LD_HD float vrank_mean(const float* col, int W, size_t row_stride) {
+  float acc = col[0];
+  for (int r = 1; r < W; ++r) acc += col[(size_t)r * row_stride];
+  return acc / (float)W;
+}
 
 // Anchor of level stride `s` at grid cell (x, y): square of side 8*s centred on
 // (x*s, y*s) -- anchor_generator.py:142-185 (center_offset = 0,

@@ -10,7 +10,12 @@
 //   ld_grad_norm         torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2)
 //                        of the averaged gradient: [total_norm, clip_coef]
 //
-// Both are HBM-bound single passes.  Everything that may change between
+//   ld_vrank_reduce      the cross-rank mean of a virtual-rank step
+//                        (train.SGDTrainer(virtual_ranks=W)): a (W, n) table of
+//                        per-rank values -> their ascending-order fp32 sum / W,
+//                        what all_reduce(SUM) + div_(world) leaves on every rank
+//
+// The first two are HBM-bound single passes.  Everything that may change between
 // replays of a captured step (momentum, 1/world, the class table, max_norm, the
 // clip coefficient) is read from device memory.  Compiled with the default
 // contraction, like nn.hip: with one class and clip_coef == 1 the update is
@@ -18,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ld_launch.h"
+#include "ld_math.h"
 
 #include "../../include/ld_hip.h"
 
@@ -119,7 +125,28 @@ __global__ __launch_bounds__(kNormThreads) void grad_norm_final_kernel(
   }
 }
 
+// One thread per column; every lane of the launch runs the same W iterations (W is
+// a kernel argument: a wave-uniform trip count, no divergence), each a coalesced
+// read of one table row.  n is 2 (the loss normalisers) or ~9 (the logged values):
+// a single 64-lane workgroup in practice, bound by its launch, so nothing is staged
+// or vectorised.  Rank order and the IEEE division are the result's definition.
+__global__ __launch_bounds__(64) void vrank_reduce_kernel(
+    const float* __restrict__ table, int W, int n, size_t row_stride,
+    float* __restrict__ out) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= n) return;
+  out[c] = ld::vrank_mean(table + c, W, row_stride);
+}
+
 }  // namespace
+
+extern "C" int ld_vrank_reduce(const float* table, int W, int n, size_t row_stride,
+                               float* out, ld_stream_t stream) {
+  if (!table || !out || W < 1 || n < 1 || row_stride < (size_t)n) return LD_EINVAL;
+  LD_LAUNCH(vrank_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0,
+            (hipStream_t)stream, table, W, n, row_stride, out);
+  return (int)hipGetLastError();
+}
 
 extern "C" int ld_sgd_step_classes(float* params, const float* grads,
                                    float* momentum_buf, size_t n,

@@ -37,7 +37,8 @@ import numpy as np
 
 from .pipeline import DevicePipeline, DistributedGroupSampler, GroupSampler
 
-__all__ = ['imread', 'batch_seed', 'build_dataloader', 'DeviceDataLoader']
+__all__ = ['imread', 'batch_seed', 'build_dataloader', 'DeviceDataLoader',
+           'VirtualRankLoader']
 
 MAX_THREADS = 16
 LOOK_AHEAD = 2
@@ -279,12 +280,120 @@ class DeviceDataLoader:
             pass
 
 
+class VirtualRankLoader:
+    """The loaders of ranks 0 .. W-1 of a W-process job in one process
+    (``SGDTrainer(virtual_ranks=W)``): item ``i`` is the list of W device
+    batches, the ``r``-th exactly batch ``i`` of ``DeviceDataLoader(dataset,
+    samples_per_gpu, ..., dist=True, num_replicas=W, rank=r, seed=seed)`` --
+    the same ``DistributedGroupSampler`` order, the same ``(seed, epoch,
+    index)`` draws, the same annotations.  ``len()`` is one rank's.
+
+    The W rank loaders share ONE decode pool of ``min(workers_per_gpu * 2,
+    16)`` threads (or ``num_threads``), whatever W is, and at most
+    ``LOOK_AHEAD`` steps (of W batches each) are started beyond the one
+    handed out."""
+
+    def __init__(self, dataset, samples_per_gpu, workers_per_gpu,
+                 virtual_ranks, shuffle=True, seed=None, device=None,
+                 num_threads=None):
+        W = int(virtual_ranks)
+        if W < 1:
+            raise NotImplementedError(
+                f'virtual_ranks={virtual_ranks}: a job has at least one rank')
+        if getattr(dataset, 'test_mode', False):
+            raise NotImplementedError(
+                f'virtual_ranks={W} with a test-mode dataset: virtual ranks '
+                'are a train-step notion')
+        self.virtual_ranks = W
+        self.ranks = [DeviceDataLoader(dataset, samples_per_gpu,
+                                       workers_per_gpu, dist=True,
+                                       shuffle=shuffle, seed=seed,
+                                       device=device, num_replicas=W, rank=r,
+                                       num_threads=num_threads)
+                      for r in range(W)]
+        self.dataset, self.seed = dataset, seed
+        self.num_threads = self.ranks[0].num_threads
+        self.epoch = 0
+        self._pool = None
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.ranks[0])
+
+    def _share_pool(self):
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(self.num_threads,
+                                            thread_name_prefix='ld-decode')
+        for ld in self.ranks:
+            ld._pool = self._pool
+
+    def host_batch(self, epoch, index):
+        """The W host halves of step ``index`` of ``epoch``, rank 0's first."""
+        self._share_pool()
+        jobs = [ld._submit(ld.epoch_order(epoch), epoch, index)
+                for ld in self.ranks]
+        return [ld._finish(j) for ld, j in zip(self.ranks, jobs)]
+
+    def host_batches(self, epoch=None):
+        epoch = self.epoch if epoch is None else int(epoch)
+        self._share_pool()
+        orders = [ld.epoch_order(epoch) for ld in self.ranks]
+        n = len(self)
+        jobs, nxt = deque(), 0
+        while True:
+            while nxt < n and len(jobs) < LOOK_AHEAD + 1:
+                jobs.append([ld._submit(o, epoch, nxt)
+                             for ld, o in zip(self.ranks, orders)])
+                nxt += 1
+            if not jobs:
+                return
+            step = jobs.popleft()
+            yield [ld._finish(j) for ld, j in zip(self.ranks, step)]
+
+    def device_batch(self, hosts):
+        return [ld.device_batch(h) for ld, h in zip(self.ranks, hosts)]
+
+    def __iter__(self):
+        for hosts in self.host_batches():
+            yield self.device_batch(hosts)
+
+    def __call__(self, epoch):
+        self.set_epoch(epoch)
+        return iter(self)
+
+    def close(self):
+        for ld in self.ranks:
+            ld._pool = None
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def build_dataloader(dataset, samples_per_gpu, workers_per_gpu, dist=False,
-                     shuffle=True, seed=None, device=None, **kwargs):
+                     shuffle=True, seed=None, device=None, virtual_ranks=None,
+                     **kwargs):
     """builder.py:76-140 -> a ``DeviceDataLoader``.  ``num_gpus`` (DataParallel
     batches) is refused: one process drives one device.  ``num_threads=``
-    (1 .. 16) sets the decode pool's size directly."""
+    (1 .. 16) sets the decode pool's size directly.  ``virtual_ranks=W`` gives
+    a ``VirtualRankLoader``: the W rank-local batches of every step of a
+    W-process job."""
     if kwargs.pop('num_gpus', 1) != 1:
         raise NotImplementedError('num_gpus > 1: one process per device')
+    if virtual_ranks is not None:
+        if dist:
+            raise NotImplementedError(
+                f'virtual_ranks={virtual_ranks} with dist=True: virtual ranks '
+                'composed with real ranks are not implemented')
+        return VirtualRankLoader(dataset, samples_per_gpu, workers_per_gpu,
+                                 virtual_ranks, shuffle, seed, device,
+                                 **kwargs)
     return DeviceDataLoader(dataset, samples_per_gpu, workers_per_gpu, dist,
                             shuffle, seed, device, **kwargs)

@@ -202,10 +202,13 @@ class SingleStageDetector(nn.Module):
             A.write_png(out_file, out[:, :, ::-1])
         return out
 
-    def _parse_losses(self, losses):
+    def _parse_losses(self, losses, out=None):
         """base.py:185-218.  Same keys and values; computed on the device in
         O(1) launches, with ONE all-reduce for all log values and a lazy D2H
-        copy (the reference does one all-reduce + .item() per key)."""
+        copy (the reference does one all-reduce + .item() per key).
+        ``out``: optional callable n -> fp32 device tensor (n,) that receives
+        the n logged values (a virtual-rank step: this rank's row of the table
+        ld_vrank_reduce averages)."""
         table = getattr(losses, 'table', None)
         if table is not None:
             names = list(losses.keys())
@@ -236,7 +239,9 @@ class SingleStageDetector(nn.Module):
         else:
             loss = key_sums.index_select(
                 0, _device_index(tuple(sel), key_sums.device)).sum()
-        logged = torch.cat([key_sums.detach(), loss.detach().reshape(1)])
+        parts = [key_sums.detach(), loss.detach().reshape(1)]
+        logged = torch.cat(parts) if out is None else \
+            torch.cat(parts, out=out(len(names) + 1))
         from .train import _diag_skip, collectives_on
         if collectives_on() and not _diag_skip('logs'):
             logged = logged.clone()

@@ -438,6 +438,12 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         host syncs (ld_head.py:338-341,362-363)."""
         import torch.distributed as dist
         from .train import _diag_skip, collectives_on
+        slot = LB.virtual_norm_slot()
+        if slot is not None:
+            # SGDTrainer(virtual_ranks=W): this micro-batch's partials go into
+            # its row of the step's table; the block's main part runs once the
+            # mean over the W rows exists (lossblock.DeferredNorm)
+            return slot
         if not collectives_on() or _diag_skip('norm'):
             return None
         ws = float(dist.get_world_size())

@@ -260,7 +260,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -548,6 +548,7 @@ SIGNATURES = {
                                       _vp]),
     'ld_grad_norm_workspace_bytes': (_sz, []),
     'ld_grad_norm': (C.c_int, [_vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    'ld_vrank_reduce': (C.c_int, [_vp, _i32, _i32, _sz, _vp, _vp]),
     'ld_levels_mix': (C.c_int, [_vp, _vp, C.c_longlong, _i32, _vp, _vp, _vp]),
     'ld_levels_abs_err_workspace_bytes': (_sz, [_LV, _i32, _i32, _i32]),
     'ld_levels_abs_err': (C.c_int, [_LV, _vp, _vp, _i32, _i32, _i32, _vp, _vp,

@@ -434,6 +434,103 @@ class _LossState:
     pass
 
 
+class DeferredNorm:
+    """``reduce_norm`` hook of ONE micro-batch of a virtual-rank step
+    (``VirtualRanks``).  The prepass writes this rank's partials into ``row``
+    and the block stops there; ``complete()`` runs the main and finalise parts
+    later, reading the normalisers from ``mean`` -- by then the cross-rank
+    mean of all W rows (ld_vrank_reduce).  Nothing of the prepass but
+    ``weight_targets`` / ``score`` (tensors of the call) and the normalisers
+    is read by the main part, so the W prepasses may share the 'loss'
+    workspace; the main / finalise pairs run one after the other."""
+
+    def __init__(self, row, mean):
+        self.row, self.mean, self._main = row, mean, None
+
+    def complete(self):
+        main, self._main = self._main, None
+        if main is not None:
+            main()
+
+
+_VRANKS = [None]
+
+
+class VirtualRanks:
+    """The device tables of ``SGDTrainer(virtual_ranks=W)``: the per-rank
+    partials of the loss normalisers, (W, 4) with (sum_img max(P_img, 1),
+    sum weight_targets) in columns 0:2 as ld_loss_prepass leaves them, their
+    mean ``norm`` (4,), and the per-rank logged values (W, n).  Inside
+    ``with vr:`` every dense head's ``_norm_reducer`` hands the loss block a
+    ``DeferredNorm`` of rank ``vr.rank``."""
+
+    def __init__(self, W, device):
+        self.W, self.device = int(W), device
+        self.partials = torch.zeros((self.W, 4), dtype=torch.float32,
+                                    device=device)
+        self.norm = torch.zeros(4, dtype=torch.float32, device=device)
+        self.logs = None
+        self.rank = 0
+        self.slots = []
+
+    def __enter__(self):
+        if _VRANKS[0] is not None:
+            raise L.LdError('a virtual-rank step is already collecting')
+        self.slots, self.rank = [[] for _ in range(self.W)], 0
+        _VRANKS[0] = self
+        return self
+
+    def __exit__(self, *exc):
+        _VRANKS[0] = None
+
+    def slot(self):
+        if self.slots[self.rank]:
+            # a second loss block of the same forward would need normalisers of
+            # its own: nothing in this project has one
+            raise NotImplementedError(
+                'virtual ranks: two reduced loss blocks in one forward')
+        d = DeferredNorm(self.partials[self.rank], self.norm)
+        self.slots[self.rank].append(d)
+        return d
+
+    def _reduce(self, table, out):
+        L.check(L.get_lib().ld_vrank_reduce(
+            L.ptr(table), self.W, table.shape[1], table.stride(0), L.ptr(out),
+            L.stream_ptr(self.device)), 'ld_vrank_reduce')
+        return out
+
+    def reduce_norm(self):
+        """norm <- ascending-order sum of the W partial rows / W (one launch;
+        none when no block asked for a reduction, e.g. LDRetinaHead)."""
+        if any(self.slots):
+            self._reduce(self.partials, self.norm)
+
+    def complete(self, rank):
+        for d in self.slots[rank]:
+            d.complete()
+        self.slots[rank] = []
+
+    def log_row(self, n):
+        """Where micro-batch ``self.rank`` writes its n logged values."""
+        if self.logs is None or self.logs.shape[1] != n:
+            self.logs = torch.empty((self.W, n), dtype=torch.float32,
+                                    device=self.device)
+        return self.logs[self.rank]
+
+    def reduce_logs(self):
+        """The per-key mean over the W micro-batches, a fresh (n,) tensor."""
+        out = torch.empty(self.logs.shape[1], dtype=torch.float32,
+                          device=self.device)
+        return self._reduce(self.logs, out)
+
+
+def virtual_norm_slot():
+    """The DeferredNorm of the micro-batch being collected, or None outside a
+    virtual-rank step."""
+    vr = _VRANKS[0]
+    return None if vr is None else vr.slot()
+
+
 def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
                        reduce_norm=None, upstream=None, kd_s=None, kd_t=None,
                        ctr=None):
@@ -472,7 +569,9 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
                                L.make_maps(g_kd))
     wt = torch.empty((N, A), dtype=torch.float32, device=device)
     score = torch.empty((N, A), dtype=torch.float32, device=device)
-    norm = torch.zeros(4, dtype=torch.float32, device=device)
+    deferred = isinstance(reduce_norm, DeferredNorm)
+    norm = reduce_norm.row if deferred else \
+        torch.zeros(4, dtype=torch.float32, device=device)
     losses = torch.empty((L.LD_NUM_LOSS_KEYS, geom.num_levels),
                          dtype=torch.float32, device=device)
     need = lib.ld_loss_workspace_bytes(C.byref(geom))
@@ -484,12 +583,43 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
         L.ptr(targets['vlr']), L.ptr(targets['counts']), L.ptr(wt),
         L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
         'ld_loss_prepass')
-    if reduce_norm is not None:
-        reduce_norm(norm)
     up = None
     if upstream is not None:
         up = L.require_device(upstream.contiguous(), torch.float32,
                               'upstream')
+    g_ctr = None
+    if hp.flags & L.LD_LOSS_ATSS:
+        if ctr is None:
+            raise L.LdError('LD_LOSS_ATSS needs the centerness maps')
+        g_ctr = alloc_level_views(ctr)
+    grads = dict(cls=g_cls, reg=g_reg, x=g_x, kd=g_kd, ctr=g_ctr)
+    aux = dict(weight_targets=wt, score=score)
+
+    # the map structs hold raw pointers: a deferred main part keeps the tensors
+    # behind them alive itself
+    keep = (cls, reg, t_cls, t_reg, x, t_x, kd_s, kd_t, grads, aux)
+
+    def _main(norm, keep=keep):
+        _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg,
+                         m_x, m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x,
+                         m_kds, m_kdt, mg_kd, ctr, g_ctr, ws, losses, st)
+
+    if deferred:
+        # virtual ranks: the main part waits for the other ranks' prepasses
+        reduce_norm._main = lambda: _main(reduce_norm.mean)
+        return losses, grads, reduce_norm.mean.view(4), aux
+    if reduce_norm is not None:
+        reduce_norm(norm)
+    _main(norm)
+    return losses, grads, norm, aux
+
+
+def _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg, m_x,
+                     m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x, m_kds,
+                     m_kdt, mg_kd, ctr, g_ctr, ws, losses, st):
+    """main -> (centerness) -> finalise of ``loss_block_forward`` with the
+    normalisers in ``norm``."""
+    split = m_kds is not None
     L.check(lib.ld_loss_main_parts(
         C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
         C.byref(m_tcls), C.byref(m_treg), C.byref(m_x), C.byref(m_tx),
@@ -501,11 +631,7 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
         C.byref(m_kds) if split else None, C.byref(m_kdt) if split else None,
         C.byref(mg_kd) if split else None, L.ptr(ws), ws.numel(), 15, st),
         'ld_loss_main')
-    g_ctr = None
-    if hp.flags & L.LD_LOSS_ATSS:
-        if ctr is None:
-            raise L.LdError('LD_LOSS_ATSS needs the centerness maps')
-        g_ctr = alloc_level_views(ctr)
+    if g_ctr is not None:
         L.check(lib.ld_loss_centerness(
             C.byref(geom), C.byref(hp), C.byref(L.make_maps(ctr)),
             L.ptr(targets['labels']), L.ptr(score), L.ptr(norm), L.ptr(up),
@@ -514,8 +640,6 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     L.check(lib.ld_loss_finalize(
         C.byref(geom), C.byref(hp), L.ptr(targets['counts']), L.ptr(norm),
         L.ptr(ws), L.ptr(losses), st), 'ld_loss_finalize')
-    return losses, dict(cls=g_cls, reg=g_reg, x=g_x, kd=g_kd, ctr=g_ctr), \
-        norm, dict(weight_targets=wt, score=score)
 
 
 class LDLossBlock(torch.autograd.Function):

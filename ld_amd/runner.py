@@ -8,7 +8,10 @@ step, restated for ``SGDTrainer`` / ``AutoStepper``.
 
 ``make_epoch_batches(epoch)`` returns the epoch's device batches (dicts of
 ``img``, ``img_metas``, ``gt_bboxes``, ``gt_labels``); a
-``dataloader.DeviceDataLoader`` over a ``datasets`` dataset is one.  Config
+``dataloader.DeviceDataLoader`` over a ``datasets`` dataset is one.  With
+``SGDTrainer(virtual_ranks=W)`` the items are lists of W such batches
+(``dataloader.VirtualRankLoader``): one log line per optimizer step, ``iter``
+counted as the W-rank job counts it.  Config
 keys read: ``runner.max_epochs`` (or the older ``total_epochs``),
 ``log_config.interval``, ``checkpoint_config.interval`` and ``resume_from``.
 
@@ -130,6 +133,11 @@ class EpochRunner:
         if max_epochs is None:
             raise ValueError('EpochRunner: no runner.max_epochs / total_epochs '
                              'in the config and none given')
+        lw = getattr(make_epoch_batches, 'virtual_ranks', None)
+        tw = getattr(self.trainer, 'virtual_ranks', 1)
+        if lw is not None and lw != tw:
+            raise ValueError(f'EpochRunner: a loader of {lw} virtual ranks '
+                             f'with a trainer of {tw}')
         if self.resume_from:
             CK.resume(self.trainer, self.resume_from)
         pipelined = getattr(self.stepper, 'mode', None) == 'pipelined'

@@ -314,11 +314,28 @@ class SGDTrainer:
       * ``lr_schedule`` (a schedule.StepLrSchedule): applied from
         (``epoch``, ``iter``) before every step, eager or replayed.
     Without ``param_classes`` and ``grad_clip`` the update is the one
-    ld_sgd_step / ld_sgd_step_dev launch of the plain constructor."""
+    ld_sgd_step / ld_sgd_step_dev launch of the plain constructor.
+
+    ``virtual_ranks=W``: one ``step`` consumes the W
+    micro-batches ranks 0..W-1 of a W-process job would hold and applies that
+    job's update -- the loss normalisers and the logged values are the
+    ascending-order means over the W micro-batches (ld_vrank_reduce), the
+    gradients accumulate in the arena in rank order and the optimizer launch
+    scales them by 1/W.  ``W = 1`` is the plain step."""
 
     def __init__(self, model, lr, momentum=0.9, weight_decay=1e-4,
                  bucket_bytes=32 << 20, tail_bytes=8 << 20, param_classes=None,
-                 grad_clip=None, lr_schedule=None):
+                 grad_clip=None, lr_schedule=None, virtual_ranks=1):
+        W = int(virtual_ranks)
+        if W < 1:
+            raise NotImplementedError(
+                f'virtual_ranks={virtual_ranks}: a job has at least one rank')
+        if W > 1 and dist.is_available() and dist.is_initialized():
+            raise NotImplementedError(
+                f'virtual_ranks={W} under a process group: virtual ranks '
+                'composed with real ranks are not implemented')
+        self.virtual_ranks = W
+        self._vranks = None
         self.model = model
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.base_lr = lr  # initial lr of an unscaled group (mmcv's initial_lr)
@@ -343,6 +360,16 @@ class SGDTrainer:
             self._init_classes()
         if lr_schedule is not None:
             lr_schedule.before_run(self._base_lrs())
+        if W > 1 and hasattr(model, 'TEACHER_SLOTS'):
+            # the frozen teacher's replayed outputs live in rotating slots; W
+            # micro-batches hold theirs until their loss block's main part, on
+            # top of the two steps of look-ahead the rotation already allows
+            model.TEACHER_SLOTS = max(model.TEACHER_SLOTS, W + 2)
+
+    def _grad_scale(self):
+        """The optimizer's gradient scale: the arena holds the SUM over the
+        (real or virtual) ranks, the update takes the mean."""
+        return 1.0 / (_world() * self.virtual_ranks)
 
     @classmethod
     def from_config(cls, model, cfg, **kw):
@@ -454,12 +481,12 @@ class SGDTrainer:
             return
         if self._classes is not None:
             max_norm = self.grad_clip['max_norm'] if self.grad_clip else 0.0
-            vals = tuple([float(self.momentum), 1.0 / _world(), float(max_norm),
+            vals = tuple([float(self.momentum), self._grad_scale(), float(max_norm),
                           0.0] + self._classes.table(self._class_lrs(),
                                                      self._class_wds()))
         else:
             vals = (float(self.lr), float(self.momentum),
-                    float(self.weight_decay), 1.0 / _world())
+                    float(self.weight_decay), self._grad_scale())
         if vals == self._hyper_last:
             return  # unchanged since the last push: the device copy is current
         if self._hyper_host is None:
@@ -593,7 +620,17 @@ class SGDTrainer:
         """One iteration on ``data``.  ``next_data`` (optional): the batch of
         the FOLLOWING step, already on the device -- a distillation detector
         then runs its frozen teacher on it concurrently with this step
-        (KnowledgeDistillationSingleStageDetector.prefetch_teacher)."""
+        (KnowledgeDistillationSingleStageDetector.prefetch_teacher).
+        With ``virtual_ranks=W`` > 1 ``data`` (and ``next_data``) is a sequence
+        of exactly W batches, rank 0's first."""
+        if self.virtual_ranks > 1:
+            return self._step_virtual(data, next_data)
+        if not isinstance(data, dict):
+            if len(data) != 1:
+                raise ValueError(f'step: {len(data)} batches for 1 rank')
+            data = data[0]
+            if next_data is not None and not isinstance(next_data, dict):
+                next_data = next_data[0]
         if next_data is not None and hasattr(self.model, 'prefetch_teacher'):
             self.model.prefetch_teacher(next_data['img'])
         self._apply_schedule()
@@ -614,17 +651,90 @@ class SGDTrainer:
         finally:
             if scoped:
                 head.unit_upstream = False
+        return self._update(loss.detach(), log_vars, len(data['img_metas']))
+
+    def _check_missing(self):
+        # the single SGD launch applies weight decay / momentum to every
+        # arena parameter; torch.optim.SGD skips parameters whose grad is
+        # None.  Equal only if every trainable parameter got a gradient.
+        missing = [i for i, p in enumerate(self.arena.order)
+                   if id(p) not in self.arena._seen]
+        if missing:
+            raise RuntimeError(
+                f'{len(missing)} trainable parameters received no '
+                'gradient this step; the fused SGD launch would still '
+                'decay them (torch.optim.SGD would not)')
+
+    def _step_virtual(self, batches, next_data=None):
+        """One optimizer step of a W-rank job on its W rank-local batches."""
+        from . import lossblock as LB
+        from .heads import LazyScalars
+        W = self.virtual_ranks
+        if isinstance(batches, dict) or len(batches) != W:
+            raise ValueError(
+                f'step: virtual_ranks={W} takes a sequence of exactly {W} '
+                'batches, got ' + ('one dict' if isinstance(batches, dict)
+                                   else str(len(batches))))
+        if torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError(
+                f'virtual_ranks={W} inside a hipGraph capture')
+        model = self.model
+        prefetch = getattr(model, 'prefetch_teacher', None)
+        self._apply_schedule()
+        self.arena.zero_grad()
+        vr = self._vranks
+        if vr is None:
+            vr = self._vranks = LB.VirtualRanks(W, self.arena.flat_grad.device)
+        head = getattr(model, 'bbox_head', None)
+        scoped = head is not None and hasattr(head, 'unit_upstream')
+        if scoped:
+            head.unit_upstream = True
+        enabled = self.arena.enabled
+        names = None
+        try:
+            # every forward (teacher, student, targets, prepass) before any loss
+            # block's main part: the partials depend on the student's scores
+            losses = []
+            with vr:
+                for r, data in enumerate(batches):
+                    if prefetch is not None:
+                        # the frozen teacher one micro-batch ahead on its stream
+                        nxt = batches[r + 1] if r + 1 < W else \
+                            next_data[0] if next_data is not None else None
+                        if nxt is not None:
+                            prefetch(nxt['img'])
+                    vr.rank = r
+                    losses.append(model(**data))
+            vr.reduce_norm()
+            for r in range(W):
+                vr.rank = r
+                vr.complete(r)
+                loss, lv = model._parse_losses(losses[r], out=vr.log_row)
+                losses[r] = None
+                names = list(lv._keys)
+                # the parameters' pending-use counts reach zero, and the
+                # buckets complete, during the LAST backward only
+                self.arena.enabled = enabled and r + 1 == W
+                loss.backward()
+                del loss, lv
+                if r + 1 < W:
+                    # a layer's deferred partials are overwritten by its next
+                    # backward: sum this micro-batch's into the arena
+                    Y.wgrad_join()
+                    Y.flush_deferred()
+        finally:
+            self.arena.enabled = enabled
+            if scoped:
+                head.unit_upstream = False
+        logged = vr.reduce_logs()
+        return self._update(logged[-1], LazyScalars(names, logged),
+                            sum(len(d['img_metas']) for d in batches))
+
+    def _update(self, loss, log_vars, num_samples):
+        """finish -> (gradient norm) -> the optimizer launch; the step's
+        result."""
         if self.check_grads:
-            # the single SGD launch applies weight decay / momentum to every
-            # arena parameter; torch.optim.SGD skips parameters whose grad is
-            # None.  Equal only if every trainable parameter got a gradient.
-            missing = [i for i, p in enumerate(self.arena.order)
-                       if id(p) not in self.arena._seen]
-            if missing:
-                raise RuntimeError(
-                    f'{len(missing)} trainable parameters received no '
-                    'gradient this step; the fused SGD launch would still '
-                    'decay them (torch.optim.SGD would not)')
+            self._check_missing()
         self.arena.finish()
         self._push_hyper()
         norm = None
@@ -642,14 +752,22 @@ class SGDTrainer:
         else:
             Y.sgd_step(self.arena.flat_param, self.arena.flat_grad,
                        self.flat_momentum, self.lr, self.momentum,
-                       self.weight_decay, 1.0 / _world(), hyper=self._hyper_dev)
+                       self.weight_decay, self._grad_scale(),
+                       hyper=self._hyper_dev)
         if not torch.cuda.is_current_stream_capturing():
             self.iter += 1  # a capture executes nothing: not an iteration
-        out = dict(loss=loss.detach(), log_vars=log_vars,
-                   num_samples=len(data['img_metas']))
+        out = dict(loss=loss, log_vars=log_vars, num_samples=num_samples)
         if norm is not None:
             out['grad_norm'] = norm[0]
         return out
+
+
+def _refuse_virtual_ranks(trainer, what):
+    W = getattr(trainer, 'virtual_ranks', 1)
+    if W > 1:
+        raise NotImplementedError(
+            f'virtual_ranks={W} with {what}: a virtual-rank step is enqueued '
+            'eagerly (its W live forward graphs are not captured or replayed)')
 
 
 def _refuse_collectives_in_capture(what):
@@ -773,6 +891,7 @@ class GraphedStep:
         """``launcher='list'``: the captured graph is re-issued by a C launch loop
         (``_StepList``) instead of hipGraphLaunch -- same launches, same buffers."""
         from . import lossblock as LB
+        _refuse_virtual_ranks(trainer, f"GraphedStep(launcher='{launcher}')")
         _refuse_collectives_in_capture('GraphedStep')
         if launcher == 'graph':
             _warn_graph_queues('GraphedStep')
@@ -888,6 +1007,8 @@ class PipelinedGraphedStep:
     def __init__(self, trainer, first, second, warmup=1, max_gt=128,
                  launcher='graph'):
         from . import lossblock as LB
+        _refuse_virtual_ranks(
+            trainer, f"PipelinedGraphedStep(launcher='{launcher}')")
         _refuse_collectives_in_capture('PipelinedGraphedStep')
         if launcher == 'graph':
             _warn_graph_queues('PipelinedGraphedStep')
@@ -1041,6 +1162,9 @@ class AutoStepper:
             raise ValueError(f'AutoStepper: unknown mode {mode!r}')
         if launcher not in ('graph', 'list'):
             raise ValueError(f'AutoStepper: unknown launcher {launcher!r}')
+        if mode != 'eager':
+            _refuse_virtual_ranks(
+                trainer, f"AutoStepper(mode='{mode}', launcher='{launcher}')")
         self.trainer, self.mode, self.launcher = trainer, mode, launcher
         self.warmup, self.max_gt = int(warmup), int(max_gt)
         # one graph per padded shape, at most max_graphs of them (least recently

@@ -2,7 +2,8 @@
 device.
 
     python tools/train.py CONFIG [--work-dir DIR] [--resume-from CKPT] \\
-        [--no-validate] [--seed N] [--deterministic] [--cfg-options k=v ...]
+        [--no-validate] [--seed N] [--deterministic] [--cfg-options k=v ...] \\
+        [--virtual-gpus W]
 
 Builds the config's detector, ``cfg.data.train`` (and ``cfg.data.val`` unless
 --no-validate), a ``DeviceDataLoader`` seeded with --seed,
@@ -10,6 +11,11 @@ Builds the config's detector, ``cfg.data.train`` (and ``cfg.data.val`` unless
 the work dir; checkpoints carry ``CLASSES`` in their meta.  With a seed a run
 is reproducible batch for batch (the loader's draws are a function of (seed,
 epoch, batch)).  Not supported, refused by name: --launcher other than none.
+
+``--virtual-gpus W`` is the reference's ``dist_train.sh CONFIG W`` on one
+device: every optimizer step takes the W rank-local batches of a W-process
+job (``SGDTrainer(virtual_ranks=W)``, ``build_dataloader(virtual_ranks=W)``)
+and ``optimizer.lr`` stays as the config wrote it for that job.
 """
 import argparse
 import os
@@ -35,6 +41,8 @@ def parse_args(argv=None):
     p.add_argument('--cfg-options', nargs='+', action=DictAction,
                    help='override config settings, KEY=VALUE')
     p.add_argument('--device', default='cuda:0')
+    p.add_argument('--virtual-gpus', type=int, default=1, metavar='W',
+                   help='train as a W-process job would, on one device')
     add_refused(p, REFUSED)
     args = p.parse_args(argv)
     check_refused(p, args, REFUSED)
@@ -81,8 +89,10 @@ def main(argv=None):
     dataset = build_dataset(cfg.data['train'])
     model.CLASSES = dataset.CLASSES  # saved into the checkpoints' meta
     workers = cfg.data.get('workers_per_gpu', 1)
+    W = args.virtual_gpus
     loader = build_dataloader(dataset, cfg.data['samples_per_gpu'], workers,
-                              dist=False, seed=args.seed, device=device)
+                              dist=False, seed=args.seed, device=device,
+                              virtual_ranks=W if W != 1 else None)
     val = None
     if not args.no_validate and cfg.data.get('val') is not None:
         vcfg = dict(cfg.data['val'])
@@ -91,7 +101,7 @@ def main(argv=None):
         val = (build_dataloader(vset, vspg, workers, dist=False,
                                 shuffle=False, device=device), vset,
                dict(cfg.get('evaluation', {}) or {}))
-    trainer = SGDTrainer.from_config(model, cfg)
+    trainer = SGDTrainer.from_config(model, cfg, virtual_ranks=W)
     runner = EpochRunner(trainer, cfg, work_dir, val=val)
     runner.run(loader)
     torch.cuda.synchronize(device)
