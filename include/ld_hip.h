@@ -839,6 +839,36 @@ typedef struct {
 int ld_bn_act_backward_nsplit(int N, int C, int P, int c8);
 int ld_bn_bwd_finalize_batch(const ld_bn_fin_job_t* jobs, const int32_t* block_job,
                              int nblocks, ld_stream_t stream);
+/* BatchNorm2d with BATCH statistics (norm_eval=False: resnet.py:639-648 leaves the
+ * unfrozen stages' BN in training mode) on (N, C, P), M = N * P >= 2 values per
+ * channel.  Forward: per-channel sum x, sum x^2 in fp64 (slice partials in the
+ * workspace, one fixed-order final, no atomics); mean = s/M, rstd = 1/sqrt(q/M -
+ * mean^2 + eps) (biased variance, formed in fp64), scale = gamma*rstd, shift = beta
+ * - mean*scale, all four [C] fp32 outputs; then y = act(x*scale + shift (+
+ * residual)) as ld_bn_act_forward.  With update_running != 0 the final launch also
+ * sets running_mean = (1-m) running_mean + m mean, running_var = (1-m) running_var
+ * + m var M/(M-1) (unbiased) and *num_batches_tracked += 1 (a device int64), m =
+ * momentum; any of the three may be NULL.  16-byte loads iff P % 4 == 0 and the
+ * tensors are 16-byte aligned.  LD_EINVAL (nothing launched) for M < 2 or a
+ * workspace smaller than ld_bn_train_workspace_bytes(N, C, P). */
+size_t ld_bn_train_workspace_bytes(int N, int C, int P);
+int ld_bn_train_forward(const float* x, const float* residual, const float* gamma,
+                        const float* beta, float eps, double momentum, int N, int C,
+                        int P, int relu, int update_running, float* running_mean,
+                        float* running_var, int64_t* num_batches_tracked, float* y,
+                        float* mean, float* rstd, float* scale, float* shift,
+                        void* workspace, size_t workspace_bytes, ld_stream_t stream);
+/* Backward of the above from its saved y, x and [C] scale / mean / rstd: dz = relu ?
+ * dy*(y>0) : dy; dbeta = sum dz, dgamma = sum dz*xhat, xhat = (x-mean)*rstd (fp64
+ * slice partials, fixed-order final; either may be NULL, the sums are formed
+ * regardless); dx = scale*(dz - dbeta/M - xhat*dgamma/M) (NULL: skipped); dres = dz
+ * (NULL: skipped).  accumulate: 0 overwrites dgamma / dbeta, 1 adds to them;
+ * LD_GRAD_DEFER is refused (dx needs the finished sums in this call). */
+int ld_bn_train_backward(const float* dy, const float* y, const float* x,
+                         const float* scale, const float* mean, const float* rstd,
+                         int N, int C, int P, int relu, float* dx, float* dres,
+                         float* dgamma, float* dbeta, int accumulate, void* workspace,
+                         size_t workspace_bytes, ld_stream_t stream);
 /* db[c] = sum_{n,p} dy (conv bias gradient, fpn.py / gfl_cls / gfl_reg). */
 int ld_bias_grad(const float* dy, int N, int C, int P, float* db, int accumulate,
                  ld_stream_t stream);

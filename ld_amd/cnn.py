@@ -387,10 +387,27 @@ class DeformConv2dPack(nn.Module):
         return y3.view(n, self.out_channels, lv[0][0], lv[0][1])
 
 
+def train_bn_refusals(conv, bn):
+    """What a conv followed by a training-mode BatchNorm2d refuses, asked
+    before the conv launches.  After a DeformConv2dPack it is refused by name:
+    the trainable DCN runs conv + BN as one node with the folded eval
+    coefficients (``forward3_bn``), which batch statistics cannot take."""
+    if not (isinstance(bn, BatchNorm2d) and bn.training):
+        return
+    if isinstance(conv, DeformConv2dPack):
+        raise NotImplementedError(
+            'BatchNorm2d in training mode (batch statistics) after a '
+            'DeformConv2dPack is not implemented: keep the norm layers of DCN '
+            'blocks in eval mode (norm_eval=True)')
+    Y.bn_train_check(bn.momentum)
+
+
 class BatchNorm2d(nn.Module):
-    """BatchNorm2d evaluated with its running statistics (the LD configs run
-    every BN with norm_eval=True, resnet.py:639-648); affine stays trainable.
-    Training-mode batch statistics are not on this path and raise."""
+    """BatchNorm2d.  Eval mode: its running statistics (the LD configs run
+    every BN with norm_eval=True, resnet.py:639-648), affine trainable.
+    Training mode (norm_eval=False): the batch's own statistics, and the
+    running statistics / num_batches_tracked updated on the device as
+    torch.nn.BatchNorm2d does (layers.bn_train_act; fp32 mode only)."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1):
         super().__init__()
@@ -404,11 +421,20 @@ class BatchNorm2d(nn.Module):
 
     def forward3(self, x3, residual=None, relu=False):
         if self.training:
-            raise NotImplementedError(
-                'BatchNorm2d in training mode (batch statistics) is outside '
-                'the LD hot path: use norm_eval=True')
+            # a replayed step rewrites the buffers without passing here: the
+            # mode switch after it (``train``) drops the eval coefficients
+            self._ld_trained = True
+            return Y.bn_train_act(x3, self.weight, self.bias,
+                                  self.running_mean, self.running_var,
+                                  self.num_batches_tracked, self.eps,
+                                  self.momentum, residual, relu)
         return Y.bn_act(x3, self.weight, self.bias, self.running_mean,
                         self.running_var, self.eps, residual, relu)
+
+    def train(self, mode=True):
+        if getattr(self, '_ld_trained', False):
+            Y.bn_stats_changed(self.weight)
+        return super().train(mode)
 
     def forward(self, x):
         n, c, h, w = x.shape
@@ -555,6 +581,8 @@ class ConvModule(nn.Module):
             return Y.conv_gn_act(x3, c.weight, n.weight, n.bias, n.num_groups,
                                  n.eps, c.stride[0], c.padding[0], levels,
                                  relu=act, c8_only=c8_out)
+        if norm and self.with_norm:
+            train_bn_refusals(self.conv, self.norm)
         y3, lv = self.conv.forward3(x3, levels)
         if norm and self.with_norm:
             n = self.norm

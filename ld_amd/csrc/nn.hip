@@ -224,6 +224,216 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
   if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)s2 : (float)s2;
 }
 
+// ------------------------------------------------- BN (batch statistics) ----
+// Training-mode BatchNorm2d on (N, C, P), M = N * P values per channel.  Every
+// reduction is two-stage and fixed-order: grid (C, nsplit), slice `split` owns a
+// contiguous range of the channel's flat (n, p) index and writes one fp64 pair;
+// one final launch adds a channel's pairs (16 lanes, slots j, j + 16, ..., then a
+// fixed butterfly).  No atomics: two runs give the same bits.
+//
+// The slice of `split`, walked image by image; f(idx) handles the 4 (VEC: P % 4
+// == 0, 16-byte aligned tensors, slices cut on multiples of 4) or 1 cells at idx.
+// Every idx lies in [0, N * C * P): n <= (end - 1) / P < N and p (+ 3) < p1 <= P.
+template <bool VEC, class F>
+__device__ __forceinline__ void bn_train_walk(int N, int C, int P, int c, int split,
+                                              int nsplit, F f) {
+  const long long total = (long long)N * P;
+  long long per = (total + nsplit - 1) / nsplit;
+  if (VEC) per = (per + 3) / 4 * 4;
+  const long long beg = (long long)split * per, end = min(total, beg + per);
+  if (beg >= end) return;
+  constexpr int W = VEC ? 4 : 1;
+  for (int n = (int)(beg / P); n <= (int)((end - 1) / P); ++n) {
+    const int p0 = (int)max(beg - (long long)n * P, 0LL);
+    const int p1 = (int)min(end - (long long)n * P, (long long)P);
+    const size_t base = ((size_t)n * C + c) * P;
+    for (int p = p0 + W * (int)threadIdx.x; p < p1; p += W * 256) f(base + p);
+  }
+}
+
+// partial[c][split] = (sum x, sum x^2) in fp64 (the square of an fp32 value is
+// exact in fp64)
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_train_stats_partial_kernel(
+    const float* __restrict__ x, int N, int C, int P, double* __restrict__ partial) {
+  const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
+  double s = 0.0, q = 0.0;
+  bn_train_walk<VEC>(N, C, P, c, split, nsplit, [&](size_t idx) {
+    if (VEC) {
+      const float4 t = *reinterpret_cast<const float4*>(x + idx);
+      const double v0 = t.x, v1 = t.y, v2 = t.z, v3 = t.w;
+      s += (v0 + v1) + (v2 + v3);
+      q += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
+    } else {
+      const double v = (double)x[idx];
+      s += v;
+      q += v * v;
+    }
+  });
+  block_sum2(s, q);
+  if (threadIdx.x == 0) {
+    partial[((size_t)c * nsplit + split) * 2 + 0] = s;
+    partial[((size_t)c * nsplit + split) * 2 + 1] = q;
+  }
+}
+
+// a channel's pairs summed by its 16 lanes; every lane of the 16 gets the sums
+__device__ __forceinline__ void bn_train_fold(const double* __restrict__ partial, int c,
+                                              int C, int nsplit, double& a, double& b) {
+  const int j = threadIdx.x & 15;
+  a = 0.0;
+  b = 0.0;
+  if (c < C) {
+    const double2* row = reinterpret_cast<const double2*>(partial) + (size_t)c * nsplit;
+    for (int k = j; k < nsplit; k += 16) {
+      const double2 v = row[k];
+      a += v.x;
+      b += v.y;
+    }
+  }
+#pragma unroll
+  for (int m = 8; m >= 1; m >>= 1) {
+    a += __shfl_xor(a, m, 16);
+    b += __shfl_xor(b, m, 16);
+  }
+}
+
+// mean, rstd (biased variance q/M - mean^2, formed in fp64), the folded affine, and
+// the running statistics as torch.nn.BatchNorm2d updates them (unbiased variance),
+// all in one launch; block 0 / thread 0 counts the batch.
+__global__ __launch_bounds__(256) void bn_train_stats_final_kernel(
+    const double* __restrict__ partial, int C, int nsplit, double M, float eps,
+    double momentum, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ scale,
+    float* __restrict__ shift, int update, float* __restrict__ running_mean,
+    float* __restrict__ running_var, long long* __restrict__ num_batches_tracked) {
+  const int c = blockIdx.x * 16 + (threadIdx.x >> 4);
+  double s, q;
+  bn_train_fold(partial, c, C, nsplit, s, q);
+  if (update && num_batches_tracked && blockIdx.x == 0 && threadIdx.x == 0)
+    num_batches_tracked[0] += 1;
+  if (c >= C || (threadIdx.x & 15) != 0) return;
+  const double m = s / M;
+  double var = q / M - m * m;
+  if (var < 0.0) var = 0.0;
+  const float mu = (float)m;
+  const float r = (float)(1.0 / sqrt(var + (double)eps));
+  const float sc = gamma[c] * r;
+  mean[c] = mu;
+  rstd[c] = r;
+  scale[c] = sc;
+  shift[c] = beta[c] - mu * sc;
+  if (update) {
+    if (running_mean)
+      running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
+    if (running_var)
+      running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] +
+                               momentum * (var * (M / (M - 1.0))));
+  }
+}
+
+// partial[c][split] = (sum dz, sum dz * xhat), dz = relu ? dy * (y > 0) : dy, xhat =
+// (x - mean) * rstd: the terms as bn_act_bwd_kernel forms them, summed in fp64
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_train_bwd_reduce_kernel(
+    const float* __restrict__ dy, const float* __restrict__ y,
+    const float* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ rstd, int N, int C, int P, int relu,
+    double* __restrict__ partial) {
+  const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
+  const float mu = mean[c], rs = rstd[c];
+  double s1 = 0.0, s2 = 0.0;
+  bn_train_walk<VEC>(N, C, P, c, split, nsplit, [&](size_t idx) {
+    if (VEC) {
+      const float4 g = *reinterpret_cast<const float4*>(dy + idx);
+      const float4 xv = *reinterpret_cast<const float4*>(x + idx);
+      float dz[4] = {g.x, g.y, g.z, g.w};
+      if (relu) {
+        const float4 yv = *reinterpret_cast<const float4*>(y + idx);
+        if (!(yv.x > 0.f)) dz[0] = 0.f;
+        if (!(yv.y > 0.f)) dz[1] = 0.f;
+        if (!(yv.z > 0.f)) dz[2] = 0.f;
+        if (!(yv.w > 0.f)) dz[3] = 0.f;
+      }
+      const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        s1 += (double)dz[k];
+        s2 += (double)(dz[k] * ((xs[k] - mu) * rs));
+      }
+    } else {
+      float dz = dy[idx];
+      if (relu && !(y[idx] > 0.f)) dz = 0.f;
+      s1 += (double)dz;
+      s2 += (double)(dz * ((x[idx] - mu) * rs));
+    }
+  });
+  block_sum2(s1, s2);
+  if (threadIdx.x == 0) {
+    partial[((size_t)c * nsplit + split) * 2 + 0] = s1;
+    partial[((size_t)c * nsplit + split) * 2 + 1] = s2;
+  }
+}
+
+// sums[c] = (sum dz, sum dz * xhat) for the apply launch; dgamma / dbeta (either may
+// be NULL: a frozen affine still needs the sums for dx)
+__global__ __launch_bounds__(256) void bn_train_bwd_final_kernel(
+    const double* __restrict__ partial, int C, int nsplit, double* __restrict__ sums,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
+  const int c = blockIdx.x * 16 + (threadIdx.x >> 4);
+  double s1, s2;
+  bn_train_fold(partial, c, C, nsplit, s1, s2);
+  if (c >= C || (threadIdx.x & 15) != 0) return;
+  sums[2 * (size_t)c + 0] = s1;
+  sums[2 * (size_t)c + 1] = s2;
+  if (dbeta) dbeta[c] = accumulate ? dbeta[c] + (float)s1 : (float)s1;
+  if (dgamma) dgamma[c] = accumulate ? dgamma[c] + (float)s2 : (float)s2;
+}
+
+// dx = scale * (dz - sum dz / M - xhat * sum(dz xhat) / M) (NULL: skipped); dres = dz
+// (NULL: skipped)
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_train_bwd_apply_kernel(
+    const float* __restrict__ dy, const float* __restrict__ y,
+    const float* __restrict__ x, const float* __restrict__ scale,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const double* __restrict__ sums, double M, int N, int C, int P, int relu,
+    float* __restrict__ dx, float* __restrict__ dres) {
+  const int c = blockIdx.x, split = blockIdx.y, nsplit = gridDim.y;
+  const float s = scale[c], mu = mean[c], rs = rstd[c];
+  const float k1 = dx ? (float)(sums[2 * (size_t)c + 0] / M) : 0.f;
+  const float k2 = dx ? (float)(sums[2 * (size_t)c + 1] / M) : 0.f;
+  bn_train_walk<VEC>(N, C, P, c, split, nsplit, [&](size_t idx) {
+    if (VEC) {
+      const float4 g = *reinterpret_cast<const float4*>(dy + idx);
+      float dz[4] = {g.x, g.y, g.z, g.w};
+      if (relu) {
+        const float4 yv = *reinterpret_cast<const float4*>(y + idx);
+        if (!(yv.x > 0.f)) dz[0] = 0.f;
+        if (!(yv.y > 0.f)) dz[1] = 0.f;
+        if (!(yv.z > 0.f)) dz[2] = 0.f;
+        if (!(yv.w > 0.f)) dz[3] = 0.f;
+      }
+      if (dx) {
+        const float4 xv = *reinterpret_cast<const float4*>(x + idx);
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          o[k] = s * ((dz[k] - k1) - ((xs[k] - mu) * rs) * k2);
+        *reinterpret_cast<float4*>(dx + idx) = make_float4(o[0], o[1], o[2], o[3]);
+      }
+      if (dres)
+        *reinterpret_cast<float4*>(dres + idx) = make_float4(dz[0], dz[1], dz[2], dz[3]);
+    } else {
+      float dz = dy[idx];
+      if (relu && !(y[idx] > 0.f)) dz = 0.f;
+      if (dx) dx[idx] = s * ((dz - k1) - ((x[idx] - mu) * rs) * k2);
+      if (dres) dres[idx] = dz;
+    }
+  });
+}
+
 // per-channel sum of dy over (N, P): conv bias gradient
 __global__ __launch_bounds__(256) void bias_grad_kernel(
     const float* __restrict__ dy, int N, int C, int P, float* __restrict__ db,
@@ -1700,6 +1910,92 @@ extern "C" int ld_bn_bwd_finalize_batch(const ld_bn_fin_job_t* jobs,
   if (!jobs || !block_job || nblocks < 1) return LD_EINVAL;
   LD_LAUNCH(bn_bwd_finalize_batch_kernel, dim3(nblocks), dim3(256), 0, LD_STREAM,
                      jobs, block_job);
+  return (int)hipGetLastError();
+}
+
+// ---- BatchNorm2d with batch statistics --------------------------------------
+// workspace: [C][kBnSplitMax] fp64 pairs (slice partials) + [C] fp64 pairs (the
+// finished backward sums the apply launch reads)
+static bool bn_train_geometry_ok(int N, int C, int P) {
+  return N >= 1 && C >= 1 && P >= 1 && P <= (1 << 30) && (long long)N * P >= 2;
+}
+
+extern "C" size_t ld_bn_train_workspace_bytes(int N, int C, int P) {
+  if (!bn_train_geometry_ok(N, C, P)) return 0;
+  return (size_t)C * (kBnSplitMax + 1) * 2 * sizeof(double);
+}
+
+extern "C" int ld_bn_train_forward(const float* x, const float* residual,
+                                   const float* gamma, const float* beta, float eps,
+                                   double momentum, int N, int C, int P, int relu,
+                                   int update_running, float* running_mean,
+                                   float* running_var, int64_t* num_batches_tracked,
+                                   float* y, float* mean, float* rstd, float* scale,
+                                   float* shift, void* workspace,
+                                   size_t workspace_bytes, ld_stream_t stream) {
+  if (!x || !gamma || !beta || !y || !mean || !rstd || !scale || !shift ||
+      !bn_train_geometry_ok(N, C, P))
+    return LD_EINVAL;
+  if (!workspace || (uintptr_t)workspace % 16 != 0 ||
+      workspace_bytes < ld_bn_train_workspace_bytes(N, C, P))
+    return LD_EINVAL;
+  const int ns = bn_splits(N, C, P);
+  double* const partial = (double*)workspace;
+  if (P % 4 == 0 && (uintptr_t)x % 16 == 0)
+    LD_LAUNCH((bn_train_stats_partial_kernel<true>), dim3(C, ns), dim3(256), 0,
+              LD_STREAM, x, N, C, P, partial);
+  else
+    LD_LAUNCH((bn_train_stats_partial_kernel<false>), dim3(C, ns), dim3(256), 0,
+              LD_STREAM, x, N, C, P, partial);
+  LD_LAUNCH(bn_train_stats_final_kernel, dim3((C + 15) / 16), dim3(256), 0, LD_STREAM,
+            (const double*)partial, C, ns, (double)N * (double)P, eps, momentum, gamma,
+            beta, mean, rstd, scale, shift, update_running, running_mean, running_var,
+            (long long*)num_batches_tracked);
+  if (int e = (int)hipGetLastError()) return e;
+  // the apply is the eval-mode launch with the batch coefficients
+  return ld_bn_act_forward(x, residual, scale, shift, N, C, P, relu, y, stream);
+}
+
+extern "C" int ld_bn_train_backward(const float* dy, const float* y, const float* x,
+                                    const float* scale, const float* mean,
+                                    const float* rstd, int N, int C, int P, int relu,
+                                    float* dx, float* dres, float* dgamma,
+                                    float* dbeta, int accumulate, void* workspace,
+                                    size_t workspace_bytes, ld_stream_t stream) {
+  if (!dy || !x || !scale || !mean || !rstd || !bn_train_geometry_ok(N, C, P))
+    return LD_EINVAL;
+  if (relu && !y) return LD_EINVAL;
+  if (accumulate != 0 && accumulate != 1) return LD_EINVAL;  // never deferred
+  if (!workspace || (uintptr_t)workspace % 16 != 0 ||
+      workspace_bytes < ld_bn_train_workspace_bytes(N, C, P))
+    return LD_EINVAL;
+  const int ns = bn_splits(N, C, P);
+  double* const partial = (double*)workspace;
+  double* const sums = partial + (size_t)C * kBnSplitMax * 2;
+  const double M = (double)N * (double)P;
+  const bool vec = P % 4 == 0 &&
+                   ((uintptr_t)dy | (uintptr_t)(y ? y : dy) | (uintptr_t)x |
+                    (uintptr_t)(dx ? dx : dy) | (uintptr_t)(dres ? dres : dy)) % 16 == 0;
+  if (dx || dgamma || dbeta) {
+    if (vec)
+      LD_LAUNCH((bn_train_bwd_reduce_kernel<true>), dim3(C, ns), dim3(256), 0,
+                LD_STREAM, dy, y, x, mean, rstd, N, C, P, relu, partial);
+    else
+      LD_LAUNCH((bn_train_bwd_reduce_kernel<false>), dim3(C, ns), dim3(256), 0,
+                LD_STREAM, dy, y, x, mean, rstd, N, C, P, relu, partial);
+    LD_LAUNCH(bn_train_bwd_final_kernel, dim3((C + 15) / 16), dim3(256), 0, LD_STREAM,
+              (const double*)partial, C, ns, sums, dgamma, dbeta, accumulate);
+  }
+  if (dx || dres) {
+    if (vec)
+      LD_LAUNCH((bn_train_bwd_apply_kernel<true>), dim3(C, ns), dim3(256), 0,
+                LD_STREAM, dy, y, x, scale, mean, rstd, (const double*)sums, M, N, C, P,
+                relu, dx, dres);
+    else
+      LD_LAUNCH((bn_train_bwd_apply_kernel<false>), dim3(C, ns), dim3(256), 0,
+                LD_STREAM, dy, y, x, scale, mean, rstd, (const double*)sums, M, N, C, P,
+                relu, dx, dres);
+  }
   return (int)hipGetLastError();
 }
 

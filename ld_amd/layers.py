@@ -1633,7 +1633,11 @@ def bn_prepare(gamma, beta, mean, var, eps):
     hit = getattr(gamma, '_ld_bn', None)
     if hit is not None and hit[0] == stamp:
         return hit[1]
-    out = _bn_prepare(gamma, beta, mean, var, eps)
+    # stale (bn_stats_changed): recompute into the same buffers, a refresh
+    # table may hold their addresses
+    out = _bn_prepare(gamma, beta, mean, var, eps,
+                      hit[1] if hit is not None and hit[0] == _BN_STALE
+                      else None)
     gamma._ld_bn = (stamp, out)
     if not frozen:
         gamma._ld_bn_src = (beta, mean, var, eps)
@@ -1641,10 +1645,14 @@ def bn_prepare(gamma, beta, mean, var, eps):
     return out
 
 
-def _bn_prepare(gamma, beta, mean, var, eps):
+_BN_STALE = ('stale', )
+
+
+def _bn_prepare(gamma, beta, mean, var, eps, into=None):
     lib = L.get_lib()
     c = gamma.numel()
-    buf = torch.empty((3, c), dtype=torch.float32, device=gamma.device)
+    buf = into if into is not None else \
+        torch.empty((3, c), dtype=torch.float32, device=gamma.device)
     L.check(lib.ld_bn_prepare(L.ptr(gamma), L.ptr(beta), L.ptr(mean),
                               L.ptr(var), eps, c, L.ptr(buf[0]), L.ptr(buf[1]),
                               L.ptr(buf[2]), L.stream_ptr(gamma.device)),
@@ -1908,6 +1916,144 @@ def bn_act(x3, gamma, beta, mean, var, eps, residual=None, relu=True):
                                      residual.requires_grad)):
         return BnActFn.apply(x3, gamma, beta, mean, var, eps, residual, relu)
     return _bn_act_forward(x3, gamma, beta, mean, var, eps, residual, relu)[0]
+
+
+# ---------------------------------------------------------------------------
+# BatchNorm (batch statistics) + residual + ReLU
+# ---------------------------------------------------------------------------
+def bn_stats_changed(gamma):
+    """The running statistics beside ``gamma`` were rewritten by a raw launch
+    (no ``_version`` moves, and a frozen affine's stamp has no parameter
+    generation): ``bn_prepare``'s cached eval coefficients no longer hold.
+    The buffers stay alive -- a refresh table may point at them."""
+    hit = getattr(gamma, '_ld_bn', None)
+    if hit is not None:
+        gamma._ld_bn = (_BN_STALE, hit[1])
+
+
+def _bn_train_forward(x3, gamma, beta, running_mean, running_var,
+                      num_batches_tracked, eps, momentum, residual, relu,
+                      update):
+    """y = relu?(BN_batch(x3) + residual): (y, scale, mean, rstd); updates the
+    running statistics in the same launches when ``update``."""
+    lib = L.get_lib()
+    N, c, P = x3.shape
+    dev = x3.device
+    y = torch.empty_like(x3)
+    coef = torch.empty((4, c), dtype=torch.float32, device=dev)
+    need = lib.ld_bn_train_workspace_bytes(N, c, P)
+    ws = workspace(dev, need, 'bn')
+    L.check(lib.ld_bn_train_forward(
+        L.ptr(x3), L.ptr(residual), L.ptr(gamma), L.ptr(beta), eps,
+        float(momentum), N, c, P, 1 if relu else 0, 1 if update else 0,
+        L.ptr(running_mean), L.ptr(running_var), L.ptr(num_batches_tracked),
+        L.ptr(y), L.ptr(coef[0]), L.ptr(coef[1]), L.ptr(coef[2]),
+        L.ptr(coef[3]), L.ptr(ws), ws.numel(), L.stream_ptr(dev)),
+        'ld_bn_train_forward')
+    if update:
+        bn_stats_changed(gamma)
+    return y, coef[2], coef[0], coef[1]
+
+
+class BnTrainActFn(torch.autograd.Function):
+    """y = relu?(BN(x) + residual) with the batch's own statistics.  Backward
+    = a fixed-order fp64 reduce (sum dz, sum dz xhat) + an apply launch; the
+    parameter gradients are never deferred: dx needs the finished sums."""
+
+    @staticmethod
+    def forward(ctx, x3, gamma, beta, running_mean, running_var,
+                num_batches_tracked, eps, momentum, residual, relu, update):
+        # (bn_train_act validated the operands)
+        y, scale, mean, rstd = _bn_train_forward(
+            x3, gamma, beta, running_mean, running_var, num_batches_tracked,
+            eps, momentum, residual, relu, update)
+        ctx.save_for_backward(x3, y, scale, mean, rstd)
+        ctx.relu = relu
+        ctx.has_res = residual is not None
+        ctx.params = (gamma, beta)
+        ctx.fan_res = fan_in(ctx, 8, residual)
+        _note_use(gamma, beta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x3, y, scale, mean, rstd = ctx.saved_tensors
+        ng = ctx.needs_input_grad
+        dx, dres, dgamma, dbeta = _bn_train_backward(
+            dy, x3, y, scale, mean, rstd, ctx.relu, ctx.params, ng[0], ng[1],
+            ng[2], ctx.has_res and ng[8])
+        return (dx, dgamma, dbeta, None, None, None, None, None,
+                fan_give(ctx.fan_res, dres), None, None)
+
+
+def _bn_train_backward(dy, x3, y, scale, mean, rstd, relu, params, need_x,
+                       need_g, need_b, need_res):
+    """(dx, dres, dgamma, dbeta) of BnTrainActFn; the parameter gradients are
+    None when they went straight into the gradient arena.  The sums are formed
+    even for a frozen affine: dx needs them."""
+    lib = L.get_lib()
+    dy = dy.contiguous()
+    dev = dy.device
+    N, c, P = x3.shape
+    dx = torch.empty_like(x3) if need_x else None
+    dres = torch.empty_like(x3) if need_res else None
+    (dgamma, dbeta), direct = _grad_outs(
+        params, (need_g, need_b),
+        lambda p: torch.empty(c, dtype=torch.float32, device=dev))
+    ws = workspace(dev, lib.ld_bn_train_workspace_bytes(N, c, P), 'bn')
+    L.check(lib.ld_bn_train_backward(
+        L.ptr(dy), L.ptr(y), L.ptr(x3), L.ptr(scale), L.ptr(mean), L.ptr(rstd),
+        N, c, P, 1 if relu else 0, L.ptr(dx), L.ptr(dres), L.ptr(dgamma),
+        L.ptr(dbeta), 1 if direct else 0, L.ptr(ws), ws.numel(),
+        L.stream_ptr(dev)), 'ld_bn_train_backward')
+    dgamma, dbeta = _grad_done(params, (dgamma, dbeta), direct)
+    return dx, dres, dgamma, dbeta
+
+
+def bn_train_check(momentum):
+    """What a training-mode BatchNorm2d refuses whatever its input is; callers
+    that launch a conv first ask before that launch."""
+    if momentum is None:
+        raise NotImplementedError(
+            'BatchNorm2d in training mode with momentum=None (cumulative '
+            'moving average) is not implemented: give a momentum')
+    if get_precision() == 'bf16':
+        raise NotImplementedError(
+            'BatchNorm2d in training mode (batch statistics) under bf16 '
+            'precision mode is not implemented: the C8 image forms have no '
+            'batch-statistics backward; train it with set_precision("fp32") '
+            'or norm_eval=True')
+
+
+def bn_train_act(x3, gamma, beta, running_mean, running_var,
+                 num_batches_tracked, eps, momentum, residual=None, relu=True,
+                 update_stats=True):
+    """Differentiable training-mode BatchNorm2d (+ residual) (+ ReLU) on an
+    (N, C, P) tensor: normalises with the batch's biased variance and updates
+    ``running_mean`` / ``running_var`` (unbiased) / ``num_batches_tracked`` on
+    the device as torch.nn.BatchNorm2d does.  ``update_stats=False`` leaves the
+    three buffers alone (the second forward of a gradient check)."""
+    bn_train_check(momentum)
+    if not isinstance(x3, C8Act) and x3.dim() == 3 and \
+            x3.shape[0] * x3.shape[2] == 1:
+        raise ValueError(
+            'Expected more than 1 value per channel when training, got input '
+            f'size {tuple(x3.shape)}')
+    _dev_f32(x3, 'bn input')
+    if x3.dim() != 3 or x3.shape[1] != gamma.numel():
+        raise L.LdError(f'bn input {tuple(x3.shape)} for {gamma.numel()} '
+                        'channels: expected (N, C, P)')
+    if residual is not None:
+        _dev_f32(residual, 'bn residual')
+    args = (x3, gamma, beta, running_mean, running_var, num_batches_tracked,
+            float(eps), float(momentum), residual, bool(relu),
+            bool(update_stats))
+    if torch.is_grad_enabled() and (x3.requires_grad or gamma.requires_grad or
+                                    beta.requires_grad or
+                                    (residual is not None and
+                                     residual.requires_grad)):
+        return BnTrainActFn.apply(*args)
+    return _bn_train_forward(*args)[0]
 
 
 _RELU_CONSTS = {}

@@ -260,7 +260,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -499,6 +499,13 @@ SIGNATURES = {
     'ld_bn_act_backward_c8in': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                           _i32, _i32, _i32, _vp, _vp, _vp, _vp,
                                           _vp, _i32, _vp, _sz, _vp]),
+    'ld_bn_train_workspace_bytes': (_sz, [_i32, _i32, _i32]),
+    'ld_bn_train_forward': (C.c_int, [_vp, _vp, _vp, _vp, _f32, C.c_double, _i32,
+                                      _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ld_bn_train_backward': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
+                                       _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp,
+                                       _sz, _vp]),
     'ld_bias_grad': (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp]),
     'ld_gn_forward_workspace_bytes': (_sz, [_LV, _i32, _i32]),
     'ld_gn_forward': (C.c_int, [_LV, _vp, _vp, _vp, _i32, _i32, _i32, _f32,

@@ -9,7 +9,10 @@ Execution plan per block:
   * trainable: ONE forward launch as well (layers.ConvBnActFn: the conv
     epilogue applies the folded eval-BN, the residual and the ReLU and also
     stores the raw conv result the gamma/beta gradients need); backward = the
-    BN-affine/ReLU backward kernel + MFMA dgrad / wgrad.
+    BN-affine/ReLU backward kernel + MFMA dgrad / wgrad;
+  * a norm layer in training mode (norm_eval=False, unfrozen stages): the
+    conv's own node, then layers.bn_train_act (batch statistics need the whole
+    conv output first, so nothing is fused).
 """
 import math
 
@@ -19,7 +22,8 @@ import torch.nn as nn
 from . import layers as Y
 from . import lib as L
 from .cnn import (BatchNorm2d, Conv2d, GroupedConv2d, ReLU, build_conv_layer,
-                  build_norm_layer, constant_init, kaiming_init)
+                  build_norm_layer, constant_init, kaiming_init,
+                  train_bn_refusals)
 from .registry import BACKBONES
 
 
@@ -30,8 +34,11 @@ def _conv_bn(x3, levels, conv, bn, residual=None, relu=True):
         x3.requires_grad or w.requires_grad or bn.weight.requires_grad or
         (residual is not None and residual.requires_grad))
     if bn.training:
-        raise NotImplementedError('BatchNorm in training mode (use '
-                                  'norm_eval=True; resnet.py:639-648)')
+        # batch statistics need the whole conv output first: no fused epilogue;
+        # the conv's own autograd node, then the training BN node
+        train_bn_refusals(conv, bn)
+        y3, lv = conv.forward3(x3, levels)
+        return bn.forward3(y3, residual, relu), lv
     if hasattr(conv, 'forward3_bn') and (need_grad or conv.needs_grad(x3)):
         # trainable DCN: offset conv, sampling and conv + BN as autograd nodes
         return conv.forward3_bn(x3, levels, bn, residual, relu)

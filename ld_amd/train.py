@@ -337,6 +337,7 @@ class SGDTrainer:
         self.virtual_ranks = W
         self._vranks = None
         self.model = model
+        self._refuse_training_bn()
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
         self.base_lr = lr  # initial lr of an unscaled group (mmcv's initial_lr)
         frozen = [p for p in model.parameters() if not p.requires_grad]
@@ -365,6 +366,24 @@ class SGDTrainer:
             # micro-batches hold theirs until their loss block's main part, on
             # top of the two steps of look-ahead the rotation already allows
             model.TEACHER_SLOTS = max(model.TEACHER_SLOTS, W + 2)
+
+    def _refuse_training_bn(self):
+        """Virtual ranks with a training-mode BatchNorm2d: each micro-batch
+        would normalise with its own statistics and the W forwards would update
+        the running statistics W times, which is not what rank 0 of the
+        W-process job saves."""
+        if self.virtual_ranks <= 1:
+            return
+        from .cnn import BatchNorm2d
+        names = [n for n, m in self.model.named_modules()
+                 if isinstance(m, BatchNorm2d) and m.training]
+        if names:
+            raise NotImplementedError(
+                f'virtual_ranks={self.virtual_ranks} with BatchNorm2d in '
+                f'training mode ({len(names)} layers, first {names[0]!r}): '
+                'batch statistics per micro-batch and W running-statistic '
+                'updates per step are not the W-process job; use '
+                'norm_eval=True or virtual_ranks=1')
 
     def _grad_scale(self):
         """The optimizer's gradient scale: the arena holds the SUM over the
@@ -678,6 +697,7 @@ class SGDTrainer:
         if torch.cuda.is_current_stream_capturing():
             raise NotImplementedError(
                 f'virtual_ranks={W} inside a hipGraph capture')
+        self._refuse_training_bn()
         model = self.model
         prefetch = getattr(model, 'prefetch_teacher', None)
         self._apply_schedule()
