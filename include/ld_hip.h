@@ -589,6 +589,36 @@ int ld_wgrad_reduce_batch(const ld_wgrad_job_t* jobs, const int32_t* block_job,
  * reduction, in-launch combination.  Order of precedence: LD_CONV_WGRAD_CFG, the
  * shape table (MODE 2), a model that is a pure function of the geometry. */
 int ld_conv_wgrad_plan(const ld_conv_t* c, int* out);
+/* ---- weight gradient of a small-Cin conv (the trainable stem) -----------------
+ * The backward counterpart of ld_conv_forward_smallc: (ci, kh, kw) is ONE flat
+ * GEMM dimension r < R = Cin*KH*KW (padded to 32 inside the kernel), dW[co][r] =
+ * sum_j dY[co][j] * Xcol[r][j] on v_mfma_f32_32x32x2f32 with the input patch
+ * staged through LDS (conv_wgrad_smallc.hip).  fp32 operands in either precision
+ * mode.  Served geometries (ld_conv_wgrad_smallc_supported == 1): Cin < 16, R <=
+ * 160, Cout 32 or 64, stride 1 or 2, one level; everything else LD_EUNSUPPORTED
+ * (the caller keeps ld_conv_wgrad).  The reduction over j = (n, ho, wo) is cut
+ * into ld_conv_wgrad_smallc_slabs(c) slabs (a function of the geometry alone);
+ * each writes one partial laid out like dW into the workspace (>=
+ * ld_conv_wgrad_smallc_workspace_bytes(c) = slabs * Cout * R * 4, else
+ * LD_ENOSPACE before any launch), and the slabs are summed in slab order: no
+ * atomics, two runs are bit-identical.
+ *   ld_conv_wgrad_smallc          dw (Cout,Cin,KH,KW) overwritten, or += if
+ *                                 accumulate != 0 (two launches: slabs, sum)
+ *   ld_conv_wgrad_smallc_partial  the slabs only; fills job->slabs / splits /
+ *                                 ntaps / Cout / Cin for ld_wgrad_reduce_batch as
+ *                                 ld_conv_wgrad_partial does (the job describes the
+ *                                 flat dW: ntaps = 1, Cout = 1, Cin = Cout * R);
+ *                                 both forms give the same bits
+ * There is no data gradient for these convs (the image needs none). */
+int ld_conv_wgrad_smallc_supported(const ld_conv_t* c);
+int ld_conv_wgrad_smallc_slabs(const ld_conv_t* c); /* < 0: LD_E* */
+size_t ld_conv_wgrad_smallc_workspace_bytes(const ld_conv_t* c);
+int ld_conv_wgrad_smallc(const ld_conv_t* c, const float* x, const float* dy, float* dw,
+                         int accumulate, void* workspace, size_t workspace_bytes,
+                         ld_stream_t stream);
+int ld_conv_wgrad_smallc_partial(const ld_conv_t* c, const float* x, const float* dy,
+                                 void* slabs, size_t slab_bytes, ld_wgrad_job_t* job,
+                                 ld_stream_t stream);
 /* Times the fp32 weight-gradient kernels / split shapes of this geometry on the
  * caller's buffers (dw is overwritten) and records the winner in the shape
  * table (key MODE 2).  Same rules and return values as ld_conv_tune_forward;
@@ -918,10 +948,21 @@ int ld_gn_backward_c8_lean(const ld_levels_t* lv, const float* dy, const float* 
                            const float* rstd, int N, int C, int G, int relu, float* dx,
                            void* dx_c8, float* dgamma, float* dbeta, int accumulate,
                            void* workspace, size_t workspace_bytes, ld_stream_t stream);
-/* MaxPool2d(kernel 3, stride 2, pad 1) on rows = N*C planes (resnet.py:570);
- * forward only (the stem is frozen, frozen_stages=1). */
+/* MaxPool2d(kernel 3, stride 2, pad 1) on rows = N*C planes (resnet.py:570). */
 int ld_maxpool3x3s2(const float* x, int rows, int H, int W, float* y,
                     ld_stream_t stream);
+/* Its gradient (the trainable stem, frozen_stages = -1): x (rows, H, W) the
+ * forward input, dy (rows, Ho, Wo), dx (rows, H, W) with EVERY element written
+ * (no memset).  A gather: each input pixel visits the at most 4 windows that
+ * cover it and takes dy of those whose maximum it is; the maximum of a window
+ * is its first in-bounds element in row-major (kh, kw) order that attains it
+ * (torch's rule; ties are the normal case behind a ReLU), the padding is -inf,
+ * the addends of a pixel are added in ascending (oh, ow) order in fp32: equal
+ * to torch's CPU backward bit for bit.  No atomics; enqueue only, capturable.
+ * 16-byte loads / stores iff W % 4 == 0 and x, dx are 16-byte aligned.  NaN
+ * inputs are outside the contract, as for the forward. */
+int ld_maxpool_3x3s2_backward(const float* x, const float* dy, int rows, int H, int W,
+                             float* dx, ld_stream_t stream);
 /* ---- Res2Net block glue (backbones/res2net.py:108-162) ----------------------
  * Everything between the convs of a Bottle2neck, one launch each, on `stream`,
  * nothing allocated or synchronised.  u is relu(bn1(conv1(x))) of shape

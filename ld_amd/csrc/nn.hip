@@ -1444,6 +1444,152 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_vec_kernel(
   }
 }
 
+// ------------------------------------------------------ max pool, backward --
+// dx of MaxPool2d(3, 2, 1) as a GATHER: an input pixel (h, w) lies in the windows
+// oh in {h / 2} (h even) or {(h - 1) / 2, (h + 1) / 2} (h odd), likewise ow -- at
+// most 4 -- and takes dy[oh][ow] of every one whose maximum it is.  The maximum
+// of a window is its FIRST in-bounds element, in row-major (kh, kw) order, that
+// attains it (torch's rule: `val > max` updates, an equal value does not); the
+// padding is -inf.  The addends of one pixel are summed in ascending (oh, ow)
+// order from 0.0f, which is the order torch's CPU backward (a scatter in output
+// order into a zeroed map) adds them in: bit-identical.  Every dx element is
+// written, nothing needs a memset, no atomics.  NaN inputs: outside the contract.
+//
+// A window as a 3 x 3 register tile (out-of-bounds = -inf) -> the (kh, kw) code
+// kh * 3 + kw of its maximum.  `first` = the code of the first in-bounds element
+// (what an all -inf window selects).
+__device__ __forceinline__ int pool_argmax9(const float (&v)[3][3], int first) {
+  float m = -INFINITY;
+  int am = first;
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw)
+      if (v[kh][kw] > m) {  // never true for a padding element
+        m = v[kh][kw];
+        am = kh * 3 + kw;
+      }
+  return am;
+}
+
+__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, int rows, int H, int W,
+    int Ho, int Wo, float* __restrict__ dx) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)rows * H * W;
+  if (i >= total) return;
+  const int w = (int)(i % W);
+  const size_t q = i / W;
+  const int h = (int)(q % H);
+  const size_t r = q / H;
+  const float* xp = x + r * H * W;
+  const float* dyp = dy + r * Ho * Wo;
+  float s = 0.0f;
+  const int oh0 = h >> 1, ow0 = w >> 1;
+  const int noh = (h & 1) ? 2 : 1, now = (w & 1) ? 2 : 1;
+  for (int a = 0; a < noh; ++a) {
+    const int oh = oh0 + a;
+    if (oh >= Ho) continue;
+    for (int b = 0; b < now; ++b) {
+      const int ow = ow0 + b;
+      if (ow >= Wo) continue;
+      const int h0 = oh * 2 - 1, w0 = ow * 2 - 1;
+      float v[3][3];
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) {
+          const int hi = h0 + kh, wi = w0 + kw;
+          const bool ok = hi >= 0 && hi < H && wi >= 0 && wi < W;
+          v[kh][kw] = ok ? xp[(size_t)hi * W + wi] : -INFINITY;
+        }
+      const int am = pool_argmax9(v, (h0 < 0 ? 3 : 0) + (w0 < 0 ? 1 : 0));
+      if (am == (h - h0) * 3 + (w - w0)) s += dyp[(size_t)oh * Wo + ow];
+    }
+  }
+  dx[i] = s;
+}
+
+// Vector form (W % 4 == 0, 16-byte aligned x / dx rows): one thread = the 2 x 4
+// pixels of rows 2i, 2i + 1 and columns 4t .. 4t + 3.  Their windows are oh in {i,
+// i + 1} x ow in {2t, 2t + 1, 2t + 2}, over rows 2i - 1 .. 2i + 3 and columns 4t - 1
+// .. 4t + 5: per input row one aligned 16-byte load, one 8-byte load (columns 4t + 4,
+// 4t + 5) and one 4-byte load (column 4t - 1), five rows for two rows of dx (a thread
+// per single row would load three rows for an even and six for an odd one); each
+// window's maximum is located once; dx leaves as two 16-byte stores.  Row 2i takes
+// from the windows oh = i alone, row 2i + 1 from oh = i and then oh = i + 1, ow
+// ascending inside each: the scalar kernel's windows, order and additions.
+__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_vec_kernel(
+    const float* __restrict__ x, const float* __restrict__ dy, int rows, int H, int W,
+    int Ho, int Wo, float* __restrict__ dx) {
+  const int quads = W >> 2;
+  const int pairs = (H + 1) >> 1;  // = Ho
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)rows * pairs * quads;
+  if (i >= total) return;
+  const int t = (int)(i % quads);
+  const size_t q = i / quads;
+  const int ip = (int)(q % pairs);
+  const size_t r = q / pairs;
+  const float* xp = x + r * H * W;
+  const float* dyp = dy + r * Ho * Wo;
+  const bool has_left = t > 0, has_right = 4 * t + 4 < W;
+  const int hb = 2 * ip - 1;  // first row of the tile
+  float v[5][7];              // rows hb .. hb + 4, columns 4t - 1 .. 4t + 5
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const int hi = hb + k;
+    const bool ok = hi >= 0 && hi < H;
+    const float* row = xp + (size_t)hi * W + 4 * t;
+    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    float2 rt = make_float2(-INFINITY, -INFINITY);
+    float lf = -INFINITY;
+    if (ok) {
+      m = *reinterpret_cast<const float4*>(row);
+      if (has_right) rt = *reinterpret_cast<const float2*>(row + 4);
+      if (has_left) lf = row[-1];
+    }
+    v[k][0] = lf;
+    v[k][1] = m.x;
+    v[k][2] = m.y;
+    v[k][3] = m.z;
+    v[k][4] = m.w;
+    v[k][5] = rt.x;
+    v[k][6] = rt.y;
+  }
+  float s[2][4] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {  // oh = ip + a: tile rows 2a .. 2a + 2
+    const int oh = ip + a;
+    if (oh >= Ho) continue;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {  // ow = 2t + b: tile columns 2b .. 2b + 2
+      const int ow = 2 * t + b;
+      if (ow >= Wo) continue;
+      float win[3][3];
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw) win[kh][kw] = v[2 * a + kh][2 * b + kw];
+      const int am = pool_argmax9(win, (oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0));
+      const int akh = am / 3, akw = am - akh * 3;
+      const int own = 2 * a + akh - 1;  // tile row -> row of this thread (0, 1)
+      if (own != 0 && own != 1) continue;
+      const float g = dyp[(size_t)oh * Wo + ow];
+      const int px = 2 * b + akw - 1;  // tile column -> pixel of this thread
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (own == 0 && px == e) s[0][e] += g;
+        if (own == 1 && px == e) s[1][e] += g;
+      }
+    }
+  }
+  float* o = dx + (r * H + 2 * ip) * W + 4 * t;
+  *reinterpret_cast<float4*>(o) = make_float4(s[0][0], s[0][1], s[0][2], s[0][3]);
+  if (2 * ip + 1 < H)  // (its maxima are in bounds: a padding row is never selected)
+    *reinterpret_cast<float4*>(o + W) = make_float4(s[1][0], s[1][1], s[1][2], s[1][3]);
+}
+
 // ---------------------------------------------------- FPN top-down pathway --
 // out = fine + nearest_up(coarse), target size = the finer map's size
 // (fpn.py:182-191: laterals[i-1] += F.interpolate(laterals[i], size=prev)).
@@ -2233,6 +2379,23 @@ extern "C" int ld_maxpool3x3s2(const float* x, int rows, int H, int W, float* y,
   }
   LD_LAUNCH(maxpool3x3s2_kernel, dim3((unsigned)((total + 255) / 256)),
                      dim3(256), 0, LD_STREAM, x, rows, H, W, Ho, Wo, y);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_maxpool_3x3s2_backward(const float* x, const float* dy, int rows, int H,
+                                        int W, float* dx, ld_stream_t stream) {
+  if (!x || !dy || !dx || rows < 1 || H < 1 || W < 1) return LD_EINVAL;
+  const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+  const size_t total = (size_t)rows * H * W;
+  if (total / 256 >= 0x7fffffffu) return LD_EUNSUPPORTED;
+  if (W % 4 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dx % 16) == 0) {
+    const size_t threads = (size_t)rows * Ho * (W / 4);  // a row pair x 4 columns each
+    LD_LAUNCH(maxpool3x3s2_bwd_vec_kernel, dim3((unsigned)((threads + 255) / 256)),
+              dim3(256), 0, LD_STREAM, x, dy, rows, H, W, Ho, Wo, dx);
+    return (int)hipGetLastError();
+  }
+  LD_LAUNCH(maxpool3x3s2_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+            LD_STREAM, x, dy, rows, H, W, Ho, Wo, dx);
   return (int)hipGetLastError();
 }
 

@@ -1462,7 +1462,14 @@ def _conv_wgrad(lib, x3, w, dy, d, pw, c8w):
     st = L.stream_ptr(dy.device)
     # one parameter: direct whenever it has an arena slice (accumulate = 1)
     (dw, ), direct = _grad_outs((pw, ), (True, ), lambda p: torch.empty_like(w))
-    need = lib.ld_conv_wgrad_workspace_bytes(C.byref(d))
+    # the forward's small-Cin predicate plus the flat kernel's geometry limits
+    # (Cin k k <= 160, Cout 32 / 64, one level): one flat (ci, kh, kw) GEMM
+    # dimension instead of a 128 x 128 tile per tap; fp32 operands in either
+    # precision mode, like the forward
+    smallc = cin < 16 and \
+        lib.ld_conv_wgrad_smallc_supported(C.byref(d)) == 1
+    need = lib.ld_conv_wgrad_smallc_workspace_bytes(C.byref(d)) if smallc \
+        else lib.ld_conv_wgrad_workspace_bytes(C.byref(d))
     # with a gradient arena only the split partials are computed here; their
     # sum runs once per bucket (flush_deferred)
     defer = direct and _DEFER_ON[0]
@@ -1470,9 +1477,9 @@ def _conv_wgrad(lib, x3, w, dy, d, pw, c8w):
     bf16 = _PRECISION[0] == 'bf16' and cin >= 16
     family = 2 if c8w else 1 if bf16 else 0
     fam = _FAMILIES[family]
-    wgrad = getattr(lib, fam.wgrad)
+    wgrad = lib.ld_conv_wgrad_smallc if smallc else getattr(lib, fam.wgrad)
     side = _wgrad_side_for(dw if direct else None, dy.device)
-    if family == 0:
+    if family == 0 and not smallc:
         # explicit tuning writes its result with accumulate = 0: into a
         # scratch dW, never into the gradient arena
         def _tune_wgrad():
@@ -1494,10 +1501,16 @@ def _conv_wgrad(lib, x3, w, dy, d, pw, c8w):
             return
         slabs = _defer_buffer(pw, '_ld_slabs', need, dy.device)
         job = L.WgradJobT()
-        L.check(lib.ld_conv_wgrad_partial(
-            C.byref(d), family, L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
-            slabs.numel(), C.byref(job), stream_ptr),
-            'ld_conv_wgrad_partial')
+        if smallc:  # the same job format: a slab is the flat dW
+            L.check(lib.ld_conv_wgrad_smallc_partial(
+                C.byref(d), L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
+                slabs.numel(), C.byref(job), stream_ptr),
+                'ld_conv_wgrad_smallc_partial')
+        else:
+            L.check(lib.ld_conv_wgrad_partial(
+                C.byref(d), family, L.ptr(xw), L.ptr(dyw), L.ptr(slabs),
+                slabs.numel(), C.byref(job), stream_ptr),
+                'ld_conv_wgrad_partial')
         _defer_wgrad_job(job, dw, dy.device)
 
     with _timed('conv_wgrad' + fam.timed, d):
@@ -2368,12 +2381,7 @@ def copy_into(dst, src):
     return dst
 
 
-def maxpool3x3s2(x4):
-    """MaxPool2d(3, 2, 1), forward only (frozen stem)."""
-    _dev_f32(x4, 'maxpool input')
-    if x4.requires_grad and torch.is_grad_enabled():
-        raise L.LdError('maxpool3x3s2 has no backward (the stem is frozen: '
-                        'frozen_stages >= 0 is required)')
+def _maxpool_forward(x4):
     lib = L.get_lib()
     N, c, h, w = x4.shape
     ho, wo = out_size(h, 3, 2, 1), out_size(w, 3, 2, 1)
@@ -2381,6 +2389,40 @@ def maxpool3x3s2(x4):
     L.check(lib.ld_maxpool3x3s2(L.ptr(x4), N * c, h, w, L.ptr(y),
                                 L.stream_ptr(x4.device)), 'ld_maxpool3x3s2')
     return y
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """MaxPool2d(3, 2, 1) of a trainable stem.  backward = a gather over the at
+    most four windows of every input pixel (ld_maxpool_3x3s2_backward): the
+    gradient of a window goes to its first maximum in row-major order, as in
+    torch, and every dx element is written (no memset, no atomics).  The
+    output's consumers use the fan protocol; the producer needs nothing."""
+
+    @staticmethod
+    def forward(ctx, x4):
+        ctx.save_for_backward(x4)
+        return _maxpool_forward(x4)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x4, = ctx.saved_tensors
+        dy = dy.contiguous()
+        _dev_f32(dy, 'maxpool output gradient')
+        N, c, h, w = x4.shape
+        dx = torch.empty_like(x4)
+        L.check(L.get_lib().ld_maxpool_3x3s2_backward(
+            L.ptr(x4), L.ptr(dy), N * c, h, w, L.ptr(dx),
+            L.stream_ptr(dy.device)), 'ld_maxpool_3x3s2_backward')
+        return dx
+
+
+def maxpool3x3s2(x4):
+    """MaxPool2d(3, 2, 1); differentiable (MaxPoolFn) when the input requires
+    a gradient -- the trainable stem, frozen_stages = -1."""
+    _dev_f32(x4, 'maxpool input')
+    if x4.requires_grad and torch.is_grad_enabled():
+        return MaxPoolFn.apply(x4)
+    return _maxpool_forward(x4)
 
 
 # ---------------------------------------------------------------------------

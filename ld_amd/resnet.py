@@ -382,12 +382,9 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         """(N, 3, H, W) -> tuple of stage outputs (resnet.py:622-637)."""
+        self._stem_refusals()  # (before any launch)
         L.require_device(x, torch.float32, 'backbone input')
         n, c, h, w = x.shape
-        if self.frozen_stages < 0 and torch.is_grad_enabled():
-            raise NotImplementedError(
-                'a trainable stem needs a max-pool backward; the LD configs '
-                'freeze it (frozen_stages=1)')
         x3, lv = x.reshape(n, c, h * w), ((h, w), )
         if self.deep_stem:
             for i in (0, 3, 6):
@@ -402,6 +399,20 @@ class ResNet(nn.Module):
             with Y.c8_only_scope():
                 return self._stages(Y.C8Act(Y.to_c8(x3), x3.shape), lv, n)
         return self._stages(x3, lv, n, self._frozen_c8_stages())
+
+    def _stem_refusals(self):
+        """What a trainable stem (``frozen_stages < 0`` under grad mode: conv
+        -> BN -> ReLU -> layers.MaxPoolFn, the conv's weight gradient from the
+        small-Cin kernel) refuses whatever its input is."""
+        if self.frozen_stages >= 0 or not torch.is_grad_enabled():
+            return
+        if Y.get_precision() == 'bf16':
+            raise NotImplementedError(
+                'a trainable stem (frozen_stages < 0) under bf16 precision '
+                'mode is not implemented: the max-pool backward is an fp32 '
+                'kernel and the stages behind it would want bf16 C8 images; '
+                'train it with set_precision("fp32") or freeze the stem '
+                '(frozen_stages >= 0)')
 
     def _frozen_c8_stages(self):
         """bf16 mode, training student: its FROZEN leading stages (frozen_stages
