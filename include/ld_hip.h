@@ -708,9 +708,9 @@ int ld_record_free(int64_t handle);
  * they start behind everything enqueued on `stream` and `stream` ends up behind
  * them.  The graph and every buffer the captured step touched must outlive the
  * list.  ld_step_list_info: counts[8] = {kernel, memcpy, memset, ordering-only
- * nodes, lanes, cross-lane waits, nodes, 0}.  Nothing in the reference (mmcv's
- * runner issues every kernel from Python, mmdet/apis/train.py:74-127): what takes
- * the host language out of the student's ~350 launches per step. */
+ * nodes, lanes, cross-lane waits, nodes, cut marks}.  Nothing in the reference
+ * (mmcv's runner issues every kernel from Python, mmdet/apis/train.py:74-127): what
+ * takes the host language out of the student's ~350 launches per step. */
 int64_t ld_step_list_build(void* hip_graph, int max_lanes);
 /* Device-to-device copy as ONE kernel launch (16 bytes per lane): what a step that
  * will be captured uses instead of hipMemcpyAsync, whose captured 1-D memcpy node
@@ -719,6 +719,26 @@ int ld_copy_d2d(void* dst, const void* src, size_t bytes, ld_stream_t stream);
 int ld_step_list_info(int64_t handle, int* counts);
 int ld_step_list_replay(int64_t handle, ld_stream_t stream);
 int ld_step_list_free(int64_t handle);
+/* Cut marks: collectives BETWEEN the segments of a replay (a multi-process job; an
+ * RCCL call inside a capture races with ProcessGroupNCCL's watchdog thread).  While
+ * the step is captured, ld_step_list_mark(index, stream) stands where a collective
+ * belongs: one launch of a marker kernel, index counting up from 0 per capture.
+ * ld_step_list_build recognises the node by the kernel's address (LD_EINVAL if the
+ * indices do not count up in list order) and counts it in counts[7];
+ * ld_step_list_replay treats it as an ordering-only node.
+ * ld_step_list_replay_until is the same replay in segments: with *cursor = 0 it
+ * forks the lanes and issues the nodes in list order (capture order: the order the
+ * eager step enqueued them in) up to the first mark, then returns *mark = its index,
+ * *lane / *lane_stream = the lane it was captured on (lane 0 is `stream`).  That
+ * stream is behind everything the mark depends on; what the caller enqueues on it
+ * before the next call (the all-reduce, or the wait for one) is what the mark's
+ * successors on every lane wait for.  Call again with the *cursor it left; the call
+ * that runs off the end joins the lanes and returns *mark = -1, *cursor = 0.  Same
+ * `stream` in every call of one replay; failures are reported as for
+ * ld_step_list_replay (ld_step_list_last_failure). */
+int ld_step_list_mark(int index, ld_stream_t stream);
+int ld_step_list_replay_until(int64_t handle, ld_stream_t stream, int* cursor, int* mark,
+                              int* lane, void** lane_stream);
 /* debugging aid: the node the last failing replay stopped at: out8 = {node index,
  * hipGraphNodeType, hipError_t, lane, four type-specific details} */
 int ld_step_list_last_failure(int* out8);

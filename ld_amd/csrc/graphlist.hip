@@ -42,12 +42,13 @@ struct Node {
   std::vector<int> waits;      // predecessors on other lanes
   hipEvent_t event = nullptr;  // recorded after this node (if `record`)
   bool module_fn = false;      // func is a hipFunction_t (hipModuleLaunchKernel)
+  int mark = -1;               // >= 0: a cut mark (ld_step_list_mark), never launched
 };
 
 struct StepList {
   std::vector<Node> nodes;
   int nlanes = 1;
-  int n_kernel = 0, n_memcpy = 0, n_memset = 0, n_noop = 0, n_cross = 0;
+  int n_kernel = 0, n_memcpy = 0, n_memset = 0, n_noop = 0, n_cross = 0, n_mark = 0;
   std::vector<hipStream_t> side;  // lanes 1 .. nlanes - 1 (lane 0 = the caller's)
   hipEvent_t fork = nullptr;
   std::vector<hipEvent_t> join;
@@ -68,7 +69,16 @@ void destroy(StepList* s) {
   delete s;
 }
 
+// A cut mark in a captured step: the place where the host issues a collective
+// between two segments of a replay (ld_step_list_replay_until).  It survives the
+// capture as an ordinary kernel node whose function is this kernel -- the build
+// recognises it by that address and reads the mark's index from its argument --
+// and it carries the dependency edges of the collective it stands for.  A replay
+// never launches it.
+__global__ void ld_step_mark_kernel(int index) { (void)index; }
+
 hipError_t issue(Node& n, hipStream_t st) {
+  if (n.mark >= 0) return hipSuccess;  // ordering only: the host acts here
   switch (n.type) {
     case hipGraphNodeTypeKernel: {
       if (!n.module_fn) {
@@ -169,6 +179,17 @@ extern "C" int64_t ld_step_list_build(void* hip_graph, int max_lanes) {
         // arguments packed in `extra` (module-API launch): only hipModuleLaunchKernel
         // takes that form
         if (e == hipSuccess && !n.kp.kernelParams && n.kp.extra) n.module_fn = true;
+        if (e == hipSuccess && n.kp.func == (void*)ld_step_mark_kernel) {
+          // marks count up in capture order (the order the host will act in);
+          // anything else is a record this file cannot cut
+          if (!n.kp.kernelParams || !n.kp.kernelParams[0] ||
+              *(const int*)n.kp.kernelParams[0] != s->n_mark) {
+            destroy(s);
+            return LD_EINVAL;
+          }
+          n.mark = s->n_mark++;
+          break;
+        }
         ++s->n_kernel;
         break;
       case hipGraphNodeTypeMemcpy:
@@ -306,70 +327,161 @@ extern "C" int64_t ld_step_list_build(void* hip_graph, int max_lanes) {
 }
 
 // counts[8] = {kernel, memcpy, memset, ordering-only nodes, lanes, cross-lane
-// waits, total nodes, 0}
+// waits, total nodes, cut marks}
 extern "C" int ld_step_list_info(int64_t handle, int* counts) {
   std::lock_guard<std::mutex> lock(g_mu);
   auto it = g_lists.find(handle);
   if (it == g_lists.end() || !counts) return LD_EINVAL;
   const StepList* s = it->second;
   const int v[8] = {s->n_kernel, s->n_memcpy, s->n_memset, s->n_noop,
-                    s->nlanes,   s->n_cross,  (int)s->nodes.size(), 0};
+                    s->nlanes,   s->n_cross,  (int)s->nodes.size(), s->n_mark};
   for (int i = 0; i < 8; ++i) counts[i] = v[i];
   return 0;
 }
 
+namespace {
+
+StepList* find_list(int64_t handle) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = g_lists.find(handle);
+  return it == g_lists.end() ? nullptr : it->second;
+}
+
+hipError_t fork_lanes(StepList* s, hipStream_t main) {
+  if (s->nlanes > 1) {
+    if (hipError_t e = hipEventRecord(s->fork, main)) return e;
+    for (hipStream_t st : s->side)
+      if (hipError_t e = hipStreamWaitEvent(st, s->fork, 0)) return e;
+  }
+  return hipSuccess;
+}
+
+hipError_t join_lanes(StepList* s, hipStream_t main) {
+  for (int l = 1; l < s->nlanes; ++l) {
+    if (hipError_t e = hipEventRecord(s->join[l - 1], s->side[l - 1])) return e;
+    if (hipError_t e = hipStreamWaitEvent(main, s->join[l - 1], 0)) return e;
+  }
+  return hipSuccess;
+}
+
+void note_failure(StepList* s, Node& n, hipError_t e) {
+  g_fail[0] = (int)(&n - s->nodes.data());
+  g_fail[1] = (int)n.type;
+  g_fail[2] = (int)e;
+  g_fail[3] = n.lane;
+  if (n.type == hipGraphNodeTypeMemcpy) {
+    g_fail[4] = (int)n.cp.kind;
+    g_fail[5] = (int)n.cp.extent.width;
+    g_fail[6] = (int)n.cp.extent.height;
+    g_fail[7] = (int)n.cp.extent.depth;
+  } else if (n.type == hipGraphNodeTypeMemset) {
+    g_fail[4] = (int)n.ms.elementSize;
+    g_fail[5] = (int)n.ms.width;
+    g_fail[6] = (int)n.ms.height;
+    g_fail[7] = (int)n.ms.pitch;
+  } else if (n.type == hipGraphNodeTypeKernel) {
+    g_fail[4] = (int)n.kp.gridDim.x;
+    g_fail[5] = (int)n.kp.blockDim.x;
+    g_fail[6] = (int)n.kp.sharedMemBytes;
+    g_fail[7] = n.kp.kernelParams ? 1 : 0;
+  }
+}
+
+// Nodes [from, ...) in list order up to and excluding the first cut mark when
+// `stop_at_mark` (its cross-lane waits are enqueued: the mark's lane is then
+// behind everything the mark depends on), else to the end.  Returns the index of
+// that mark's node, or the node count.
+hipError_t issue_from(StepList* s, hipStream_t main, size_t from, bool stop_at_mark,
+                      size_t* stopped) {
+  size_t k = from;
+  for (; k < s->nodes.size(); ++k) {
+    Node& n = s->nodes[k];
+    hipStream_t st = n.lane == 0 ? main : s->side[n.lane - 1];
+    for (int w : n.waits)
+      if (hipError_t e = hipStreamWaitEvent(st, s->nodes[w].event, 0)) return e;
+    if (stop_at_mark && n.mark >= 0) break;
+    if (hipError_t e = issue(n, st)) {
+      note_failure(s, n, e);
+      return e;
+    }
+    if (n.record)
+      if (hipError_t e = hipEventRecord(n.event, st)) return e;
+  }
+  *stopped = k;
+  return hipSuccess;
+}
+
+}  // namespace
+
 // Re-issues the step on `stream` (lane 0) and the list's own side streams: they
 // start after everything enqueued on `stream` so far, and `stream` ends up behind
 // all of them, so the replay is ordered like ONE operation of `stream`.  Only
-// enqueues.  One replay at a time per list (its events are re-recorded).
+// enqueues.  One replay at a time per list (its events are re-recorded).  Cut
+// marks are ordering-only nodes here.
 extern "C" int ld_step_list_replay(int64_t handle, ld_stream_t stream) {
-  StepList* s;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    auto it = g_lists.find(handle);
-    if (it == g_lists.end()) return LD_EINVAL;
-    s = it->second;
-  }
+  StepList* s = find_list(handle);
+  if (!s) return LD_EINVAL;
   hipStream_t main = (hipStream_t)stream;
-  if (s->nlanes > 1) {
-    if (hipError_t e = hipEventRecord(s->fork, main)) return (int)e;
-    for (hipStream_t st : s->side)
-      if (hipError_t e = hipStreamWaitEvent(st, s->fork, 0)) return (int)e;
+  size_t end = 0;
+  if (hipError_t e = fork_lanes(s, main)) return (int)e;
+  if (hipError_t e = issue_from(s, main, 0, false, &end)) return (int)e;
+  if (hipError_t e = join_lanes(s, main)) return (int)e;
+  return 0;
+}
+
+// Leaves cut mark `index` on `stream`: one launch of the marker kernel, which a
+// capture records as the node ld_step_list_build recognises.  Marks of one capture
+// count up from 0 in the order they are left.
+extern "C" int ld_step_list_mark(int index, ld_stream_t stream) {
+  if (index < 0) return LD_EINVAL;
+  hipLaunchKernelGGL(ld_step_mark_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, index);
+  return (int)hipGetLastError();
+}
+
+// The replay in segments.  *cursor = 0 starts one: the fork of ld_step_list_replay,
+// then the nodes in list order (= capture order = the order the eager step
+// enqueued them) up to the first cut mark.  At a mark the call returns with *mark =
+// its index, *lane / *lane_stream = the lane it was captured on (lane 0: `stream`
+// itself) -- that stream is behind everything the mark depends on, and whatever
+// the caller enqueues on it before the next call is what the mark's successors,
+// on every lane, wait for.  Call again with the *cursor it left.  The call that
+// runs off the end joins the lanes and sets *mark = -1, *cursor = 0.  `stream`
+// must be the same in every call of one replay.
+extern "C" int ld_step_list_replay_until(int64_t handle, ld_stream_t stream, int* cursor,
+                                         int* mark, int* lane, void** lane_stream) {
+  StepList* s = find_list(handle);
+  if (!s || !cursor || !mark || !lane || !lane_stream) return LD_EINVAL;
+  hipStream_t main = (hipStream_t)stream;
+  const size_t nn = s->nodes.size();
+  size_t from = 0;
+  if (*cursor == 0) {
+    if (hipError_t e = fork_lanes(s, main)) return (int)e;
+  } else {
+    // resuming behind the mark at node *cursor - 1: the caller's work on its lane
+    // is enqueued, the mark's event (if any lane waits for it) goes after it
+    if (*cursor < 1 || (size_t)*cursor > nn || s->nodes[*cursor - 1].mark < 0)
+      return LD_EINVAL;
+    Node& m = s->nodes[*cursor - 1];
+    if (m.record)
+      if (hipError_t e = hipEventRecord(m.event, m.lane == 0 ? main : s->side[m.lane - 1]))
+        return (int)e;
+    from = (size_t)*cursor;
   }
-  for (Node& n : s->nodes) {
-    hipStream_t st = n.lane == 0 ? main : s->side[n.lane - 1];
-    for (int w : n.waits)
-      if (hipError_t e = hipStreamWaitEvent(st, s->nodes[w].event, 0)) return (int)e;
-    if (hipError_t e = issue(n, st)) {
-      g_fail[0] = (int)(&n - s->nodes.data());
-      g_fail[1] = (int)n.type;
-      g_fail[2] = (int)e;
-      g_fail[3] = n.lane;
-      if (n.type == hipGraphNodeTypeMemcpy) {
-        g_fail[4] = (int)n.cp.kind;
-        g_fail[5] = (int)n.cp.extent.width;
-        g_fail[6] = (int)n.cp.extent.height;
-        g_fail[7] = (int)n.cp.extent.depth;
-      } else if (n.type == hipGraphNodeTypeMemset) {
-        g_fail[4] = (int)n.ms.elementSize;
-        g_fail[5] = (int)n.ms.width;
-        g_fail[6] = (int)n.ms.height;
-        g_fail[7] = (int)n.ms.pitch;
-      } else if (n.type == hipGraphNodeTypeKernel) {
-        g_fail[4] = (int)n.kp.gridDim.x;
-        g_fail[5] = (int)n.kp.blockDim.x;
-        g_fail[6] = (int)n.kp.sharedMemBytes;
-        g_fail[7] = n.kp.kernelParams ? 1 : 0;
-      }
-      return (int)e;
-    }
-    if (n.record)
-      if (hipError_t e = hipEventRecord(n.event, st)) return (int)e;
+  size_t at = 0;
+  if (hipError_t e = issue_from(s, main, from, true, &at)) return (int)e;
+  if (at < nn) {
+    const Node& m = s->nodes[at];
+    *cursor = (int)at + 1;
+    *mark = m.mark;
+    *lane = m.lane;
+    *lane_stream = m.lane == 0 ? (void*)main : (void*)s->side[m.lane - 1];
+    return 0;
   }
-  for (int l = 1; l < s->nlanes; ++l) {
-    if (hipError_t e = hipEventRecord(s->join[l - 1], s->side[l - 1])) return (int)e;
-    if (hipError_t e = hipStreamWaitEvent(main, s->join[l - 1], 0)) return (int)e;
-  }
+  if (hipError_t e = join_lanes(s, main)) return (int)e;
+  *cursor = 0;
+  *mark = -1;
+  *lane = 0;
+  *lane_stream = (void*)main;
   return 0;
 }
 

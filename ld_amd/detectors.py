@@ -242,10 +242,13 @@ class SingleStageDetector(nn.Module):
         parts = [key_sums.detach(), loss.detach().reshape(1)]
         logged = torch.cat(parts) if out is None else \
             torch.cat(parts, out=out(len(names) + 1))
-        from .train import _diag_skip, collectives_on
+        from .train import _diag_skip, all_reduce_or_record, collectives_on
         if collectives_on() and not _diag_skip('logs'):
-            logged = logged.clone()
-            dist.all_reduce(logged.div_(dist.get_world_size()))
+            # (a new tensor by the division itself, not clone() + div_(): the same
+            # values from one launch, and no memcpy node in a captured step --
+            # ld_step_list_build cannot re-issue those)
+            logged = logged / dist.get_world_size()
+            all_reduce_or_record(logged)
         log_vars = LazyScalars(names + ['loss'], logged)
         return loss, log_vars
 

@@ -437,7 +437,7 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         side all-reduce instead of the reference's two reduce_mean(...).item()
         host syncs (ld_head.py:338-341,362-363)."""
         import torch.distributed as dist
-        from .train import _diag_skip, collectives_on
+        from .train import _diag_skip, all_reduce_or_record, collectives_on
         slot = LB.virtual_norm_slot()
         if slot is not None:
             # SGDTrainer(virtual_ranks=W): this micro-batch's partials go into
@@ -449,7 +449,7 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         ws = float(dist.get_world_size())
 
         def _r(norm):
-            dist.all_reduce(norm)
+            all_reduce_or_record(norm)
             norm.div_(ws)
 
         return _r

@@ -55,6 +55,133 @@ class suspend_collectives:
         _SUSPENDED[0] -= 1
 
 
+_RECORDING = []
+
+
+class CollectivePlan:
+    """The collectives of ONE captured step, in the order the eager step issues
+    them (normaliser, logs, buckets in bucket order), each with the tensor it
+    reduces -- a buffer of the capture's private pool, so the address a replay
+    reduces is the one the captured kernels read and write.  Filled under
+    ``record_collectives(plan)``; every entry leaves a cut mark on the stream the
+    eager step would have called ``dist.all_reduce`` from (``ld_step_list_mark``:
+    a node the step list recognises and stops at).  Kinds:
+      * ``'sync'``  -- ``dist.all_reduce(t)``: issue and wait at the same place in
+        stream order (the loss normaliser, the logged values);
+      * ``'issue'`` -- ``dist.all_reduce(t, async_op=True)`` (a gradient bucket,
+        from the weight-gradient stream: it overlaps the rest of backward);
+      * ``'wait'``  -- ``.wait()`` of the ``'issue'`` entry ``ref`` (the main
+        stream in ``GradArena.finish``).
+    ``run`` is the replay's side: it issues them between the segments of a list."""
+
+    def __init__(self):
+        self.entries = []  # (kind, tensor, ref)
+
+    def __len__(self):
+        return len(self.entries)
+
+    @property
+    def collectives(self):
+        """all-reduces per replay (a wait mark is not one)."""
+        return sum(1 for kind, _, _ in self.entries if kind != 'wait')
+
+    def add(self, kind, tensor=None, ref=None):
+        if kind not in ('sync', 'issue', 'wait'):
+            raise ValueError(f'CollectivePlan: unknown kind {kind!r}')
+        if kind == 'wait':
+            if ref is None or not 0 <= ref < len(self.entries) or \
+                    self.entries[ref][0] != 'issue':
+                raise ValueError(f'CollectivePlan: wait for entry {ref}, which '
+                                 'is not an issued all-reduce')
+            tensor = self.entries[ref][1]
+        index = len(self.entries)
+        self.entries.append((kind, tensor, ref))
+        if tensor.is_cuda:
+            from . import lib as L
+            L.check(L.get_lib().ld_step_list_mark(index, L.stream_ptr(tensor.device)),
+                    'ld_step_list_mark')
+        return index
+
+    def run(self, segments):
+        """Drive one replay.  ``segments`` yields ``(mark, stream)`` each time the
+        list has enqueued everything up to cut mark ``mark`` (``stream``: the lane
+        the mark was captured on, None for the caller's current stream) and
+        enqueues the rest when it is resumed.  The marks must be exactly this
+        plan's entries, in order: a rank that replays issues the collectives its
+        eagerly stepping peers issue."""
+        works, n = {}, 0
+        for mark, stream in segments:
+            if mark != n or n >= len(self.entries):
+                raise RuntimeError(
+                    f'step list stopped at cut mark {mark}, the plan expects '
+                    f'{n} of {len(self.entries)}')
+            kind, t, ref = self.entries[n]
+            if stream is None:
+                works[n] = self._act(kind, t, works, ref)
+            else:
+                with torch.cuda.stream(stream):
+                    works[n] = self._act(kind, t, works, ref)
+            n += 1
+        if n != len(self.entries):
+            raise RuntimeError(
+                f'step list ended after {n} cut marks, the plan holds '
+                f'{len(self.entries)} entries: collectives were not issued')
+        if any(w is not None for w in works.values()):
+            raise RuntimeError('step list ended with all-reduces nobody waited for')
+
+    @staticmethod
+    def _act(kind, t, works, ref):
+        # dist.all_reduce looked up at call time (tests count calls by replacing it)
+        if kind == 'sync':
+            dist.all_reduce(t)
+        elif kind == 'issue':
+            return dist.all_reduce(t, async_op=True)
+        else:
+            works[ref].wait()
+            works[ref] = None
+        return None
+
+
+class record_collectives:
+    """``with record_collectives(plan):`` -- the third state beside "on" and
+    "suspended", for the capture of a step list under a process group.
+    ``collectives_on()`` stays True, so every arithmetic side effect of the
+    multi-rank step is captured (the normaliser's ``div_(world)``, the clone and
+    ``div_`` of the logged values, the bucket issue and wait points), but each site
+    that would call ``dist.all_reduce`` appends an entry to ``plan`` and leaves a
+    cut mark on its stream instead: no RCCL call is made while a stream captures.
+    Inside ``suspend_collectives`` suspension wins (nothing is on, nothing is
+    recorded)."""
+
+    def __init__(self, plan):
+        self.plan = plan
+
+    def __enter__(self):
+        _RECORDING.append(self.plan)
+        return self.plan
+
+    def __exit__(self, *exc):
+        _RECORDING.pop()
+
+
+def recording_plan():
+    """The plan collectives are recorded into, or None (not recording, or
+    suspended)."""
+    if _SUSPENDED[0] or not _RECORDING:
+        return None
+    return _RECORDING[-1]
+
+
+def all_reduce_or_record(tensor):
+    """A synchronous SUM all-reduce of ``tensor``: issued, or -- under
+    ``record_collectives`` -- recorded as a ``'sync'`` entry of the plan."""
+    plan = recording_plan()
+    if plan is None:
+        dist.all_reduce(tensor)
+    else:
+        plan.add('sync', tensor)
+
+
 def _diag_skip(kind):
     """LD_COLLECTIVES_SKIP=buckets,norm,logs -- timing diagnostics of the forced
     1-rank group only (tools/sessions): honoured when the group has ONE rank, where
@@ -194,7 +321,8 @@ class GradArena:
         self._seen.add(id(p))
         b = self.bucket_of[id(p)]
         self._ready[b] += 1
-        if self.trace is not None and self._ready[b] == self.buckets[b]['n']:
+        if self.trace is not None and self._ready[b] == self.buckets[b]['n'] \
+                and recording_plan() is None:  # no event timing inside a capture
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()
             self.trace.append((b, ev))
@@ -240,10 +368,26 @@ class GradArena:
                 self._all_reduce(todo)
 
     def _all_reduce(self, buckets):
+        plan = recording_plan()
         for b in buckets:
             bk = self.buckets[b]
-            self._works.append(dist.all_reduce(
-                self.flat_grad[bk['start']:bk['end']], async_op=True))
+            t = self.flat_grad[bk['start']:bk['end']]
+            if plan is not None:
+                # a capture for a step list: the issue mark on THIS stream (the
+                # weight-gradient stream in the LD step), the entry's index in
+                # place of the work object
+                self._works.append(plan.add('issue', t))
+            else:
+                self._works.append(dist.all_reduce(t, async_op=True))
+
+    def drain(self):
+        """Wait for bucket reductions still in flight (a step that raised between
+        issue and finish): nothing of RCCL's may be outstanding when a capture
+        begins."""
+        for w in self._works:
+            if hasattr(w, 'wait'):
+                w.wait()
+        self._works = []
 
     def finish(self):
         """Wait for the in-flight bucket reductions (sums, not yet averaged).
@@ -256,13 +400,18 @@ class GradArena:
             # what was held back or never completed, still in bucket order
             self._all_reduce(range(self._next, len(self.buckets)))
             self._next = len(self.buckets)
-            timed = self.exposed is not None and self.flat_grad.is_cuda
+            plan = recording_plan()
+            timed = self.exposed is not None and self.flat_grad.is_cuda and \
+                plan is None
             if timed:
                 a = torch.cuda.Event(enable_timing=True)
                 b = torch.cuda.Event(enable_timing=True)
                 a.record()
             for w in self._works:
-                w.wait()
+                if plan is not None:
+                    plan.add('wait', ref=w)  # the wait mark, on the main stream
+                else:
+                    w.wait()
             if timed:
                 b.record()
                 self.exposed.append((a, b))
@@ -790,22 +939,52 @@ def _refuse_virtual_ranks(trainer, what):
             'eagerly (its W live forward graphs are not captured or replayed)')
 
 
-def _refuse_collectives_in_capture(what):
-    """RCCL collectives inside a hipGraph capture: measured in round 5 under a
+def _refuse_collectives_in_capture(what, launcher='graph'):
+    """Returns the ``CollectivePlan`` to capture under (``launcher='list'`` with
+    collectives on: they are recorded as cut marks and issued by the host between
+    the segments of a replay, never inside the capture), None when the capture
+    holds its collectives itself or has none, and refuses the rest.
+
+    RCCL collectives inside a hipGraph capture: measured in round 5 under a
     one-rank RCCL group with the collectives forced (the only form a one-GPU box
     admits): the captured step replays bit-identical to the eager one when it
     works, but 2 of 3 runs died in ProcessGroupNCCL's WATCHDOG thread, which polls
     the events of collective work objects from another thread -- "operation not
     permitted when stream is capturing" in the default capture mode, "operation not
     permitted on an event last recorded in a capturing stream" in thread-local
-    mode.  Not something this library can order, so it is refused unless
-    LD_GRAPH_COLLECTIVES=1 (experiments)."""
-    if collectives_on() and os.environ.get('LD_GRAPH_COLLECTIVES') != '1':
-        raise RuntimeError(
-            f'{what}: capturing a train step that issues RCCL collectives is '
-            'refused (it races with ProcessGroupNCCL\'s watchdog thread on this '
-            'stack); multi-process jobs step eagerly -- AutoStepper does that by '
-            'default -- or set LD_GRAPH_COLLECTIVES=1 to try')
+    mode.  Not something this library can order, so ``launcher='graph'`` (one
+    hipGraphLaunch: nothing can be issued in between) is refused unless
+    LD_GRAPH_COLLECTIVES=1 (experiments; it then means the same for both
+    launchers: the RCCL calls are captured)."""
+    if not collectives_on() or os.environ.get('LD_GRAPH_COLLECTIVES') == '1':
+        return None
+    if launcher == 'list':
+        return CollectivePlan()
+    raise RuntimeError(
+        f'{what}: capturing a train step that issues RCCL collectives is '
+        'refused (it races with ProcessGroupNCCL\'s watchdog thread on this '
+        'stack); multi-process jobs step eagerly -- AutoStepper does that by '
+        'default -- or set LD_GRAPH_COLLECTIVES=1 to try')
+
+
+def _capture_collectives(plan):
+    """The context a step is captured in: recording into ``plan``, or nothing."""
+    import contextlib
+    return record_collectives(plan) if plan is not None else \
+        contextlib.nullcontext()
+
+
+def _checked_list(graph, plan):
+    """The step list of a capture made under ``plan``: every recorded collective
+    must have come back as a cut mark."""
+    sl = _StepList(graph)
+    want = len(plan) if plan is not None else 0
+    if sl.info['marks'] != want:
+        from . import lib as L
+        raise L.LdError(
+            f'the captured step recorded {want} collective marks, its step list '
+            f'holds {sl.info["marks"]}: the marker nodes were not recognised')
+    return sl
 
 
 def _capture_mode():
@@ -839,17 +1018,54 @@ class _StepList:
         counts = (C.c_int * 8)()
         L.check(L.get_lib().ld_step_list_info(self.handle, counts), 'ld_step_list_info')
         self.info = dict(zip(('kernels', 'memcpys', 'memsets', 'ordering_nodes',
-                              'lanes', 'cross_lane_waits', 'nodes'), list(counts)))
+                              'lanes', 'cross_lane_waits', 'nodes', 'marks'),
+                             list(counts)))
+        self._lane_streams = {}
+
+    def _failed(self, what, rc):
+        from . import lib as L
+        f = (C.c_int * 8)()
+        L.get_lib().ld_step_list_last_failure(f)
+        raise L.LdError(f'{what} failed (hipError_t {rc}) at node '
+                        f'{f[0]} of {self.info["nodes"]}: type {f[1]}, lane {f[3]}, '
+                        f'details {list(f)[4:]}')
 
     def replay(self, device):
         from . import lib as L
         rc = L.get_lib().ld_step_list_replay(self.handle, L.stream_ptr(device))
         if rc != 0:
-            f = (C.c_int * 8)()
-            L.get_lib().ld_step_list_last_failure(f)
-            raise L.LdError(f'ld_step_list_replay failed (hipError_t {rc}) at node '
-                            f'{f[0]} of {self.info["nodes"]}: type {f[1]}, lane {f[3]}, '
-                            f'details {list(f)[4:]}')
+            self._failed('ld_step_list_replay', rc)
+
+    def segments(self, device):
+        """One replay in segments (``ld_step_list_replay_until``): yields ``(mark,
+        stream)`` at every cut mark -- ``stream`` None on lane 0 (the caller's
+        stream), else the list's own stream of that lane -- and enqueues the next
+        segment when resumed; the last one joins the lanes."""
+        from . import lib as L
+        fn = L.get_lib().ld_step_list_replay_until
+        main = L.stream_ptr(device)
+        cursor, mark, lane = C.c_int(0), C.c_int(-1), C.c_int(0)
+        ptr = C.c_void_p()
+        while True:
+            rc = fn(self.handle, main, C.byref(cursor), C.byref(mark),
+                    C.byref(lane), C.byref(ptr))
+            if rc != 0:
+                self._failed('ld_step_list_replay_until', rc)
+            if mark.value < 0:
+                return
+            st = None
+            if lane.value != 0:
+                st = self._lane_streams.get(ptr.value)
+                if st is None:
+                    st = self._lane_streams[ptr.value] = \
+                        torch.cuda.ExternalStream(ptr.value, device=device)
+            yield mark.value, st
+
+    def replay_segments(self, device, plan):
+        """The replay of a step captured under ``record_collectives(plan)``: the
+        host issues the plan's collectives between the segments, each from the
+        stream its eager counterpart was issued from."""
+        plan.run(self.segments(device))
 
     def __del__(self):
         try:
@@ -899,9 +1115,15 @@ class GraphedStep:
     synchronisation: include/ld_hip.h), which is what makes the step capturable;
     shape tuning must have happened before (ld_conv_tune_* refuse a capturing
     stream).  Under a process group the captured step would contain the bucketed
-    RCCL all-reduces; that is REFUSED (see ``_refuse_collectives_in_capture``: it
-    races with ProcessGroupNCCL's watchdog thread) -- multi-process jobs step
-    eagerly, which round 5 made GPU-bound in bf16 as well.  ``warmup_collectives =
+    RCCL all-reduces; with ``launcher='graph'`` that is REFUSED (see
+    ``_refuse_collectives_in_capture``: it races with ProcessGroupNCCL's watchdog
+    thread).  With ``launcher='list'`` the step is captured under
+    ``record_collectives``: every collective becomes a cut mark of the step list and
+    an entry of ``self.plan``, and ``replay`` goes through
+    ``_StepList.replay_segments`` -- the host issues the real ``dist.all_reduce``
+    calls between the segments, in the eager step's order and from the eager step's
+    streams, so no RCCL call is ever made while a stream captures.  Work objects still
+    outstanding are waited for before the capture begins.  ``warmup_collectives =
     False`` runs the warm-up steps without collectives (see
     ``suspend_collectives``): for captures that only this rank performs.
     """
@@ -909,10 +1131,11 @@ class GraphedStep:
     def __init__(self, trainer, data, warmup=2, max_gt=128,
                  warmup_collectives=True, launcher='graph'):
         """``launcher='list'``: the captured graph is re-issued by a C launch loop
-        (``_StepList``) instead of hipGraphLaunch -- same launches, same buffers."""
+        (``_StepList``) instead of hipGraphLaunch -- same launches, same buffers;
+        the only launcher that works under a process group."""
         from . import lossblock as LB
         _refuse_virtual_ranks(trainer, f"GraphedStep(launcher='{launcher}')")
-        _refuse_collectives_in_capture('GraphedStep')
+        self.plan = _refuse_collectives_in_capture('GraphedStep', launcher)
         if launcher == 'graph':
             _warn_graph_queues('GraphedStep')
         self.trainer = trainer
@@ -951,12 +1174,15 @@ class GraphedStep:
                         with suspend_collectives():
                             trainer.step(self.data)
         torch.cuda.current_stream(dev).wait_stream(side)
+        trainer.arena.drain()
         torch.cuda.synchronize(dev)
         self.graph = _new_graph(launcher)
         with torch.cuda.graph(self.graph, stream=side,
                               capture_error_mode=_capture_mode()):
-            out = trainer.step(self.data)
-        self.list = _StepList(self.graph) if launcher == 'list' else None
+            with _capture_collectives(self.plan):
+                out = trainer.step(self.data)
+        self.list = _checked_list(self.graph, self.plan) if launcher == 'list' \
+            else None
         self._loss = out['loss']
         self._grad_norm = out.get('grad_norm')
         lv = out['log_vars']
@@ -992,7 +1218,9 @@ class GraphedStep:
     def replay(self):
         from .heads import LazyScalars
         self.trainer._before_step()
-        if self.list is not None:
+        if self.plan is not None:
+            self.list.replay_segments(self.dev, self.plan)
+        elif self.list is not None:
             self.list.replay(self.dev)
         else:
             self.graph.replay()
@@ -1025,11 +1253,14 @@ class PipelinedGraphedStep:
     (tests/test_gpu_graph.py)."""
 
     def __init__(self, trainer, first, second, warmup=1, max_gt=128,
-                 launcher='graph'):
+                 launcher='graph', warmup_collectives=True):
+        """``launcher`` and ``warmup_collectives`` as in ``GraphedStep``; under a
+        process group each of the two lists has its own ``CollectivePlan``."""
         from . import lossblock as LB
         _refuse_virtual_ranks(
             trainer, f"PipelinedGraphedStep(launcher='{launcher}')")
-        _refuse_collectives_in_capture('PipelinedGraphedStep')
+        plan = _refuse_collectives_in_capture('PipelinedGraphedStep', launcher)
+        self.plans = [plan, CollectivePlan() if plan is not None else None]
         if launcher == 'graph':
             _warn_graph_queues('PipelinedGraphedStep')
         self.trainer = trainer
@@ -1066,23 +1297,30 @@ class PipelinedGraphedStep:
             with Y.capture_warmup():
                 for _ in range(max(warmup, 1)):
                     for sl in self.slots:
-                        trainer.step(sl['data'])
+                        if warmup_collectives:
+                            trainer.step(sl['data'])
+                        else:  # captures only THIS rank performs (AutoStepper)
+                            with suspend_collectives():
+                                trainer.step(sl['data'])
             for sl in self.slots:
                 tx, tout = model._teacher_forward(sl['data']['img'])
                 sl['teacher'] = (tuple(t.clone() for t in tx),
                                  tuple([t.clone() for t in lvl]
                                        for lvl in tout))
         torch.cuda.current_stream(dev).wait_stream(cap)
+        trainer.arena.drain()
         torch.cuda.synchronize(dev)
         self.graphs, self.outs, self.lists = [], [], []
         for k in (0, 1):
             g = _new_graph(launcher)
             with torch.cuda.graph(g, stream=cap,
                                   capture_error_mode=_capture_mode()):
-                out = self._one(k)
+                with _capture_collectives(self.plans[k]):
+                    out = self._one(k)
             lv = out['log_vars']
             self.graphs.append(g)
-            self.lists.append(_StepList(g) if launcher == 'list' else None)
+            self.lists.append(_checked_list(g, self.plans[k])
+                              if launcher == 'list' else None)
             self.outs.append((out['loss'], list(lv._keys), lv._tensor,
                               out['num_samples'], out.get('grad_norm')))
         self.cur = 0
@@ -1121,7 +1359,9 @@ class PipelinedGraphedStep:
         nxt['static'].load(next_data['img_metas'], next_data['gt_bboxes'],
                            next_data['gt_labels'])
         self.trainer._before_step()
-        if self.lists[self.cur] is not None:
+        if self.plans[self.cur] is not None:
+            self.lists[self.cur].replay_segments(self.dev, self.plans[self.cur])
+        elif self.lists[self.cur] is not None:
             self.lists[self.cur].replay(self.dev)
         else:
             self.graphs[self.cur].replay()
@@ -1145,7 +1385,8 @@ class AutoStepper:
     ``data``; the results are bit-identical in every mode.
       * ``'eager'`` (the default since round 5, every precision): ``trainer.step``
         with the frozen teacher of ``next_data`` one step ahead on its own stream;
-      * ``'graph'`` (on request; single-process jobs): one ``GraphedStep`` per padded
+      * ``'graph'`` (on request; under a process group only with
+        ``launcher='list'``): one ``GraphedStep`` per padded
         image shape (the reference's GroupSampler yields two aspect-ratio
         groups, mmdet/datasets/samplers/group_sampler.py), captured the first
         time a shape is seen.  The capture's warm-up steps are real steps on
@@ -1159,6 +1400,14 @@ class AutoStepper:
     are re-issued by the C launch loop of ``_StepList`` instead of hipGraphLaunch --
     ~2 ms of host time per step instead of ~11, the same step time (the GPU bounds
     both precisions with one rank per GPU); what a host with few cores per GPU wants.
+    Under a process group it is also the only launcher that captures: the
+    collectives are recorded as cut marks (``record_collectives``) and issued by the
+    host between the segments of each replay, the same ones in the same order
+    (normaliser, logs, buckets in bucket order) as a peer that steps eagerly at that
+    iteration.  The first step of such a job is eager on every rank, the captures'
+    warm-up steps run with collectives suspended (only this rank captures at this
+    iteration).  ``launcher='graph'`` under a process group raises at the first
+    capture (``_refuse_collectives_in_capture``).
     """
 
     def __init__(self, trainer, mode=None, warmup=1, max_gt=128, max_graphs=6,
@@ -1173,10 +1422,11 @@ class AutoStepper:
             # two hipGraphs (profiles/r05_bench_final_bf16_wgrad_side.json) -- a
             # graph launch costs ~19 us of host time per node on this runtime
             # (profiles/r05_graph_launch_knobs.jsonl), more than an eager launch
-            # now does.  A multi-process job (BASELINE config 3's form) could not
-            # capture anyway: RCCL collectives inside a capture race with
-            # ProcessGroupNCCL's watchdog (_refuse_collectives_in_capture).  'graph'
-            # and 'pipelined' stay available on request.
+            # now does.  A multi-process job (BASELINE config 3's form) cannot hold
+            # RCCL collectives inside a capture: they race with ProcessGroupNCCL's
+            # watchdog (_refuse_collectives_in_capture); launcher='list' cuts the
+            # step at them instead.  'graph' and 'pipelined' stay available on
+            # request.
             mode = 'eager'
         if mode not in ('eager', 'graph', 'pipelined'):
             raise ValueError(f'AutoStepper: unknown mode {mode!r}')
@@ -1264,7 +1514,8 @@ class AutoStepper:
             self._pipe = PipelinedGraphedStep(self.trainer, data, next_data,
                                               warmup=self.warmup,
                                               max_gt=self.max_gt,
-                                              launcher=self.launcher)
+                                              launcher=self.launcher,
+                                              warmup_collectives=False)
             torch.cuda.synchronize(data['img'].device)
             self._restore_state(st)
             self._pipe_loaded = data
