@@ -1243,6 +1243,42 @@ int ld_deform_col2im_sum(const float* d_col, int N, int Cin, int Hin, int Win, i
                          int KW, int stride, int pad, int dilation, void* workspace,
                          size_t workspace_bytes, float* d_x, ld_stream_t stream);
 
+/* ---- modulated deformable convolution, DCNv2 (conv type 'DCNv2'; trainable) ---
+ * mmcv.ops.ModulatedDeformConv2dPack, deform_groups = 1 (Zhu et al. 2019,
+ * "Deformable ConvNets v2"; parity with mmcv UNPINNED: the op is in neither the
+ * reference checkout nor on the build machine; checked against the float64
+ * restatement tests/_mdcn_ref64.py).  `om` (N, 3*KH*KW, Hout, Wout) is the raw
+ * output of the layer's conv_offset: channels [0, 2*KH*KW) are the offsets,
+ * (dy, dx) interleaved per tap exactly as ld_deform_im2col's `offset`; channels
+ * [2*KH*KW, 3*KH*KW) are the mask logits, one per tap.  No offset / mask tensor
+ * is materialised: the kernels read the planes of `om` and take the sigmoid
+ * themselves.
+ *   col[n][ci*KH*KW + t][p] = sigmoid(logit_t(p)) * (v1's four-term bilinear sum)
+ * with v1's window, floor, zero corners and term order; the mask multiplies the
+ * finished sum, so with om = 0 col is exactly 0.5 x ld_deform_im2col's.
+ * ld_mdeform_offset_mask_grad writes all 3*KH*KW channels of d_om in one launch
+ * (one writer per element, every element written): the offset channels are v1's
+ * expression times m, the logit channels m (1 - m) sum_ci d_col * (four-term
+ * sum) -- exactly 0 where the sample is outside (-1, H) x (-1, W).
+ * Data gradient: ld_mdeform_col2im_index is ld_deform_col2im_index with every
+ * corner weight stored as weight * m.  The workspace layout is unchanged, so
+ * ld_deform_col2im_workspace_bytes sizes it and ld_deform_col2im_sum consumes
+ * it as they are (no float atomics; bitwise reproducible).
+ * Return codes as the v1 entry points.  Measured once on an MI355X against the
+ * v1 calls of the same shape (R101 c3-c5 conv2 at 2 x 800 x 1344; HIP events, v1
+ * and v2 alternating in one process; tools/bench_mdcn.py ->
+ * profiles/mdcn_latency.json): im2col 0.72-0.96 x, offset + mask gradient
+ * 1.00-1.03 x, index 1.00-1.02 x, index + sum 1.00-1.01 x the v1 call. */
+int ld_mdeform_im2col(const float* x, const float* om, int N, int Cin, int Hin, int Win,
+                      int KH, int KW, int stride, int pad, int dilation, float* col,
+                      ld_stream_t stream);
+int ld_mdeform_offset_mask_grad(const float* x, const float* om, const float* d_col, int N,
+                                int Cin, int Hin, int Win, int KH, int KW, int stride,
+                                int pad, int dilation, float* d_om, ld_stream_t stream);
+int ld_mdeform_col2im_index(const float* om, int N, int Cin, int Hin, int Win, int KH,
+                            int KW, int stride, int pad, int dilation, void* workspace,
+                            size_t workspace_bytes, ld_stream_t stream);
+
 /* ---- device input pipeline ---------------------
  * Resize(keep_ratio) -> flip -> Normalize(to_rgb) -> Pad -> collate of the
  * reference's train_pipeline (configs/ld/ld_r18_gflv1_r101_fpn_coco_1x.py:66-77,

@@ -100,11 +100,31 @@ def _strip_prefix(state_dict, prefix='module.'):
     return out
 
 
+def _rename_legacy_dcnv2(module, state_dict):
+    """The ``_offset`` -> ``conv_offset`` rename of every DCNv2 layer in
+    ``module`` (mmcv ModulatedDeformConv2dPack._load_from_state_dict, which
+    mmcv's loader calls with the whole dict).  The caller's dict is copied
+    only when a layer asks for it."""
+    from .cnn import ModulatedDeformConv2dPack
+    layers = [k for k, m in module.named_modules()
+              if isinstance(m, ModulatedDeformConv2dPack)]
+    if not layers:
+        return state_dict
+    meta = getattr(state_dict, '_metadata', None) or {}
+    out = OrderedDict(state_dict)
+    for name in layers:
+        version = meta.get(name, {}).get('version', None)
+        ModulatedDeformConv2dPack.rename_legacy_keys(
+            out, name + '.' if name else '', version)
+    return out
+
+
 def load_state_dict(module, state_dict, strict=False, logger=None):
     """mmcv.runner.load_state_dict: copy matching entries, REPORT (not raise,
     unless ``strict``) missing / unexpected / shape-mismatched keys.
     ``num_batches_tracked`` buffers are not counted as missing."""
     own = module.state_dict()
+    state_dict = _rename_legacy_dcnv2(module, state_dict)
     unexpected = [k for k in state_dict if k not in own]
     missing = [k for k in own
                if k not in state_dict and 'num_batches_tracked' not in k]

@@ -191,31 +191,19 @@ class GroupedConv2d(nn.Module):
                 f'padding={self.padding}, groups={self.groups}, bias=False')
 
 
-class DeformConv2dPack(nn.Module):
-    """mmcv.ops.DeformConv2dPack (conv type 'DCN'): deformable convolution v1
-    whose offsets come from its own ``conv_offset`` 3x3 conv (zero-initialised,
-    with bias).  Parameter names / shapes as mmcv's: ``weight`` (Cout, Cin, k,
-    k), no bias, ``conv_offset.weight`` (2*k*k*deform_groups, Cin, k, k),
-    ``conv_offset.bias``.  deform_groups = 1, no dilation.
+class _DeformConvPack(nn.Module):
+    """What DeformConv2dPack (DCNv1) and ModulatedDeformConv2dPack (DCNv2)
+    share: the parameters, the cached (Cout, Cin*k*k, 1, 1) weight views and
+    the three paths (frozen, trainable plain / conv + eval-BN pair, trainable
+    grouped as conv + BN pair).  A subclass names itself (``_NAME``, used in
+    every refusal), says how many ``conv_offset`` channels a tap takes
+    (``_TAP_CHANNELS``), checks its own constructor arguments
+    (``_check_args``) and supplies the sampling (``_sample`` without autograd,
+    ``_sample_fn`` differentiable)."""
 
-    Frozen or under ``torch.no_grad()`` (the R101-DCN teacher of config 4,
-    resnet.py:171-194): offset conv -> ld_deform_im2col -> 1x1 GEMM with the
-    fused epilogue, three launches, no autograd (``groups`` > 1: the grouped
-    GEMM of the X-101 teacher).
-
-    Trainable (``forward3`` / ``forward3_fused`` / ``forward3_bn`` with
-    autograd on and anything upstream or inside that needs a gradient;
-    configs/gfl/gfl_r101_fpn_dconv_c3-c5_mstrain_2x_coco.py): the offset conv is
-    a layers.ConvFn, the sampling a layers.DeformIm2colFn (offset gradient +
-    sorted, atomic-free data gradient, csrc/dcn.hip) and the product with
-    ``weight.view(Cout, Cin*k*k, 1, 1)`` the differentiable 1x1 conv
-    (layers.conv2d, or layers.conv_bn_act with the following eval-mode BN), so
-    the GEMM's dgrad / wgrad and the BN backward are the existing kernels.
-    ``groups`` > 1 (configs/imv2/gflv2_x101_fpn_2x_coco.py): the product is
-    layers.gconv2d over the Cin*k*k column channels followed by the BN node,
-    fp32 only and only as that conv + BN pair.  The input must exist in fp32
-    (not C8-only).  The 4-D
-    convenience ``forward`` stays inference-only."""
+    _NAME = 'DCN'
+    _TAP_CHANNELS = 2
+    _NOT_SQUARE = 'only square kernels/strides/pads'
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1,
                  padding=0, dilation=1, groups=1, deform_groups=1, bias=False,
@@ -224,25 +212,24 @@ class DeformConv2dPack(nn.Module):
         k, s, p, d = (_pair(kernel_size), _pair(stride), _pair(padding),
                       _pair(dilation))
         if k[0] != k[1] or s[0] != s[1] or p[0] != p[1] or d[0] != d[1]:
-            raise NotImplementedError('only square kernels/strides/pads')
-        if deform_groups != 1 or bias:
-            raise NotImplementedError(
-                'DCN: deform_groups = 1 and no bias (the configs/gfl/*dconv* '
-                'and configs/imv2/gflv2_x101* settings) are built')
+            raise NotImplementedError(self._NOT_SQUARE)
+        self._check_args(deform_groups, bias, groups)
         if groups != 1 and (in_channels % groups or out_channels % groups or
                             out_channels // groups not in (4, 8, 16, 32)):
             raise NotImplementedError(
-                f'grouped DCN {in_channels}->{out_channels} / {groups}')
+                f'grouped {self._NAME} {in_channels}->{out_channels} / '
+                f'{groups}')
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.padding, self.dilation = k, s, p, d
         self.groups, self.deform_groups = groups, deform_groups
         self.weight = nn.Parameter(
             torch.empty(out_channels, in_channels // groups, k[0], k[1]))
-        self.bias = None
-        self.conv_offset = Conv2d(in_channels, deform_groups * 2 * k[0] * k[1],
-                                  k[0], stride=s[0], padding=p[0], bias=True)
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.conv_offset = Conv2d(
+            in_channels, deform_groups * self._TAP_CHANNELS * k[0] * k[1],
+            k[0], stride=s[0], padding=p[0], bias=True)
         if d != (1, 1):
-            raise NotImplementedError('dilated DCN')
+            raise NotImplementedError(f'dilated {self._NAME}')
         self.reset_parameters()
         self._w2d = None
         self._w2d_train = None
@@ -252,6 +239,8 @@ class DeformConv2dPack(nn.Module):
         n = self.in_channels * self.kernel_size[0] * self.kernel_size[1]
         stdv = 1.0 / math.sqrt(n)
         nn.init.uniform_(self.weight, -stdv, stdv)
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
         nn.init.zeros_(self.conv_offset.weight)
         nn.init.zeros_(self.conv_offset.bias)
 
@@ -302,24 +291,33 @@ class DeformConv2dPack(nn.Module):
     def forward3_bn(self, x3, levels, bn=None, residual=None, relu=False):
         """The trainable path: relu?(BN_eval(dcn(x)) + residual), or the plain
         deformable conv with ``bn`` None.  Every piece is an autograd node."""
+        name = self._NAME
         if self.groups != 1 and bn is None:
             raise NotImplementedError(
-                'grouped DCN trains as the conv + BN pair of a ResNeXt '
+                f'grouped {name} trains as the conv + BN pair of a ResNeXt '
                 'Bottleneck only (forward3_bn with its norm layer)')
         if self.groups != 1 and Y.get_precision() == 'bf16':
             raise NotImplementedError(
-                'trainable grouped DCN is fp32 only (bf16 mode is not built)')
+                f'trainable grouped {name} is fp32 only (bf16 mode is not '
+                'built)')
         if self.deform_groups != 1 or self.dilation != (1, 1):
             raise NotImplementedError(
-                'trainable DCN: deform_groups = 1 and no dilation are built')
-        Y._fp32_readable(x3, 'trainable DCN input')
+                f'trainable {name}: deform_groups = 1 and no dilation are '
+                'built')
+        if self.bias is not None and bn is not None:
+            raise NotImplementedError(
+                f'{name} with a bias followed by a folded norm layer (bn)')
+        Y._fp32_readable(x3, f'trainable {name} input')
         if len(levels) != 1:
-            raise NotImplementedError('DCN on level-concatenated tensors')
+            raise NotImplementedError(
+                f'{name} on level-concatenated tensors')
+        if self.groups == 1 and bn is None and (residual is not None or relu):
+            raise NotImplementedError(f'{name} epilogue without a norm layer')
         (h, w), = levels
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
         co = self.conv_offset
         off3, out_levels = Y.conv2d(x3, co.weight, co.bias, s, p, levels)
-        col = Y.deform_im2col_fn(x3, off3, h, w, k, s, p)
+        col = self._sample_fn(x3, off3, h, w, k, s, p)
         w2 = self._weight_2d_train()
         if self.groups != 1:
             # grouped DCN (resnext.py:62-74): rows [g * cg * k * k, (g + 1) * cg
@@ -328,9 +326,7 @@ class DeformConv2dPack(nn.Module):
             y3, _ = Y.gconv2d(col, w2, self.groups, 1, 0, out_levels)
             return bn.forward3(y3, residual, relu), out_levels
         if bn is None:
-            if residual is not None or relu:
-                raise NotImplementedError('DCN epilogue without a norm layer')
-            return Y.conv2d(col, w2, None, 1, 0, out_levels)
+            return Y.conv2d(col, w2, self.bias, 1, 0, out_levels)
         return Y.conv_bn_act(col, w2, bn.weight, bn.bias, bn.running_mean,
                              bn.running_var, bn.eps, 1, 0, out_levels, residual,
                              relu)
@@ -344,12 +340,20 @@ class DeformConv2dPack(nn.Module):
             if scale is not None or shift is not None or \
                     residual is not None or relu:
                 raise NotImplementedError(
-                    'DeformConv2dPack.forward3_fused with a folded epilogue is '
-                    'inference-only: the trainable conv + BN pair is '
-                    'forward3_bn (resnet._conv_bn takes it)')
+                    f'{type(self).__name__}.forward3_fused with a folded '
+                    'epilogue is inference-only: the trainable conv + BN pair '
+                    'is forward3_bn (resnet._conv_bn takes it)')
             return self.forward3_bn(x3, levels)
         if len(levels) != 1:
-            raise NotImplementedError('DCN on level-concatenated tensors')
+            raise NotImplementedError(
+                f'{self._NAME} on level-concatenated tensors')
+        if self.bias is not None and (scale is not None or shift is not None):
+            raise NotImplementedError(
+                f'{self._NAME} with a bias and a folded norm layer (scale / '
+                'shift)')
+        if self.groups != 1 and residual is not None:
+            raise NotImplementedError(
+                f'grouped {self._NAME} with a fused residual')
         (h, w), = levels
         N, cin, P = x3.shape
         k, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
@@ -357,19 +361,17 @@ class DeformConv2dPack(nn.Module):
             x3, self.conv_offset.weight, s, p, levels,
             bias=self.conv_offset.bias)
         (ho, wo), = out_levels
-        col = Y.deform_im2col(x3, off3, h, w, k, s, p, 1)
+        col = self._sample(x3, off3, h, w, k, s, p)
         if self.groups != 1:
             # grouped DCN (ResNeXt-DCN, resnext.py:62-74): rows [g * cg * k * k,
             # (g + 1) * cg * k * k) of the column tensor feed group g -- a grouped
             # 1x1 conv over Cin * k * k channels
-            if residual is not None:
-                raise NotImplementedError('grouped DCN with a fused residual')
             y3, _ = Y.gconv_forward(col, self._weight_2d(), self.groups, 1, 0,
                                     ((ho, wo), ), scale, shift, relu)
             return y3, out_levels
         y3, _ = Y.conv_forward_raw(col, self._weight_2d(), 1, 0,
-                                   ((ho, wo), ), scale=scale, shift=shift,
-                                   residual=residual, relu=relu)
+                                   ((ho, wo), ), bias=self.bias, scale=scale,
+                                   shift=shift, residual=residual, relu=relu)
         return y3, out_levels
 
     def forward3(self, x3, levels):
@@ -379,12 +381,129 @@ class DeformConv2dPack(nn.Module):
         if torch.is_grad_enabled() and (x.requires_grad or
                                         self.weight.requires_grad):
             raise NotImplementedError(
-                'DeformConv2dPack.forward (4-D) is inference-only: call it '
-                'under torch.no_grad(); the trainable entry points are '
+                f'{type(self).__name__}.forward (4-D) is inference-only: call '
+                'it under torch.no_grad(); the trainable entry points are '
                 'forward3 / forward3_bn on (N, C, H*W) tensors')
         n, c, h, w = x.shape
         y3, lv = self.forward3(x.reshape(n, c, h * w), ((h, w), ))
         return y3.view(n, self.out_channels, lv[0][0], lv[0][1])
+
+
+class DeformConv2dPack(_DeformConvPack):
+    """mmcv.ops.DeformConv2dPack (conv type 'DCN'): deformable convolution v1
+    whose offsets come from its own ``conv_offset`` 3x3 conv (zero-initialised,
+    with bias).  Parameter names / shapes as mmcv's: ``weight`` (Cout, Cin, k,
+    k), no bias, ``conv_offset.weight`` (2*k*k*deform_groups, Cin, k, k),
+    ``conv_offset.bias``.  deform_groups = 1, no dilation.
+
+    Frozen or under ``torch.no_grad()`` (the R101-DCN teacher of config 4,
+    resnet.py:171-194): offset conv -> ld_deform_im2col -> 1x1 GEMM with the
+    fused epilogue, three launches, no autograd (``groups`` > 1: the grouped
+    GEMM of the X-101 teacher).
+
+    Trainable (``forward3`` / ``forward3_fused`` / ``forward3_bn`` with
+    autograd on and anything upstream or inside that needs a gradient;
+    configs/gfl/gfl_r101_fpn_dconv_c3-c5_mstrain_2x_coco.py): the offset conv is
+    a layers.ConvFn, the sampling a layers.DeformIm2colFn (offset gradient +
+    sorted, atomic-free data gradient, csrc/dcn.hip) and the product with
+    ``weight.view(Cout, Cin*k*k, 1, 1)`` the differentiable 1x1 conv
+    (layers.conv2d, or layers.conv_bn_act with the following eval-mode BN), so
+    the GEMM's dgrad / wgrad and the BN backward are the existing kernels.
+    ``groups`` > 1 (configs/imv2/gflv2_x101_fpn_2x_coco.py): the product is
+    layers.gconv2d over the Cin*k*k column channels followed by the BN node,
+    fp32 only and only as that conv + BN pair.  The input must exist in fp32
+    (not C8-only).  The 4-D
+    convenience ``forward`` stays inference-only."""
+
+    def _check_args(self, deform_groups, bias, groups):
+        if deform_groups != 1 or bias:
+            raise NotImplementedError(
+                'DCN: deform_groups = 1 and no bias (the configs/gfl/*dconv* '
+                'and configs/imv2/gflv2_x101* settings) are built')
+
+    def _sample(self, x3, off3, h, w, k, s, p):
+        return Y.deform_im2col(x3, off3, h, w, k, s, p, 1)
+
+    def _sample_fn(self, x3, off3, h, w, k, s, p):
+        return Y.deform_im2col_fn(x3, off3, h, w, k, s, p)
+
+
+class ModulatedDeformConv2dPack(_DeformConvPack):
+    """mmcv.ops.ModulatedDeformConv2dPack (conv type 'DCNv2'): deformable
+    convolution v2, DeformConv2dPack with a modulation mask.  ``conv_offset``
+    has 3*k*k channels: [0, 2*k*k) the offsets, (dy, dx) interleaved per tap as
+    in v1, [2*k*k, 3*k*k) the mask logits (mmcv: ``o1, o2, mask = chunk(out,
+    3, 1); offset = cat(o1, o2); mask = sigmoid(mask)``); the sample of tap t
+    is sigmoid(logit_t) times v1's bilinear sum, so the zero-initialised layer
+    is 0.5 x the plain convolution.  Parity with mmcv itself is UNPINNED (the
+    op is not in the reference checkout; tests/_mdcn_ref64.py restates it).
+
+    Parameter names / shapes as mmcv's: ``weight`` (Cout, Cin/groups, k, k),
+    an optional ``bias`` (Cout) (mmcv's class default is bias=True; ResNet and
+    ConvModule pass False), ``conv_offset.weight`` (3*k*k, Cin, k, k),
+    ``conv_offset.bias``.  A checkpoint from before mmcv's module version 2
+    carries ``<name>_offset.weight / .bias``; they load into ``conv_offset``.
+
+    The three paths are DeformConv2dPack's with the sampling replaced by
+    ld_mdeform_im2col / layers.ModulatedDeformIm2colFn (csrc/dcn.hip): frozen or
+    ``no_grad`` in three launches (``groups`` > 1 through gconv_forward),
+    trainable plain or as conv + eval-BN pair, trainable grouped as conv + BN
+    pair in fp32.  ``bias`` is added by the 1x1 GEMM on the paths without a
+    folded norm; together with ``bn`` / ``scale`` / ``shift``, or with
+    ``groups`` > 1, it is refused by name.  deform_groups = 1, no dilation."""
+
+    _NAME = 'DCNv2'
+    _TAP_CHANNELS = 3
+    _NOT_SQUARE = 'DCNv2: only square kernels/strides/pads'
+    _version = 2
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1,
+                 padding=0, dilation=1, groups=1, deform_groups=1, bias=True,
+                 **kwargs):
+        super().__init__(in_channels, out_channels, kernel_size, stride,
+                         padding, dilation, groups, deform_groups, bias,
+                         **kwargs)
+
+    def _check_args(self, deform_groups, bias, groups):
+        if deform_groups != 1:
+            raise NotImplementedError(
+                f'DCNv2: deform_groups = {deform_groups} is not built '
+                '(deform_groups = 1 is)')
+        if bias and groups != 1:
+            raise NotImplementedError(
+                'grouped DCNv2 with a bias (the grouped GEMM has no bias '
+                'operand; ResNeXt passes bias=False)')
+
+    def _sample(self, x3, om3, h, w, k, s, p):
+        return Y.mdeform_im2col(x3, om3, h, w, k, s, p, 1)
+
+    def _sample_fn(self, x3, om3, h, w, k, s, p):
+        return Y.mdeform_im2col_fn(x3, om3, h, w, k, s, p)
+
+    @staticmethod
+    def rename_legacy_keys(state_dict, prefix, version):
+        """mmcv's version-2 rename, in place: a checkpoint without a module
+        version, or with one below 2, carries the offset conv as ``<prefix
+        minus its trailing dot>_offset.weight / .bias``."""
+        if version is None or version < 2:
+            for leaf in ('weight', 'bias'):
+                old = prefix[:-1] + '_offset.' + leaf
+                new = prefix + 'conv_offset.' + leaf
+                if new not in state_dict and old in state_dict:
+                    state_dict[new] = state_dict.pop(old)
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata,
+                              strict, missing_keys, unexpected_keys,
+                              error_msgs):
+        # nn.Module.load_state_dict hands a nested module only the keys under
+        # its own prefix, so this serves a layer loaded on its own (as mmcv's
+        # loader, which passes the whole dict, serves every depth);
+        # checkpoint.load_state_dict applies the same rename at every depth
+        self.rename_legacy_keys(state_dict, prefix,
+                                local_metadata.get('version', None))
+        super()._load_from_state_dict(state_dict, prefix, local_metadata,
+                                      strict, missing_keys, unexpected_keys,
+                                      error_msgs)
 
 
 def train_bn_refusals(conv, bn):
@@ -394,11 +513,11 @@ def train_bn_refusals(conv, bn):
     coefficients (``forward3_bn``), which batch statistics cannot take."""
     if not (isinstance(bn, BatchNorm2d) and bn.training):
         return
-    if isinstance(conv, DeformConv2dPack):
+    if isinstance(conv, _DeformConvPack):
         raise NotImplementedError(
             'BatchNorm2d in training mode (batch statistics) after a '
-            'DeformConv2dPack is not implemented: keep the norm layers of DCN '
-            'blocks in eval mode (norm_eval=True)')
+            f'{type(conv).__name__} is not implemented: keep the norm layers '
+            f'of {conv._NAME} blocks in eval mode (norm_eval=True)')
     Y.bn_train_check(bn.momentum)
 
 
@@ -481,9 +600,13 @@ def build_conv_layer(cfg, *args, **kwargs):
         kw = {k: v for k, v in cfg.items() if k != 'type'}
         kw.update(kwargs)
         return DeformConv2dPack(*args, **kw)
+    if layer_type == 'DCNv2':
+        kw = {k: v for k, v in cfg.items() if k != 'type'}
+        kw.update(kwargs)
+        return ModulatedDeformConv2dPack(*args, **kw)
     raise NotImplementedError(
         f'conv layer type {layer_type} is not implemented on the MI355X path '
-        '(DCNv2 / grouped convs are outside SURVEY.md section 8)')
+        "(built: 'Conv2d' / 'Conv', 'DCN', 'DCNv2')")
 
 
 def build_norm_layer(cfg, num_features, postfix=''):

@@ -48,11 +48,41 @@
 //     sort, segment starts) is shared by all Cin channels and built once per
 //     call.  All buffers come from the caller's workspace; every launch, the
 //     sort's included, goes to the stream argument.
+//
+// Modulated deformable convolution, DCNv2 (mmcv.ops.ModulatedDeformConv2dPack,
+// conv type 'DCNv2', deform_groups = 1; Zhu et al. 2019, "Deformable ConvNets
+// v2: More Deformable, Better Results"; mmcv/ops/csrc
+// modulated_deform_conv_cuda_kernel.cuh).  mmcv is not in the reference
+// checkout either, so the semantics are restated here:
+//   om = conv_offset(x), 3*KH*KW channels (zero-initialised conv, with bias)
+//   mmcv: o1, o2, mask = chunk(om, 3, 1); offset = cat(o1, o2); mask = sigmoid(mask)
+//   => channels [0, 2*KH*KW) of om are the offsets, (dy, dx) interleaved per tap
+//      exactly as in v1; channels [2*KH*KW, 3*KH*KW) are the mask logits, one
+//      per tap
+//   col[n][ci*KH*KW + t][p] = m_t(p) * (w1*x1 + w2*x2 + w3*x3 + w4*x4),
+//      m = sigmoidf_(logit) (ld_math.h); the four terms, the window, the floor
+//      and the zero corners are v1's, in v1's order; the mask multiplies the
+//      finished sum (so om = 0 gives exactly 0.5 x v1's column tensor)
+//   d_logit_t(p) = m (1 - m) * sum_ci d_col * (four-term sum)   (0 outside)
+//   d_offset = v1's expression times m;  d_x = v1's scatter, corner weights times m
+// Parity status: UNPINNED against mmcv; checked against tests/_mdcn_ref64.py
+// (float64, autograd) built on tests/_dcn_ref64.py.
+// The kernels read the offset and logit planes straight from om (no offset /
+// mask tensor is materialised) and share Corners / deform_corners with v1.  The
+// data gradient stores corner weight * m into the v1 workspace (same layout:
+// ld_deform_col2im_workspace_bytes and ld_deform_col2im_sum serve it unchanged),
+// so it stays atomic-free and bit-reproducible.  HBM-bound like v1, one more
+// plane read per tap.  Measured once on an MI355X against the v1 calls of the
+// same shape (R101 c3-c5 conv2 at 2 x 800 x 1344, HIP events, alternating in one
+// process; tools/bench_mdcn.py -> profiles/mdcn_latency.json): im2col 0.72-0.96 x,
+// offset + mask gradient 1.00-1.03 x, index + sum 1.00-1.01 x the v1 call; at
+// 16 % of the HBM rate or less these calls are paced by launch and latency.
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
 
 #include "ld_launch.h"
+#include "ld_math.h"
 
 #include "../../include/ld_hip.h"
 
@@ -342,6 +372,118 @@ int col2im_layout(int N, int Cin, int Hin, int Win, int KH, int KW, int stride, 
   return 0;
 }
 
+// ---- DCNv2: the same three pieces with the modulation mask --------------------
+// om (N, 3*KK, Pout): planes [0, 2*KK) the offsets as v1's, planes [2*KK, 3*KK)
+// the mask logits.  deform_corners only needs the image's first offset plane, so
+// it takes om's image base as it is.
+__device__ __forceinline__ float mdeform_mask(const float* __restrict__ omn, int Pout, int p,
+                                              int k, int ntaps) {
+  return ld::sigmoidf_(omn[(size_t)(2 * ntaps + k) * Pout + p]);
+}
+
+// The four-term expression c1 x1 + c2 x2 + c3 x3 + c4 x4 with the rounding the v1
+// kernels have as compiled (-ffp-contract=fast: c2 x2 rounded, then terms 1, 3, 4
+// by fused multiply-add), spelled out so that the bits depend neither on how a
+// channel loop is unrolled nor on which terms a vectoriser pairs: with a mask of
+// exactly 0.5 every DCNv2 result is then exactly half of v1's.
+__device__ __forceinline__ float four_terms(float c1, float x1, float c2, float x2, float c3,
+                                            float x3, float c4, float x4) {
+  return fmaf(c4, x4, fmaf(c3, x3, fmaf(c1, x1, c2 * x2)));
+}
+
+// Thread = (n, tap, position) as deform_im2col_kernel; col = m * (four-term sum).
+__global__ __launch_bounds__(256) void mdeform_im2col_kernel(
+    const float* __restrict__ x, const float* __restrict__ om, int Cin, int Hin, int Win,
+    int Hout, int Wout, int KH, int KW, int stride, int pad, int dil,
+    float* __restrict__ col) {
+  const int Pout = Hout * Wout, Pin = Hin * Win, ntaps = KH * KW;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int k = blockIdx.y, n = blockIdx.z;
+  if (p >= Pout) return;
+  const float* omn = om + (size_t)n * 3 * ntaps * Pout;
+  const Corners c = deform_corners(omn, Pout, p, k, Hin, Win, Wout, KW, stride, pad, dil);
+  const float m = mdeform_mask(omn, Pout, p, k, ntaps);
+  const float w1 = c.w[0], w2 = c.w[1], w3 = c.w[2], w4 = c.w[3];
+  const int o1 = c.o[0], o2 = c.o[1], o3 = c.o[2], o4 = c.o[3];
+  const float* xn = x + (size_t)n * Cin * Pin;
+  float* cn = col + ((size_t)n * Cin * ntaps + k) * Pout + p;
+  const size_t cstep = (size_t)ntaps * Pout;
+#pragma unroll 4
+  for (int ci = 0; ci < Cin; ++ci) {
+    const float* xc = xn + (size_t)ci * Pin;
+    // v1's expression, then the mask on the finished sum
+    const float v = four_terms(w1, xc[o1], w2, xc[o2], w3, xc[o3], w4, xc[o4]);
+    cn[(size_t)ci * cstep] = m * v;
+  }
+}
+
+// d_om: planes 2k, 2k + 1 = m * v1's two offset sums; plane 2*KK + k = m (1 - m) *
+// sum_ci d_col * (four-term sum).  The three sums stay in registers over the
+// channel loop; the mask factors are applied at the store.  Thread = (n, tap,
+// position) writes its three elements: one writer each, every element written.
+__global__ __launch_bounds__(256) void mdeform_offset_mask_grad_kernel(
+    const float* __restrict__ x, const float* __restrict__ om,
+    const float* __restrict__ dcol, int Cin, int Hin, int Win, int Hout, int Wout, int KH,
+    int KW, int stride, int pad, int dil, float* __restrict__ dom) {
+  const int Pout = Hout * Wout, Pin = Hin * Win, ntaps = KH * KW;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int k = blockIdx.y, n = blockIdx.z;
+  if (p >= Pout) return;
+  const float* omn = om + (size_t)n * 3 * ntaps * Pout;
+  const Corners c = deform_corners(omn, Pout, p, k, Hin, Win, Wout, KW, stride, pad, dil);
+  const float m = mdeform_mask(omn, Pout, p, k, ntaps);
+  const float uh = 1.0f - c.lh, uw = 1.0f - c.lw;
+  const float h1 = c.ok[0] ? -uw : 0.0f, h2 = c.ok[1] ? -c.lw : 0.0f;
+  const float h3 = c.ok[2] ? uw : 0.0f, h4 = c.ok[3] ? c.lw : 0.0f;
+  const float v1 = c.ok[0] ? -uh : 0.0f, v2 = c.ok[1] ? uh : 0.0f;
+  const float v3 = c.ok[2] ? -c.lh : 0.0f, v4 = c.ok[3] ? c.lh : 0.0f;
+  const float* xn = x + (size_t)n * Cin * Pin;
+  const float* gn = dcol + ((size_t)n * Cin * ntaps + k) * Pout + p;
+  const size_t cstep = (size_t)ntaps * Pout;
+  float ah = 0.0f, aw = 0.0f, am = 0.0f;
+#pragma unroll 4
+  for (int ci = 0; ci < Cin; ++ci) {
+    const float* xc = xn + (size_t)ci * Pin;
+    const float g = gn[(size_t)ci * cstep];
+    const float x1 = xc[c.o[0]], x2 = xc[c.o[1]], x3 = xc[c.o[2]], x4 = xc[c.o[3]];
+    ah = fmaf(g, four_terms(h1, x1, h2, x2, h3, x3, h4, x4), ah);
+    aw = fmaf(g, four_terms(v1, x1, v2, x2, v3, x3, v4, x4), aw);
+    am = fmaf(g, four_terms(c.w[0], x1, c.w[1], x2, c.w[2], x3, c.w[3], x4), am);
+  }
+  float* dn = dom + (size_t)n * 3 * ntaps * Pout;
+  dn[(size_t)(2 * k) * Pout + p] = m * ah;
+  dn[(size_t)(2 * k + 1) * Pout + p] = m * aw;
+  dn[(size_t)(2 * ntaps + k) * Pout + p] = m * (1.0f - m) * am;
+}
+
+// deform_entries_kernel with the corner weights stored as weight * m: keys, entry
+// ids and the workspace layout are v1's, so the sort, the segments and
+// ld_deform_col2im_sum run on it unchanged.
+__global__ __launch_bounds__(256) void mdeform_entries_kernel(
+    const float* __restrict__ om, int Hin, int Win, int Hout, int Wout, int KH, int KW,
+    int stride, int pad, int dil, unsigned NC, unsigned* __restrict__ keys,
+    unsigned* __restrict__ vals, float* __restrict__ wq) {
+  const int Pout = Hout * Wout, Pin = Hin * Win, ntaps = KH * KW;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const int k = blockIdx.y, n = blockIdx.z;
+  if (p >= Pout) return;
+  const float* omn = om + (size_t)n * 3 * ntaps * Pout;
+  const Corners c = deform_corners(omn, Pout, p, k, Hin, Win, Wout, KW, stride, pad, dil);
+  const float m = mdeform_mask(omn, Pout, p, k, ntaps);
+  const unsigned e = (unsigned)(((size_t)n * ntaps + k) * Pout + p) * 4u;
+  uint4 kk, vv;
+  const unsigned base = (unsigned)n * (unsigned)Pin;
+  kk.x = c.ok[0] ? base + (unsigned)c.o[0] : NC;
+  kk.y = c.ok[1] ? base + (unsigned)c.o[1] : NC;
+  kk.z = c.ok[2] ? base + (unsigned)c.o[2] : NC;
+  kk.w = c.ok[3] ? base + (unsigned)c.o[3] : NC;
+  vv.x = e; vv.y = e + 1; vv.z = e + 2; vv.w = e + 3;
+  *reinterpret_cast<uint4*>(keys + e) = kk;
+  *reinterpret_cast<uint4*>(vals + e) = vv;
+  *reinterpret_cast<float4*>(wq + e) =
+      make_float4(c.w[0] * m, c.w[1] * m, c.w[2] * m, c.w[3] * m);
+}
+
 }  // namespace
 
 extern "C" int ld_deform_im2col(const float* x, const float* offset, int N, int Cin,
@@ -437,5 +579,66 @@ extern "C" int ld_deform_col2im_sum(const float* d_col, int N, int Cin, int Hin,
   LD_LAUNCH(deform_col2im_fixup_kernel, dim3((L.NC + 3) / 4, (Cin + 63) / 64), dim3(256), 0,
             st, (const unsigned*)(ws + L.start), (const float*)(ws + L.partial), L.NC, Cin,
             Pin, d_x);
+  return (int)hipGetLastError();
+}
+
+// ---- DCNv2 entry points ----------------------------------------------------------
+extern "C" int ld_mdeform_im2col(const float* x, const float* om, int N, int Cin, int Hin,
+                                 int Win, int KH, int KW, int stride, int pad, int dilation,
+                                 float* col, ld_stream_t stream) {
+  Col2imWs L;
+  if (!x || !om || !col ||
+      col2im_layout(N, Cin, Hin, Win, KH, KW, stride, pad, dilation, false, &L) != 0)
+    return LD_EINVAL;
+  const int Pout = L.Hout * L.Wout;
+  LD_LAUNCH(mdeform_im2col_kernel, dim3((Pout + 255) / 256, KH * KW, N), dim3(256), 0,
+            (hipStream_t)stream, x, om, Cin, Hin, Win, L.Hout, L.Wout, KH, KW, stride, pad,
+            dilation, col);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_mdeform_offset_mask_grad(const float* x, const float* om,
+                                           const float* d_col, int N, int Cin, int Hin,
+                                           int Win, int KH, int KW, int stride, int pad,
+                                           int dilation, float* d_om, ld_stream_t stream) {
+  Col2imWs L;
+  if (!x || !om || !d_col || !d_om ||
+      col2im_layout(N, Cin, Hin, Win, KH, KW, stride, pad, dilation, false, &L) != 0)
+    return LD_EINVAL;
+  const int Pout = L.Hout * L.Wout;
+  LD_LAUNCH(mdeform_offset_mask_grad_kernel, dim3((Pout + 255) / 256, KH * KW, N),
+            dim3(256), 0, (hipStream_t)stream, x, om, d_col, Cin, Hin, Win, L.Hout, L.Wout,
+            KH, KW, stride, pad, dilation, d_om);
+  return (int)hipGetLastError();
+}
+
+// The workspace is ld_deform_col2im_workspace_bytes'; ld_deform_col2im_sum reads it.
+extern "C" int ld_mdeform_col2im_index(const float* om, int N, int Cin, int Hin, int Win,
+                                       int KH, int KW, int stride, int pad, int dilation,
+                                       void* workspace, size_t workspace_bytes,
+                                       ld_stream_t stream) {
+  Col2imWs L;
+  if (!om || !workspace) return LD_EINVAL;
+  const int rc = col2im_layout(N, Cin, Hin, Win, KH, KW, stride, pad, dilation, true, &L);
+  if (rc != 0) return rc > 0 ? rc : LD_EINVAL;
+  if (workspace_bytes < L.total) return LD_ENOSPACE;
+  char* ws = (char*)workspace;
+  unsigned* keys = (unsigned*)(ws + L.keys);
+  unsigned* skeys = (unsigned*)(ws + L.skeys);
+  unsigned* vals = (unsigned*)(ws + L.vals);
+  unsigned* svals = (unsigned*)(ws + L.svals);
+  const int Pout = L.Hout * L.Wout;
+  hipStream_t st = (hipStream_t)stream;
+  LD_LAUNCH(mdeform_entries_kernel, dim3((Pout + 255) / 256, KH * KW, N), dim3(256), 0, st,
+            om, Hin, Win, L.Hout, L.Wout, KH, KW, stride, pad, dilation, L.NC, keys, vals,
+            (float*)(ws + L.wq));
+  size_t bytes = L.sort_bytes;
+  // stable: entries of one cell stay in entry-id order
+  const hipError_t e = hipcub::DeviceRadixSort::SortPairs(
+      (void*)(ws + L.sort), bytes, (const unsigned*)keys, skeys, (const unsigned*)vals, svals,
+      L.E, 0, L.end_bit, st);
+  if (e != hipSuccess) return (int)e;
+  LD_LAUNCH(deform_segments_kernel, dim3(L.NC / 256 + 1), dim3(256), 0, st,
+            (const unsigned*)skeys, L.E, L.NC, (unsigned*)(ws + L.start));
   return (int)hipGetLastError();
 }

@@ -2776,6 +2776,112 @@ def deform_im2col_fn(x3, off3, h, w, k, stride, pad):
     return deform_im2col(x3, off3, h, w, k, stride, pad, 1)
 
 
+def _mdeform_shapes(x3, om3, h, w, k, stride, pad, what):
+    N, cin, P = x3.shape
+    ho, wo = out_size(h, k, stride, pad), out_size(w, k, stride, pad)
+    if P != h * w or om3.shape != (N, 3 * k * k, ho * wo):
+        raise L.LdError(f'{what}: shape mismatch')
+    return N, cin, ho * wo
+
+
+def mdeform_im2col(x3, om3, h, w, k, stride, pad, dilation):
+    """DCNv2 sampling: (N, Cin, H*W) + the conv_offset output ``om3`` (N,
+    3*k*k, Hout*Wout) -- offsets in channels [0, 2*k*k) as deform_im2col's,
+    mask logits in [2*k*k, 3*k*k) -- -> column tensor (N, Cin*k*k, Hout*Wout)
+    with the sigmoid mask applied, no autograd (ld_mdeform_im2col; the
+    differentiable form is mdeform_im2col_fn)."""
+    _dev_f32(x3, 'dcnv2 input')
+    _dev_f32(om3, 'dcnv2 offset/mask')
+    lib = L.get_lib()
+    N, cin, po = _mdeform_shapes(x3, om3, h, w, k, stride, pad,
+                                 'mdeform_im2col')
+    col = torch.empty((N, cin * k * k, po), dtype=torch.float32,
+                      device=x3.device)
+    L.check(lib.ld_mdeform_im2col(L.ptr(x3), L.ptr(om3), N, cin, h, w, k, k,
+                                  stride, pad, dilation, L.ptr(col),
+                                  L.stream_ptr(x3.device)),
+            'ld_mdeform_im2col')
+    return col
+
+
+def mdeform_col2im_index(om3, cin, h, w, k, stride, pad, dilation=1):
+    """deform_col2im_index for DCNv2: the same workspace with the corner
+    weights times the mask (ld_mdeform_col2im_index); deform_col2im_sum then
+    gives d_x."""
+    lib = L.get_lib()
+    _dev_f32(om3, 'dcnv2 offset/mask')
+    N = om3.shape[0]
+    ho, wo = out_size(h, k, stride, pad), out_size(w, k, stride, pad)
+    if om3.shape != (N, 3 * k * k, ho * wo):
+        raise L.LdError('mdeform_col2im_index: shape mismatch')
+    geo = (N, cin, h, w, k, k, stride, pad, dilation)
+    need = lib.ld_deform_col2im_workspace_bytes(*geo)
+    if not need:
+        raise L.LdError(f'mdeform_col2im: unsupported geometry {geo}')
+    ws = torch.empty(need, dtype=torch.uint8, device=om3.device)
+    L.check(lib.ld_mdeform_col2im_index(L.ptr(om3), *geo, L.ptr(ws), need,
+                                        L.stream_ptr(om3.device)),
+            'ld_mdeform_col2im_index')
+    return ws
+
+
+def mdeform_offset_mask_grad(x3, om3, dcol, h, w, k, stride, pad, dilation=1):
+    """d_om (N, 3*k*k, Hout*Wout): the offset and the mask-logit gradients of
+    the DCNv2 sampling in one launch (ld_mdeform_offset_mask_grad)."""
+    lib = L.get_lib()
+    _dev_f32(x3, 'dcnv2 input')
+    _dev_f32(om3, 'dcnv2 offset/mask')
+    _dev_f32(dcol, 'dcnv2 column gradient')
+    N, cin, po = _mdeform_shapes(x3, om3, h, w, k, stride, pad,
+                                 'mdeform_offset_mask_grad')
+    if dcol.shape != (N, cin * k * k, po):
+        raise L.LdError('mdeform_offset_mask_grad: shape mismatch')
+    dom = torch.empty_like(om3)
+    L.check(lib.ld_mdeform_offset_mask_grad(
+        L.ptr(x3), L.ptr(om3), L.ptr(dcol), N, cin, h, w, k, k, stride, pad,
+        dilation, L.ptr(dom), L.stream_ptr(x3.device)),
+        'ld_mdeform_offset_mask_grad')
+    return dom
+
+
+class ModulatedDeformIm2colFn(torch.autograd.Function):
+    """col = modulated deformable im2col(x, om) of DCNv2 (deform_groups = 1,
+    fp32).  backward: offset and mask-logit gradients in one launch, the data
+    gradient as DeformIm2colFn's sort + per-cell sum with the mask folded into
+    the corner weights (csrc/dcn.hip; no float atomics, bitwise reproducible).
+    ``x3`` also feeds the layer's conv_offset: fan protocol as DeformIm2colFn."""
+
+    @staticmethod
+    def forward(ctx, x3, om3, h, w, k, stride, pad):
+        col = mdeform_im2col(x3, om3, h, w, k, stride, pad, 1)
+        ctx.save_for_backward(x3, om3)
+        ctx.geo = (h, w, k, stride, pad)
+        ctx.fan = fan_in(ctx, 0, x3)
+        return col
+
+    @staticmethod
+    def backward(ctx, dcol):
+        x3, om3 = ctx.saved_tensors
+        dcol = dcol.contiguous()
+        _dev_f32(dcol, 'dcnv2 column gradient')
+        cin = x3.shape[1]
+        dx = dom = None
+        if ctx.needs_input_grad[1]:
+            dom = mdeform_offset_mask_grad(x3, om3, dcol, *ctx.geo)
+        if ctx.needs_input_grad[0]:
+            ws = mdeform_col2im_index(om3, cin, *ctx.geo)
+            dx = deform_col2im_sum(dcol, ws, cin, *ctx.geo)
+            dx._ld_fresh = True
+        return fan_give(ctx.fan, dx), dom, None, None, None, None, None
+
+
+def mdeform_im2col_fn(x3, om3, h, w, k, stride, pad):
+    """Differentiable mdeform_im2col (dilation 1)."""
+    if torch.is_grad_enabled() and (x3.requires_grad or om3.requires_grad):
+        return ModulatedDeformIm2colFn.apply(x3, om3, h, w, k, stride, pad)
+    return mdeform_im2col(x3, om3, h, w, k, stride, pad, 1)
+
+
 def _gconv_xform(lib, w, groups, img, backward):
     cout, cin_g, k, _ = w.shape
     fn, what = (lib.ld_gconv_weight_transform_bwd,

@@ -260,7 +260,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -312,6 +312,10 @@ SIGNATURES = {
     'ld_deform_col2im_index': (C.c_int, [_vp] + [_i32] * 9 + [_vp, _sz, _vp]),
     'ld_deform_col2im_sum': (C.c_int, [_vp] + [_i32] * 9 +
                              [_vp, _sz, _vp, _vp]),
+    'ld_mdeform_im2col': (C.c_int, [_vp, _vp] + [_i32] * 9 + [_vp, _vp]),
+    'ld_mdeform_offset_mask_grad': (C.c_int, [_vp, _vp, _vp] + [_i32] * 9 +
+                                    [_vp, _vp]),
+    'ld_mdeform_col2im_index': (C.c_int, [_vp] + [_i32] * 9 + [_vp, _sz, _vp]),
     'ld_quality_forward': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp]),
     'ld_quality_backward_workspace_bytes': (_sz, [_i32, _i32]),

@@ -100,6 +100,19 @@ def gfl_dcn_detector(depth=101):
     return cfg
 
 
+def gfl_dcnv2_detector(depth=101):
+    """gfl_dcn_detector with the modulated op: DCNv2
+    (``dcn=dict(type='DCNv2', ...)``, how mmdet spells the stronger deformable
+    backbone, e.g. configs/fcos/fcos_center-normbbox-centeronreg-giou_r50_
+    caffe_fpn_gn-head_dcn_1x_coco.py) in the conv2 of every c3-c5 Bottleneck,
+    trainable.  The reference ships no GFL file with it; this is the
+    composition (parity with mmcv's op unpinned)."""
+    cfg = gfl_dcn_detector(depth)
+    cfg['backbone']['dcn'] = dict(type='DCNv2', deform_groups=1,
+                                  fallback_on_stride=False)
+    return cfg
+
+
 def gfl_x101_detector():
     """configs/gfl/gfl_x101_32x4d_fpn_mstrain_2x_coco.py: GFL on a trainable
     ResNeXt-101 32x4d (33 grouped 3x3 convs, 30 of them past the frozen
@@ -375,6 +388,19 @@ def ld_r101_dcn_detector(loss_im_weight=0.0):
                       with_vlr_kd=False)
     cfg['teacher_config']['model']['backbone'].update(
         dcn=dict(type='DCN', deform_groups=1, fallback_on_stride=False),
+        stage_with_dcn=(False, True, True, True))
+    return cfg
+
+
+def ld_r101_dcnv2_detector(loss_im_weight=0.0, student_depth=101,
+                           teacher_depth=101):
+    """ld_r101_dcn_detector (BASELINE config 4's pair) with a DCNv2 teacher:
+    the frozen teacher is gfl_dcnv2_detector's network.  ``student_depth`` /
+    ``teacher_depth`` give the smaller forms of the same pair."""
+    cfg = ld_detector(student_depth, teacher_depth,
+                      loss_im_weight=loss_im_weight, with_vlr_kd=False)
+    cfg['teacher_config']['model']['backbone'].update(
+        dcn=dict(type='DCNv2', deform_groups=1, fallback_on_stride=False),
         stage_with_dcn=(False, True, True, True))
     return cfg
 

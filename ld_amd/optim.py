@@ -118,7 +118,7 @@ def classify(model, paramwise_cfg):
     norms, convs = _norm_types(), _conv_types()
     seen, names, mults = set(), [], []
     for prefix, module in model.named_modules():
-        if cfg and isinstance(module, cnn.DeformConv2dPack) and \
+        if cfg and isinstance(module, cnn._DeformConvPack) and \
                 any(p.requires_grad for p in module.parameters()):
             # mmcv's dcn rules (no bias_lr_mult / bias_decay_mult under a DCN,
             # dcn_offset_lr_mult) touch trainable parameters only; a frozen
