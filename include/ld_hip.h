@@ -1299,6 +1299,42 @@ int ld_preprocess_batch(const ld_image_t* imgs, int N, int Hpad, int Wpad,
                         const float* mean, const float* std_inv, int to_rgb,
                         float* out, ld_stream_t stream);
 
+/* ---- train-time augmentation in the same launch ----------------------------
+ * Expand -> MinIoURandomCrop -> Resize -> RandomCrop -> RandomFlip -> Normalize
+ * -> Pad (datasets/pipelines/transforms.py:916-1000, 1008-1140, 203-233,
+ * 588-760, 416-450, 476-540) for a whole batch in one launch, with no
+ * intermediate image.  Per image, all host decisions (ld_amd/pipeline.py):
+ *   canvas  (canvas_h, canvas_w): Expand's canvas; the decoded image sits at
+ *           (img_top, img_left), everything else is fill[c] (uint8, in the
+ *           decoded image's BGR channel order).  No Expand: the image itself.
+ *   window  (win_y, win_x, win_h, win_w) in canvas coordinates: what the resize
+ *           reads (MinIoURandomCrop's patch; the whole canvas without it).
+ *   resize  the window -> (new_h, new_w), the bilinear of ld_preprocess_batch
+ *           with scale = win / new and source indices clamped to the WINDOW.
+ *   crop    (crop_y, crop_x, out_h, out_w) in resized coordinates (RandomCrop);
+ *           crop_y + out_h <= new_h, crop_x + out_w <= new_w.
+ *   flip    horizontal, within the crop.
+ * out (N, 3, Hpad, Wpad) fp32; outside (out_h, out_w) channel c holds
+ * pad_val[c] as it is (Pad comes after Normalize).  mean / std_inv / pad_val are
+ * HOST float[3] in output-channel order.  A descriptor with no canvas, the
+ * full window, no crop and pad_val 0 gives ld_preprocess_batch's bits.
+ * LD_EINVAL for a null pointer or a non-positive size; the descriptors are on
+ * the device and are not inspected. */
+typedef struct {
+  const unsigned char* data;
+  int32_t src_h, src_w;
+  int32_t canvas_h, canvas_w, img_top, img_left;
+  int32_t win_y, win_x, win_h, win_w;
+  int32_t new_h, new_w;
+  int32_t crop_y, crop_x, out_h, out_w;
+  int32_t flip;
+  unsigned char fill[4]; /* fill[0..2] = B, G, R; fill[3] unused */
+} ld_image_aug_t;
+int ld_preprocess_batch_aug(const ld_image_aug_t* imgs, int N, int Hpad, int Wpad,
+                            const float* mean, const float* std_inv,
+                            const float* pad_val, int to_rgb, float* out,
+                            ld_stream_t stream);
+
 /* ---- baseline JPEG decode, host half (LoadImageFromFile -> mmcv.imfrombytes ->
  * cv2.imdecode, datasets/pipelines/loading.py:12-71) -------------------------
  * The serial half of a JPEG decode: bytes -> int16 coefficient blocks, the input

@@ -89,7 +89,75 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   }
 }
 
+// The train-time augmentations in the same launch (ld_hip.h, ld_image_aug_t):
+// every output pixel walks back through crop -> resize -> window -> canvas to
+// at most four source bytes per channel; nothing intermediate is stored.
+// Same 64 x 4 mapping: a wavefront writes 64 consecutive floats of one row per
+// plane, and reads a contiguous (scale x 192 byte) run of one source row.
+__global__ __launch_bounds__(256) void preprocess_aug_kernel(
+    const ld_image_aug_t* __restrict__ imgs, int Hpad, int Wpad, float mean0,
+    float mean1, float mean2, float inv0, float inv1, float inv2, float pad0,
+    float pad1, float pad2, int to_rgb, float* __restrict__ out) {
+  const int n = blockIdx.z;
+  const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+  if (x >= Wpad || y >= Hpad) return;
+  const ld_image_aug_t im = imgs[n];
+  const size_t plane = (size_t)Hpad * Wpad;
+  float* o = out + (size_t)n * 3 * plane + (size_t)y * Wpad + x;
+  if (y >= im.out_h || x >= im.out_w) {  // Pad(size / size_divisor, pad_val)
+    o[0] = pad0;
+    o[plane] = pad1;
+    o[2 * plane] = pad2;
+    return;
+  }
+  // flip within the crop, then the crop offset: resized coordinates
+  const int xr = (im.flip ? im.out_w - 1 - x : x) + im.crop_x;
+  const int yr = y + im.crop_y;
+  int sx0, sx1, ax0, ax1, sy0, sy1, ay0, ay1;  // window coordinates
+  lin_coef(xr, (double)im.win_w / (double)im.new_w, im.win_w, sx0, sx1, ax0, ax1);
+  lin_coef(yr, (double)im.win_h / (double)im.new_h, im.win_h, sy0, sy1, ay0, ay1);
+  // window -> canvas -> image; a tap outside the image reads the fill
+  const int ix0 = im.win_x + sx0 - im.img_left, ix1 = im.win_x + sx1 - im.img_left;
+  const int iy0 = im.win_y + sy0 - im.img_top, iy1 = im.win_y + sy1 - im.img_top;
+  const bool inx0 = (unsigned)ix0 < (unsigned)im.src_w;
+  const bool inx1 = (unsigned)ix1 < (unsigned)im.src_w;
+  const bool iny0 = (unsigned)iy0 < (unsigned)im.src_h;
+  const bool iny1 = (unsigned)iy1 < (unsigned)im.src_h;
+  // rows that are not read keep a valid address (row 0)
+  const unsigned char* r0 = im.data + ((size_t)(iny0 ? iy0 : 0) * im.src_w) * 3;
+  const unsigned char* r1 = im.data + ((size_t)(iny1 ? iy1 : 0) * im.src_w) * 3;
+  const float mean[3] = {mean0, mean1, mean2}, inv[3] = {inv0, inv1, inv2};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {  // c = output channel
+    const int cs = to_rgb ? 2 - c : c;  // source (BGR) channel
+    const int f = im.fill[cs];
+    const int p00 = (iny0 && inx0) ? r0[ix0 * 3 + cs] : f;
+    const int p01 = (iny0 && inx1) ? r0[ix1 * 3 + cs] : f;
+    const int p10 = (iny1 && inx0) ? r1[ix0 * 3 + cs] : f;
+    const int p11 = (iny1 && inx1) ? r1[ix1 * 3 + cs] : f;
+    const int h0 = p00 * ax0 + p01 * ax1;
+    const int h1 = p10 * ax0 + p11 * ax1;
+    int v = (h0 * ay0 + h1 * ay1 + (1 << (2 * kCoefBits - 1))) >> (2 * kCoefBits);
+    v = min(max(v, 0), 255);
+    o[(size_t)c * plane] = ((float)v - mean[c]) * inv[c];
+  }
+}
+
 }  // namespace
+
+extern "C" int ld_preprocess_batch_aug(const ld_image_aug_t* imgs, int N, int Hpad,
+                                       int Wpad, const float* mean,
+                                       const float* std_inv, const float* pad_val,
+                                       int to_rgb, float* out, ld_stream_t stream) {
+  if (!imgs || !mean || !std_inv || !pad_val || !out || N < 1 || Hpad < 1 || Wpad < 1)
+    return LD_EINVAL;
+  LD_LAUNCH(preprocess_aug_kernel, dim3((Wpad + 63) / 64, (Hpad + 3) / 4, N),
+                     dim3(256), 0, (hipStream_t)stream, imgs, Hpad, Wpad, mean[0],
+                     mean[1], mean[2], std_inv[0], std_inv[1], std_inv[2], pad_val[0],
+                     pad_val[1], pad_val[2], to_rgb, out);
+  return (int)hipGetLastError();
+}
 
 extern "C" int ld_preprocess_batch(const ld_image_t* imgs, int N, int Hpad, int Wpad,
                                    const float* mean, const float* std_inv, int to_rgb,

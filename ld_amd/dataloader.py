@@ -19,7 +19,10 @@ orientation is applied as ``cv2.IMREAD_COLOR`` does, through
 **Determinism.**  The order of epoch ``e`` comes from the sampler seeded with
 ``(seed, e)``; the random scale and flip draws of batch ``b`` come from
 ``RandomState(batch_seed(seed, e, b))``.  A batch is a pure function of
-``(seed, epoch, index)``, whatever the thread timing.  ``seed=None`` leaves
+``(seed, epoch, index)``, whatever the thread timing.  With a RandomCrop in
+the pipeline an image can be rejected (no gt box left); its replacement is
+drawn from the same generator, so the rule still holds, and the indices a
+batch really holds are ``host['indices']``.  ``seed=None`` leaves
 both to numpy's global generator, as the reference does.
 
 The loader has started at most two batches beyond the one it last handed out
@@ -42,6 +45,7 @@ __all__ = ['imread', 'batch_seed', 'build_dataloader', 'DeviceDataLoader',
 
 MAX_THREADS = 16
 LOOK_AHEAD = 2
+MAX_REPLACEMENTS = 1000  # of one rejected image, before giving up
 
 
 def imread(path):
@@ -199,7 +203,12 @@ class DeviceDataLoader:
             return host
         rng = np.random if self.seed is None else np.random.RandomState(
             batch_seed(self.seed, epoch, index))
-        host['plans'] = self.pipeline.plan(shapes, rng)
+        if self.pipeline.augmented:
+            host['plans'] = [self._plan_or_replace(host, k, rng)
+                             for k in range(len(images))]
+            idxs = host['indices']
+        else:
+            host['plans'] = self.pipeline.plan(shapes, rng)
         anns = [self.dataset.get_ann_info(i) for i in idxs]
         host['gt_bboxes'] = [a['bboxes'] for a in anns]
         host['gt_labels'] = [a['labels'] for a in anns]
@@ -207,6 +216,32 @@ class DeviceDataLoader:
             a.get('bboxes_ignore', np.zeros((0, 4), np.float32))
             for a in anns]
         return host
+
+    def _plan_or_replace(self, host, k, rng):
+        """The plan of image ``k`` of the batch.  A plan the pipeline rejects
+        (RandomCrop left no gt box: the reference's pipeline returns None) is
+        answered as ``CustomDataset.__getitem__`` answers it (custom.py:
+        184-203, ``_rand_another``): another index of the same aspect-ratio
+        group, drawn from the batch's generator, decoded here and planned
+        again.  ``host`` is updated in place."""
+        flag = getattr(self.dataset, 'flag', None)
+        for _ in range(MAX_REPLACEMENTS):
+            idx = host['indices'][k]
+            ann = self.dataset.get_ann_info(idx)
+            plan = self.pipeline.plan_image(
+                tuple(host['images'][k].shape[:2]), rng, ann['bboxes'],
+                ann['labels'], ann.get('bboxes_ignore'))
+            if not plan['rejected']:
+                return plan
+            pool = np.arange(len(self.dataset)) if flag is None else \
+                np.where(np.asarray(flag) == flag[idx])[0]
+            idx = int(rng.choice(pool))
+            host['indices'][k] = idx
+            host['images'][k] = self._decode(idx)
+            host['filenames'][k] = self.dataset.img_names(idx)
+        raise RuntimeError(
+            f'no image of the group of index {idx} survives the crop after '
+            f'{MAX_REPLACEMENTS} replacements')
 
     def host_batch(self, epoch, index, order=None):
         """The host half of batch ``index`` of ``epoch``: ``indices``, decoded

@@ -22,6 +22,14 @@ rounding; GT boxes are tiny and go to the device with the same async copy.
 51-147 (the sampler build_dataloader picks for dist=True) index for index; it
 is pinned against the reference's own sampler in tests/test_pipeline.py.
 
+Train-time augmentations -- Expand, MinIoURandomCrop, Resize(keep_ratio=False),
+RandomCrop, Pad(size=, pad_val=) (transforms.py:916-1000, 1008-1140, 588-760,
+476-540) -- stay in that one launch (``ld_preprocess_batch_aug``): the host
+draws and transforms the boxes exactly as the reference does
+(``DevicePipeline.plan_image``, pinned on the reference's own classes in
+tests/golden/augment.npz), the kernel walks every output pixel back through
+crop, resize, window and canvas.  The plain pipeline keeps the plain launch.
+
 There is no CPU fallback for the image arithmetic: DevicePipeline refuses to
 run without the HIP library and a device.
 """
@@ -101,6 +109,110 @@ def _ceil_to(v, d):
     return int(math.ceil(v / d)) * d
 
 
+def patch_overlaps(patch, boxes, eps=1e-6):
+    """mmdet/core/evaluation/bbox_overlaps.py:4-48 (mode='iou', no + 1) for
+    one patch against (k, 4) boxes, in fp32 as there."""
+    a = np.asarray(patch).reshape(4).astype(np.float32)
+    b = np.asarray(boxes).reshape(-1, 4).astype(np.float32)
+    if len(b) == 0:
+        return np.zeros(0, np.float32)
+    area1 = (a[2] - a[0]) * (a[3] - a[1])
+    area2 = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    overlap = np.maximum(np.minimum(a[2], b[:, 2]) - np.maximum(a[0], b[:, 0]),
+                         0) * \
+        np.maximum(np.minimum(a[3], b[:, 3]) - np.maximum(a[1], b[:, 1]), 0)
+    union = np.maximum(area1 + area2 - overlap, eps)
+    return (overlap / union).astype(np.float32)
+
+
+def _centers_in_patch(boxes, patch):
+    """MinIoURandomCrop's is_center_of_bboxes_in_patch (transforms.py:
+    1097-1103): strict on all four sides."""
+    center = (boxes[:, :2] + boxes[:, 2:]) / 2
+    return ((center[:, 0] > patch[0]) * (center[:, 1] > patch[1]) *
+            (center[:, 0] < patch[2]) * (center[:, 1] < patch[3]))
+
+
+def expand_draw(shape, rng, ratio_range=(1, 4), prob=0.5):
+    """Expand.__call__'s draws (transforms.py:955-975) for an (h, w) image:
+    None when ``prob`` skips it, else (canvas_h, canvas_w, top, left)."""
+    h, w = shape
+    if rng.uniform(0, 1) > prob:
+        return None
+    ratio = rng.uniform(ratio_range[0], ratio_range[1])
+    left = int(rng.uniform(0, w * ratio - w))
+    top = int(rng.uniform(0, h * ratio - h))
+    return int(h * ratio), int(w * ratio), top, left
+
+
+def min_iou_patch(shape, boxes, rng, min_ious=(0.1, 0.3, 0.5, 0.7, 0.9),
+                  min_crop_size=0.3):
+    """MinIoURandomCrop.__call__'s search (transforms.py:1064-1107) on an
+    (h, w) image with all bbox fields concatenated in ``boxes``: the mode
+    drawn last and the accepted patch (x1, y1, x2, y2) as an int array, or
+    None for mode 1.  ``random.uniform(w - new_w)`` is numpy's
+    uniform(low=w - new_w, high=1.0), drawn as the reference draws it."""
+    h, w = shape
+    sample_mode = (1, *min_ious, 0)
+    while True:
+        mode = rng.choice(sample_mode)
+        if mode == 1:
+            return mode, None
+        for _ in range(50):
+            new_w = rng.uniform(min_crop_size * w, w)
+            new_h = rng.uniform(min_crop_size * h, h)
+            if new_h / new_w < 0.5 or new_h / new_w > 2:
+                continue
+            left = rng.uniform(w - new_w)
+            top = rng.uniform(h - new_h)
+            patch = np.array(
+                (int(left), int(top), int(left + new_w), int(top + new_h)))
+            if patch[2] == patch[0] or patch[3] == patch[1]:
+                continue
+            overlaps = patch_overlaps(patch, boxes)
+            if len(overlaps) > 0 and overlaps.min() < mode:
+                continue
+            if len(overlaps) > 0 and not _centers_in_patch(boxes, patch).any():
+                continue
+            return mode, patch
+
+
+def crop_size_draw(image_size, crop_size, crop_type, rng):
+    """RandomCrop._get_crop_size (transforms.py:716-744)."""
+    h, w = image_size
+    if crop_type == 'absolute':
+        return min(crop_size[0], h), min(crop_size[1], w)
+    if crop_type == 'absolute_range':
+        assert crop_size[0] <= crop_size[1]
+        crop_h = rng.randint(min(h, crop_size[0]), min(h, crop_size[1]) + 1)
+        crop_w = rng.randint(min(w, crop_size[0]), min(w, crop_size[1]) + 1)
+        return crop_h, crop_w
+    if crop_type == 'relative':
+        crop_h, crop_w = crop_size
+        return int(h * crop_h + 0.5), int(w * crop_w + 0.5)
+    if crop_type == 'relative_range':
+        cs = np.asarray(crop_size, dtype=np.float32)
+        crop_h, crop_w = cs + rng.rand(2) * (1 - cs)
+        return int(h * crop_h + 0.5), int(w * crop_w + 0.5)
+    raise ValueError(f'Invalid crop_type {crop_type}.')
+
+
+def crop_bboxes(bboxes, offset_w, offset_h, img_shape, clip=True):
+    """RandomCrop._crop_data's bbox half (transforms.py:684-691): the fp32
+    offset subtraction, the clip, and ``valid_inds``.  Returns (the shifted
+    boxes BEFORE selection, valid_inds)."""
+    off = np.array([offset_w, offset_h, offset_w, offset_h], dtype=np.float32)
+    b = bboxes - off
+    if clip:
+        b[:, 0::2] = np.clip(b[:, 0::2], 0, img_shape[1])
+        b[:, 1::2] = np.clip(b[:, 1::2], 0, img_shape[0])
+    return b, (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+
+
+_STEP_RANK = {'Expand': 0, 'MinIoURandomCrop': 1, 'Resize': 2, 'RandomCrop': 3,
+              'RandomFlip': 4, 'Normalize': 4, 'Pad': 5}
+
+
 class DevicePipeline:
     """The reference's train_pipeline from Resize to collate, on the device.
 
@@ -116,11 +228,48 @@ class DevicePipeline:
     def __init__(self, img_scale=(1333, 800), keep_ratio=True, flip_ratio=0.5,
                  mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375),
                  to_rgb=True, size_divisor=32, multiscale_mode='range',
-                 ratio_range=None, bbox_clip_border=True, device=None):
-        if not keep_ratio:
-            raise NotImplementedError(
-                'keep_ratio=False is not used by any configs/ld or configs/ldv2 '
-                'train pipeline')
+                 ratio_range=None, bbox_clip_border=True, device=None,
+                 crop=None, expand=None, min_iou_crop=None, pad_size=None,
+                 pad_val=0):
+        """``crop`` / ``expand`` / ``min_iou_crop``: the keyword dicts of the
+        reference's RandomCrop / Expand / MinIoURandomCrop (or None);
+        ``pad_size`` (H, W) and ``pad_val``: Pad(size=, pad_val=)."""
+        if pad_size is not None and size_divisor is not None:
+            # transforms.py:495 asserts that only one of them is given
+            raise ValueError(
+                f'Pad: size={tuple(pad_size)} and size_divisor={size_divisor} '
+                'are both given; pass size_divisor=None with a fixed size')
+        self.keep_ratio = bool(keep_ratio)
+        self.crop = None if crop is None else dict(
+            dict(crop_type='absolute', allow_negative_crop=False,
+                 bbox_clip_border=True), **crop)
+        if self.crop is not None and self.crop['crop_type'] not in (
+                'relative_range', 'relative', 'absolute', 'absolute_range'):
+            raise ValueError(f"Invalid crop_type {self.crop['crop_type']}.")
+        self.expand = None if expand is None else dict(
+            dict(mean=(0, 0, 0), to_rgb=True, ratio_range=(1, 4), prob=0.5),
+            **expand)
+        # Expand's canvas colour as the reference builds it: the mean in the
+        # decoded image's BGR order, cast to uint8 by np.full (transforms.py:
+        # 937-940, 971-973)
+        self.expand_fill = (0, 0, 0)
+        if self.expand is not None:
+            m = self.expand['mean']
+            m = m[::-1] if self.expand['to_rgb'] else m
+            self.expand_fill = tuple(
+                int(v) for v in np.full((3,), m, dtype=np.uint8))
+        self.min_iou_crop = None if min_iou_crop is None else dict(
+            dict(min_ious=(0.1, 0.3, 0.5, 0.7, 0.9), min_crop_size=0.3,
+                 bbox_clip_border=True), **min_iou_crop)
+        self.pad_size = None if pad_size is None else tuple(
+            int(v) for v in pad_size)
+        self.pad_val = np.broadcast_to(
+            np.asarray(pad_val, np.float32), (3,)).copy()
+        # everything ld_preprocess_batch cannot express goes through
+        # ld_preprocess_batch_aug; the plain pipeline keeps the plain launch
+        self.augmented = bool(
+            self.crop or self.expand or self.min_iou_crop or self.pad_size
+            or not self.keep_ratio or self.pad_val.any())
         self.img_scale = img_scale
         self.multiscale_mode = multiscale_mode
         self.ratio_range = ratio_range
@@ -139,11 +288,35 @@ class DevicePipeline:
     def from_cfg(cls, train_pipeline, device=None):
         """Build from a reference config's ``train_pipeline`` list (the dicts
         with type Resize / RandomFlip / Normalize / Pad); other entries are the
-        loading / formatting steps this class subsumes."""
+        loading / formatting steps this class subsumes.  The optional
+        augmentations are taken in one order only: [Expand],
+        [MinIoURandomCrop], Resize, [RandomCrop], RandomFlip / Normalize in
+        either order, Pad last."""
         kw = {}
+        prev = None
         for step in train_pipeline:
             t = step['type']
-            if t == 'Resize':
+            if t in _STEP_RANK:
+                if prev is not None and _STEP_RANK[t] < _STEP_RANK[prev]:
+                    raise NotImplementedError(
+                        f'pipeline step {t} after {prev}: the device '
+                        'pipeline runs Expand, MinIoURandomCrop, Resize, '
+                        'RandomCrop, RandomFlip / Normalize, Pad in this '
+                        'order only')
+                prev = t
+            args = {k: v for k, v in step.items() if k != 'type'}
+            if t == 'Expand':
+                if args.get('seg_ignore_label') is not None:
+                    raise NotImplementedError(
+                        'Expand(seg_ignore_label=...): segmentation maps are '
+                        'not carried by the device pipeline')
+                args.pop('seg_ignore_label', None)
+                kw['expand'] = args
+            elif t == 'MinIoURandomCrop':
+                kw['min_iou_crop'] = args
+            elif t == 'RandomCrop':
+                kw['crop'] = args
+            elif t == 'Resize':
                 kw['img_scale'] = step['img_scale']
                 kw['keep_ratio'] = step.get('keep_ratio', True)
                 kw['multiscale_mode'] = step.get('multiscale_mode', 'range')
@@ -155,6 +328,8 @@ class DevicePipeline:
                 kw['to_rgb'] = step.get('to_rgb', True)
             elif t == 'Pad':
                 kw['size_divisor'] = step.get('size_divisor')
+                kw['pad_size'] = step.get('size')
+                kw['pad_val'] = step.get('pad_val', 0)
             elif t not in ('LoadImageFromFile', 'LoadAnnotations',
                            'DefaultFormatBundle', 'Collect'):
                 raise NotImplementedError(f'pipeline step {t}')
@@ -213,6 +388,10 @@ class DevicePipeline:
         major, then (no flip), then each flip direction; one plan per view of
         an image of ``shape`` (h, w)."""
         h, w = shape
+        if not self.keep_ratio:
+            raise NotImplementedError(
+                'keep_ratio=False is not used by any configs/ld or configs/ldv2 '
+                'test pipeline')
         scales = getattr(self, 'aug_scales', [tuple(self.img_scale)])
         flips = getattr(self, 'aug_flips', [(False, None)])
         plans = []
@@ -251,10 +430,20 @@ class DevicePipeline:
         return imgs, metas
 
     # -- per-image host decisions -------------------------------------------
-    def plan(self, shapes, rng=np.random):
+    def plan(self, shapes, rng=np.random, gt_bboxes=None, gt_labels=None,
+             gt_bboxes_ignore=None):
         """For each (h, w): the scale, the resized size, scale_factor and the
         flip decision, drawing from ``rng`` in the reference's order (scale
-        draws of Resize, then RandomFlip's one np.random.choice)."""
+        draws of Resize, then RandomFlip's one np.random.choice).
+
+        With augmentations (``self.augmented``) the annotations decide draws
+        and survive or not, so they are planned too: see ``plan_image``."""
+        if self.augmented:
+            n = len(shapes)
+            none = [None] * n
+            return [self.plan_image(s, rng, b, l, ig) for s, b, l, ig in zip(
+                shapes, gt_bboxes or none, gt_labels or none,
+                gt_bboxes_ignore or none)]
         plans = []
         for (h, w) in shapes:
             scale = sample_scale(self.img_scale, self.multiscale_mode,
@@ -271,12 +460,153 @@ class DevicePipeline:
                               scale_factor=sf, flip=flip, scale=tuple(scale)))
         return plans
 
+    def plan_image(self, shape, rng=np.random, gt_bboxes=None, gt_labels=None,
+                   gt_bboxes_ignore=None):
+        """One image through Expand -> MinIoURandomCrop -> Resize ->
+        RandomCrop -> RandomFlip on the host: every draw the reference makes,
+        in its order, and its box arithmetic on the two bbox fields.  The plan
+        carries the geometry the kernel needs (``canvas`` (h, w, top, left),
+        ``window`` (y, x, h, w) in canvas coordinates, ``resized`` (h, w),
+        ``crop`` (y, x) in resized coordinates, ``img_shape``, ``flip``), the
+        transformed ``gt_bboxes`` / ``gt_labels`` / ``gt_bboxes_ignore`` and
+        which input rows they are (``keep`` / ``keep_ignore``).  A RandomCrop
+        that the reference answers with None gives ``dict(rejected=True)``;
+        no draw is made after it."""
+        h, w = shape
+        boxes = np.zeros((0, 4), np.float32) if gt_bboxes is None else \
+            np.array(gt_bboxes, np.float32).reshape(-1, 4)
+        ignore = np.zeros((0, 4), np.float32) if gt_bboxes_ignore is None \
+            else np.array(gt_bboxes_ignore, np.float32).reshape(-1, 4)
+        keep, keep_ig = np.arange(len(boxes)), np.arange(len(ignore))
+        # Expand (transforms.py:945-997)
+        canvas = (h, w, 0, 0)
+        if self.expand is not None:
+            e = expand_draw((h, w), rng, self.expand['ratio_range'],
+                            self.expand['prob'])
+            if e is not None:
+                canvas = e
+                shift = np.tile((e[3], e[2]), 2)
+                boxes = boxes + shift.astype(boxes.dtype)
+                ignore = ignore + shift.astype(ignore.dtype)
+        ch, cw = canvas[:2]
+        # MinIoURandomCrop (transforms.py:1045-1137)
+        window, mode = (0, 0, ch, cw), None
+        if self.min_iou_crop is not None:
+            m = self.min_iou_crop
+            mode, patch = min_iou_patch(
+                (ch, cw), np.concatenate([ignore, boxes], 0), rng,
+                m['min_ious'], m['min_crop_size'])
+            if patch is not None:
+                if len(boxes) + len(ignore) > 0:
+                    out = []
+                    for b, k in ((boxes, keep), (ignore, keep_ig)):
+                        b = b.copy()
+                        mask = _centers_in_patch(b, patch)
+                        b = b[mask]
+                        if m['bbox_clip_border']:
+                            b[:, 2:] = b[:, 2:].clip(max=patch[2:])
+                            b[:, :2] = b[:, :2].clip(min=patch[:2])
+                        b -= np.tile(patch[:2], 2)
+                        out += [b, k[mask]]
+                    boxes, keep, ignore, keep_ig = out
+                # img[patch[1]:patch[3], patch[0]:patch[2]]
+                y2, x2 = min(int(patch[3]), ch), min(int(patch[2]), cw)
+                window = (int(patch[1]), int(patch[0]), y2 - int(patch[1]),
+                          x2 - int(patch[0]))
+        wh, ww = window[2:]
+        # Resize (transforms.py:203-241)
+        scale = sample_scale(self.img_scale, self.multiscale_mode,
+                             self.ratio_range, rng)
+        if self.keep_ratio:
+            new_w, new_h = rescale_size((ww, wh), tuple(scale))
+        else:  # mmcv.imresize(img, size=(w, h)): independent w_scale, h_scale
+            new_w, new_h = int(scale[0]), int(scale[1])
+        sf = np.array([new_w / ww, new_h / wh, new_w / ww, new_h / wh],
+                      np.float32)
+        boxes = resize_bboxes(boxes, sf, (new_h, new_w), self.bbox_clip_border)
+        ignore = resize_bboxes(ignore, sf, (new_h, new_w),
+                               self.bbox_clip_border)
+        # RandomCrop (transforms.py:651-760)
+        crop, img_shape = (0, 0), (new_h, new_w, 3)
+        if self.crop is not None:
+            c = self.crop
+            crop_h, crop_w = crop_size_draw((new_h, new_w), c['crop_size'],
+                                            c['crop_type'], rng)
+            assert crop_h > 0 and crop_w > 0
+            off_h = int(rng.randint(0, max(new_h - crop_h, 0) + 1))
+            off_w = int(rng.randint(0, max(new_w - crop_w, 0) + 1))
+            crop = (off_h, off_w)
+            img_shape = (min(off_h + crop_h, new_h) - off_h,
+                         min(off_w + crop_w, new_w) - off_w, 3)
+            ignore, valid = crop_bboxes(ignore, off_w, off_h, img_shape,
+                                        c['bbox_clip_border'])
+            ignore, keep_ig = ignore[valid, :], keep_ig[valid]
+            boxes, valid = crop_bboxes(boxes, off_w, off_h, img_shape,
+                                       c['bbox_clip_border'])
+            if not valid.any() and not c['allow_negative_crop']:
+                return dict(rejected=True, ori_shape=(h, w, 3))
+            boxes, keep = boxes[valid, :], keep[valid]
+        # RandomFlip (transforms.py:416-450)
+        flip = False
+        if self.flip_ratio > 0:
+            flip = int(rng.choice(2, p=[self.flip_ratio,
+                                        1 - self.flip_ratio])) == 0
+        if flip:
+            boxes = flip_bboxes(boxes, img_shape)
+            ignore = flip_bboxes(ignore, img_shape)
+        labels = None if gt_labels is None else \
+            np.asarray(gt_labels, np.int64)[keep]
+        return dict(rejected=False, ori_shape=(h, w, 3), img_shape=img_shape,
+                    scale_factor=sf, flip=flip, scale=tuple(scale),
+                    canvas=tuple(int(v) for v in canvas), window=window,
+                    resized=(new_h, new_w), crop=crop, fill=self.expand_fill,
+                    mode=None if mode is None else float(mode),
+                    gt_bboxes=boxes, gt_labels=labels,
+                    gt_bboxes_ignore=ignore, keep=keep, keep_ignore=keep_ig)
+
     def transform_boxes(self, bboxes, plan):
+        if 'gt_bboxes' in plan:
+            raise ValueError('an augmented plan carries its own boxes '
+                             "(plan['gt_bboxes'])")
         b = resize_bboxes(bboxes, plan['scale_factor'], plan['img_shape'],
                           self.bbox_clip_border)
         if plan['flip']:
             b = flip_bboxes(b, plan['img_shape'])
         return b
+
+    @staticmethod
+    def fill_descriptor(d, plan, shape):
+        """The geometry of one plan -> an ``ld_image_aug_t`` (``data``,
+        ``src_h`` / ``src_w`` and ``flip`` are the caller's).  A plain plan
+        (no canvas, window or crop) gives the identity descriptor."""
+        h, w = shape
+        ch, cw, top, left = plan.get('canvas', (h, w, 0, 0))
+        d.canvas_h, d.canvas_w, d.img_top, d.img_left = ch, cw, top, left
+        d.win_y, d.win_x, d.win_h, d.win_w = plan.get('window',
+                                                      (0, 0, ch, cw))
+        d.new_h, d.new_w = plan.get('resized', plan['img_shape'][:2])
+        d.crop_y, d.crop_x = plan.get('crop', (0, 0))
+        d.out_h, d.out_w = plan['img_shape'][:2]
+        fill = plan.get('fill', (0, 0, 0))
+        for c in range(3):
+            d.fill[c] = int(fill[c])
+
+    def batch_shape(self, plans):
+        """(Hpad, Wpad) of the batch tensor.  Pad(size_divisor) per image, then
+        collate pads to the batch maximum; Pad(size) is that size for every
+        batch, and an image larger than it raises (mmcv.impad asserts)."""
+        if self.pad_size is not None:
+            for p in plans:
+                if p['img_shape'][0] > self.pad_size[0] or \
+                        p['img_shape'][1] > self.pad_size[1]:
+                    raise ValueError(
+                        f"Pad(size={self.pad_size}): the image is "
+                        f"{tuple(p['img_shape'][:2])}, larger than the pad "
+                        'size')
+            return self.pad_size
+        div = self.size_divisor or 1
+        return (max(_ceil_to(p['img_shape'][0], div) for p in plans),
+                max(_ceil_to(p['img_shape'][1], div) for p in plans))
 
     # -- the batch ------------------------------------------------------------
     def __call__(self, images, gt_bboxes=None, gt_labels=None, rng=np.random,
@@ -285,6 +615,9 @@ class DevicePipeline:
         lib = L.get_lib()  # raises when the HIP library is missing
         if self.device.type != 'cuda':
             raise RuntimeError('DevicePipeline needs a GPU device')
+        if self.augmented:
+            return self._call_augmented(images, gt_bboxes, gt_labels, rng,
+                                        plans, stream, gt_bboxes_ignore)
         N = len(images)
         shapes = [tuple(im.shape[:2]) for im in images]
         if plans is None:
@@ -348,6 +681,82 @@ class DevicePipeline:
             result['gt_labels'] = [
                 torch.as_tensor(np.asarray(l, np.int64)).to(
                     self.device, non_blocking=True) for l in gt_labels]
+        return result
+
+    def _call_augmented(self, images, gt_bboxes, gt_labels, rng, plans, stream,
+                        gt_bboxes_ignore):
+        """``__call__`` of a pipeline with augmentations: the same staging
+        copy, then ONE ``ld_preprocess_batch_aug`` launch; the annotations
+        are the plans' own (transformed and selected by ``plan_image``)."""
+        from . import lib as L
+        lib = L.get_lib()  # raises when the HIP library is missing
+        if self.device.type != 'cuda':
+            raise RuntimeError('DevicePipeline needs a GPU device')
+        N = len(images)
+        shapes = [tuple(im.shape[:2]) for im in images]
+        if plans is None:
+            plans = self.plan(shapes, rng, gt_bboxes, gt_labels,
+                              gt_bboxes_ignore)
+        if any(p.get('rejected') for p in plans):
+            raise ValueError(
+                'a rejected plan (RandomCrop left no gt box) cannot be '
+                'launched: the loader replaces such an image')
+        Hpad, Wpad = self.batch_shape(plans)
+        sizes = [h * w * 3 for h, w in shapes]
+        offs = np.concatenate([[0], np.cumsum([(s + 255) // 256 * 256
+                                               for s in sizes])])
+        stage = torch.empty(int(offs[-1]), dtype=torch.uint8, pin_memory=True)
+        for im, o, s in zip(images, offs, sizes):
+            t = im if isinstance(im, torch.Tensor) else torch.from_numpy(
+                np.ascontiguousarray(im))
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+                raise ValueError('images must be uint8 HWC with 3 channels')
+            stage[int(o):int(o) + s].copy_(t.reshape(-1))
+        raw = stage.to(self.device, non_blocking=True)
+        desc = (L.ImageAugT * N)()
+        for i, (p, (h, w)) in enumerate(zip(plans, shapes)):
+            desc[i].data = raw.data_ptr() + int(offs[i])
+            desc[i].src_h, desc[i].src_w = h, w
+            desc[i].flip = int(p['flip'])
+            self.fill_descriptor(desc[i], p, (h, w))
+        dbytes = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8)
+        ddesc = dbytes.pin_memory().to(self.device, non_blocking=True)
+        out = torch.empty(N, 3, Hpad, Wpad, dtype=torch.float32,
+                          device=self.device)
+        s = stream if stream is not None else torch.cuda.current_stream(
+            self.device)
+        mean = (C.c_float * 3)(*self.mean.tolist())
+        sinv = (C.c_float * 3)(*self.std_inv.tolist())
+        pad = (C.c_float * 3)(*self.pad_val.tolist())
+        L.check(lib.ld_preprocess_batch_aug(
+            ddesc.data_ptr(), N, Hpad, Wpad, mean, sinv, pad,
+            int(self.to_rgb), out.data_ptr(), s.cuda_stream),
+            'ld_preprocess_batch_aug')
+        div = self.size_divisor or 1
+        metas = []
+        for p in plans:
+            pad_shape = (_ceil_to(p['img_shape'][0], div),
+                         _ceil_to(p['img_shape'][1], div), 3)
+            if self.pad_size is not None:
+                pad_shape = self.pad_size + (3,)
+            metas.append(dict(
+                ori_shape=p['ori_shape'], img_shape=p['img_shape'],
+                pad_shape=pad_shape, scale_factor=p['scale_factor'],
+                flip=p['flip'],
+                flip_direction='horizontal' if p['flip'] else None,
+                img_norm_cfg=dict(mean=self.mean, std=self.std,
+                                  to_rgb=self.to_rgb)))
+            if self.pad_size is not None:
+                metas[-1]['pad_fixed_size'] = self.pad_size
+        result = dict(img=out, img_metas=metas)
+
+        def dev(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(
+                self.device, non_blocking=True)
+        for key, given in (('gt_bboxes', gt_bboxes), ('gt_labels', gt_labels),
+                           ('gt_bboxes_ignore', gt_bboxes_ignore)):
+            if given is not None:
+                result[key] = [dev(p[key]) for p in plans]
         return result
 
 
