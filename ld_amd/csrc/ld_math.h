@@ -284,11 +284,17 @@ LD_HD float dciou_loss_grad_(const Box& p, const Box& t, float eps, bool ciou,
     float d = atanf(tw / h2) - atanf(r1);
     float v = factor * (d * d);
     float den = 1.0f - iou + v;
-    float vd2 = (v * v) / (den * den);
-    pen = pen + (v * v) / den;
+    // den == 0 only for a perfect box (iou == 1 once fp32 drops the additive eps
+    // of the union, and v == 0): q = v^2 / den and its derivatives are 0 there,
+    // as in exact arithmetic.  The reference's fp32 evaluates 0 / 0 = NaN at such
+    // a box; float64 gives 0 (tests/test_gpu_loss_edges.py, box_ties_ciou).
+    const bool live = den > 0.0f;
+    float vd2 = live ? (v * v) / (den * den) : 0.0f;
+    pen = pen + (live ? (v * v) / den : 0.0f);
     k_iou = -1.0f + vd2;
     // d q / d v * d v / d r1, q = v^2 / den
-    float gr1 = (2.0f * v / den - vd2) * (-(factor * 2.0f * d) / (1.0f + r1 * r1));
+    float gr1 = ((live ? 2.0f * v / den : 0.0f) - vd2) *
+                (-(factor * 2.0f * d) / (1.0f + r1 * r1));
     g_w = gr1 / h1;
     g_h = -gr1 * r1 / h1;
   }
@@ -326,6 +332,17 @@ struct SideKL {
   float kl;
   float lse_s, lse_t;  // log-sum-exp of s/T and t/T (max-shifted form folded in)
 };
+
+// a * b - c * d for the KL gradient direction ps - pt of kl_rows_inplace:
+// fma(a, b, -(c * d)), one rounding fewer than two products -- except where
+// (a, b) == (c, d).  There the difference is exactly 0 and the fma would return
+// the rounding residual of c * d (about 1e-8 of p): a student row that equals its
+// teacher's gets exactly zero, as kl_rows gives it
+// (tests/test_gpu_loss_edges.py, student_is_teacher).  Every other input keeps
+// the fma's bits.
+LD_HD float diff_of_products_(float a, float b, float c, float d) {
+  return (a == c && b == d) ? 0.0f : fmaf(a, b, -(c * d));
+}
 
 template <int K>
 LD_HD float kl_rows(const float* s, const float* t, float invT, float T,
@@ -401,7 +418,7 @@ LD_HD float kl_rows_inplace(float* s, float* t, float invT, float T) {
   const float rzt = FAST ? fast_rcp_(zt) : 1.0f / zt;
   const float kl = (acc * rzt * invT + (logf(zs) - logf(zt))) * ((T * T) / (float)K);
 #pragma unroll
-  for (int k = 0; k < K; ++k) s[k] = fmaf(s[k], rzs, -(t[k] * rzt));
+  for (int k = 0; k < K; ++k) s[k] = diff_of_products_(s[k], rzs, t[k], rzt);
   return kl;
 }
 

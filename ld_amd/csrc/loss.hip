@@ -21,6 +21,17 @@
 // of the loss partial sums, which are written per block and summed in a fixed
 // order by the finalise kernel (bitwise run-to-run reproducible, no float
 // atomics).
+//
+// Tests: tests/test_gpu_lossblock.py and its per-head siblings compare four
+// ordinary batches with the reference's stored outputs; tests/test_gpu_loss_edges.py
+// runs the states those never reach against a float64 autograd restatement
+// (tests/_loss_ref64.py): images without a GT box and batches without a positive
+// (each avg_divisor form at a zero normaliser, every P_l == 0 guard), levels of
+// 1, 2, 64, 256 and 561 cells, 1 / 17 / 128 classes and 8 / 48 / 264 feature
+// channels (the chunk-count edges of the cls and IM kernels; 129 classes are
+// refused), saturated logits, student == teacher, exact box ties, poisoned
+// workspace and gradient memory, non-unit and zero upstream rows.  Which test
+// runs which reg-side kernel and branch: see LD_REG_VARIANT_DEFAULT below.
 #include <hip/hip_runtime.h>
 
 #include "ld_launch.h"
@@ -408,6 +419,7 @@ __global__ __launch_bounds__(kBlk) void loss_reg_dense_kernel(
 #pragma unroll
         for (int k = 0; k < K17; ++k) gr[k] = cg * d[k];
       } else if (hp.T_ld == hp.T_ld_vlr) {
+        // run only with variant word -1 (test_reg_variants_vs_ref64[*-round2])
         const float T = hp.T_ld;
         const float kl = ld::kl_rows<K17>(sv, tv, 1.0f / T, T, d);
         s_ld = wt * kl;
@@ -416,6 +428,11 @@ __global__ __launch_bounds__(kBlk) void loss_reg_dense_kernel(
 #pragma unroll
         for (int k = 0; k < K17; ++k) gr[k] = cg * d[k];
       } else {
+        // T_ld != T_ld_vlr: two KL evaluations, one per temperature.  No shipped
+        // config sets them apart; tests/test_gpu_loss_edges.py runs this branch
+        // (case two_temperatures: T_ld 10, T_ld_vlr 4, T_kd 1) and the mutation
+        // test of tests/test_loss_ref64_host.py shows its bar tells the two
+        // temperatures apart.
         if (pos) {
           const float T = hp.T_ld;
           const float kl = ld::kl_rows<K17>(sv, tv, 1.0f / T, T, d);
@@ -1220,6 +1237,22 @@ inline int im_chunk(int ch) { return max(32, (ch + kZMax - 1) / kZMax); }
 // ld_loss_set_reg_variant(LD_REG_VARIANT_DEFAULT & ~16) restores the exact forms.
 // vec 1, NT loads + stores, hardware exp, side-fast: 568-571 us at 2^24 rows =
 // 0.76 of 8 TB/s (round-2 kernel: 665-743 us), 11.2 us at the C2 step size
+//
+// Every word below runs in tests/test_gpu_loss_edges.py against float64
+// (test_reg_variants_vs_ref64, test_poisoned_memory_reg_variants; loose maps and
+// the packed arena, whose odd level bases send VEC 2 / 4 down the scalar path):
+//   default          every other loss-block test as well
+//   default & ~16    the exact expf / division forms           [exact]
+//   default | 1, | 2 VEC 2, VEC 4: vec_ok, level tails          [vec2] [vec4]
+//   default & ~32    one sweep per side (grid z = side)         [side_off]
+//   default | 1<<16  the 4 sides of a chunk on one XCD; a full group of 32
+//                    blocks and a tail need >= 8 blocks per image: the
+//                    ten_blocks case has 10                      [one_xcd]
+//   default | 128    VEC 1 held to 64 VGPRs                     [waves8]
+//   default | 64     non-temporal access below the cache size   [small_nt]
+//   -1               loss_reg_dense_kernel, T_ld == T_ld_vlr    [round2]
+// loss_reg_dense_kernel's other two branches: LD_LOSS_RETINA (every retina case)
+// and T_ld != T_ld_vlr (case two_temperatures), whatever the word.
 #define LD_REG_VARIANT_DEFAULT (0 | 4 | 8 | 16 | 32)
 int g_reg_variant = LD_REG_VARIANT_DEFAULT;
 

@@ -4,7 +4,7 @@ oracle/ref_shim.py) on CPU in fp32.  Run from the repo root in the build
 container:
 
     python oracle/gen_golden.py [--only kat,anchors,targets,lossblock,e2e,infer,
-                                        target_edges]
+                                        target_edges,loss_edges]
 
 The fixtures it writes are committed; the GPU box has no /root/reference and
 only ever reads the .npz files.  Inputs that can be regenerated from a seed
@@ -1825,6 +1825,130 @@ def gen_target_edges():
         'at the 9th place of a level.'])
 
 
+LOSS_EDGE_CASES = [
+    ('ragged', 'ld'), ('ten_blocks', 'ld'), ('pos_every_level', 'ld'),
+    ('two_temperatures', 'ld'), ('two_temperatures_t1', 'ld'),
+    ('pos_every_level', 'atss'), ('pos_every_level', 'fcos'),
+    ('pos_every_level', 'retina'), ('ragged', 'atss'), ('ragged', 'fcos'),
+    ('ragged', 'retina')]
+
+
+# LDFCOSHead alone is defined on an image without a GT box: these run whole
+LOSS_EDGE_FULL = [('empty_beside_full', 'fcos'), ('all_empty', 'fcos')]
+
+
+def _edge_head_loss(flavour, c):
+    """The reference head of ``flavour`` on an edge case of
+    tests/_loss_edges.py -> (loss dict, the student maps by family)."""
+    T = torch.from_numpy
+    m = {k: None if v is None else [t.clone() for t in v]
+         for k, v in c['maps'].items()}
+    gtb = [T(b).reshape(-1, 4) for b in c['boxes']]
+    gtl = [T(l) for l in c['labels']]
+    N = len(gtb)
+    if flavour == 'retina':   # pseudo-images back to (N, 9 * C, H, W)
+        m = {k: None if v is None else [t.reshape(N, -1, *t.shape[2:])
+                                        for t in v] for k, v in m.items()}
+    fam = dict(ld=('cls', 'reg', 'x'), atss=('cls', 'reg', 'ctr'),
+               fcos=('cls', 'reg', 'ctr'), retina=('cls', 'reg'))[flavour]
+    for k in fam:
+        for t in m[k]:
+            t.requires_grad_(True)
+    hp = c['hp']
+    if flavour == 'ld':
+        head = _ld_head()
+        head.loss_ld.T = hp.get('T_ld', 10.0)
+        head.loss_ld_vlr.T = hp.get('T_ld_vlr', 10.0)
+        head.loss_kd.T = hp.get('T_kd', 2.0)
+        losses = head.loss(m['cls'], m['reg'], gtb, gtl,
+                           (m['t_cls'], m['t_reg']), m['x'], m['t_x'],
+                           c['metas'])
+        keys = LOSS_KEYS
+    elif flavour == 'retina':
+        losses = _ld_retina_head().loss(m['cls'], m['reg'], gtb, gtl,
+                                        (m['t_cls'], m['t_reg']), c['metas'])
+        keys = RETINA_KEYS
+    else:
+        head = _ld_atss_head() if flavour == 'atss' else _ld_fcos_head()
+        losses = head.loss(m['cls'], m['reg'], m['ctr'], gtb, gtl,
+                           (m['t_cls'], m['t_reg'], None), c['metas'])
+        keys = ATSS_KEYS
+    return losses, keys, {k: m[k] for k in fam}
+
+
+def gen_loss_edges():
+    """The edge cases of tests/_loss_edges.py on which the reference's own
+    ``loss`` is defined, executed by the reference on CPU: loss tables,
+    per-level gradient sums and abs-sums, every 101st gradient element.  The
+    images without a GT box are removed first (E.without_empty); whether each
+    head's ``loss`` raises on such an image is recorded as
+    ``raises_on_empty_<flavour>``."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import _loss_edges as E
+    d, no_backward = {}, []
+    for name, fl in LOSS_EDGE_CASES + LOSS_EDGE_FULL:
+        full = (name, fl) in LOSS_EDGE_FULL
+        c = E.build(name, fl) if full else E.without_empty(E.build(name, fl))
+        losses, keys, student = _edge_head_loss(fl, c)
+        total = sum(sum(v) for v in losses.values())
+        key = f'{name}_{fl}' + ('_full' if full else '')
+        d[key + '_losses'] = np.stack(
+            [np.array([float(v.detach()) for v in losses[k]]) for k in keys])
+        try:
+            total.backward()
+        except RuntimeError as e:
+            # LDRetinaHead.loss_single rewrites a weight tensor in place after
+            # a loss has saved it; whether autograd notices depends on the
+            # level sizes.  The loss table stands, there are no gradients.
+            no_backward.append(key)
+            print(f'  loss_edges {key}: backward fails ({str(e)[:60]}...)')
+            continue
+        for k, ts in student.items():
+            gs = [t.grad if t.grad is not None else torch.zeros_like(t)
+                  for t in ts]
+            d[f'{key}_g{k}_sum'] = np.array(
+                [float(g.double().sum()) for g in gs])
+            d[f'{key}_g{k}_abs_sum'] = np.array(
+                [float(g.double().abs().sum()) for g in gs])
+            for l, g in enumerate(gs):
+                d[f'{key}_g{k}_{l}_every101'] = _np(g).reshape(-1)[::101]
+        print(f'  loss_edges {key}: total={float(total):.6f}')
+    raises = {}
+    for fl in ('ld', 'atss', 'fcos', 'retina'):
+        c = E.build('empty_beside_full', fl)
+        try:
+            _edge_head_loss(fl, c)
+            raises[fl] = ''
+        except Exception as e:  # noqa: BLE001 -- whatever the reference raises
+            raises[fl] = type(e).__name__
+        d['raises_on_empty_' + fl] = np.array(bool(raises[fl]))
+        print(f'  loss_edges empty image, {fl}: {raises[fl] or "runs"}')
+    path = os.path.join(OUT, 'loss_edges.npz')
+    np.savez_compressed(path, **d)
+    print('loss_edges.npz', len(d), 'arrays', os.path.getsize(path), 'bytes')
+    _manifest('loss_edges.npz', [
+        'Edge cases of `tests/_loss_edges.py` run through the reference\'s '
+        'own `loss` on CPU (`python oracle/gen_golden.py --only loss_edges`): '
+        + ', '.join(f'{n} ({f})' for n, f in LOSS_EDGE_CASES) + '; and with '
+        'their empty images, as `<case>_fcos_full`: '
+        + ', '.join(n for n, _ in LOSS_EDGE_FULL) + '.',
+        f'{len(d)} arrays, {os.path.getsize(path)} bytes; recorded outputs '
+        'only: loss tables, per-level gradient sums and abs-sums, every '
+        '101st gradient element.  The inputs are regenerated from the seeds '
+        'in `tests/_loss_edges.py`.' + (
+            '  Loss table only (the reference\'s own backward fails on an '
+            'in-place write): ' + ', '.join(no_backward) + '.'
+            if no_backward else ''),
+        'Images without a GT box are removed before the reference runs '
+        '(`without_empty`).  On `empty_beside_full`, whose first image has '
+        'none, the reference\'s `loss`: ' + ', '.join(
+            f'{f}: ' + (f'raises {r}' if r else 'runs')
+            for f, r in raises.items()) +
+        ' (`raises_on_empty_<flavour>`); LDv2Head shares LDHead\'s target '
+        'code.  The project defines such an image as all background '
+        '(`tests/_loss_ref64.py`).'])
+
+
 def _manifest(fname, lines):
     """Create or replace the `## fname` section of tests/golden/MANIFEST.md."""
     path = os.path.join(OUT, 'MANIFEST.md')
@@ -1905,6 +2029,8 @@ def main():
         gen_grad_samples([c for c in args.e2e_cases.split(',') if c])
     if 'target_edges' in only:
         gen_target_edges()
+    if 'loss_edges' in only:
+        gen_loss_edges()
 
 
 if __name__ == '__main__':
