@@ -1335,6 +1335,68 @@ int ld_preprocess_batch_aug(const ld_image_aug_t* imgs, int N, int Hpad, int Wpa
                             const float* pad_val, int to_rgb, float* out,
                             ld_stream_t stream);
 
+/* ---- float-image mode: PhotoMetricDistortion in the same launch --------------
+ * LoadImageFromFile(to_float32=True) -> PhotoMetricDistortion -> Expand ->
+ * MinIoURandomCrop -> Resize -> RandomCrop -> RandomFlip -> Normalize -> Pad
+ * (datasets/pipelines/transforms.py:810-902 and the steps above) for a whole
+ * batch in one launch, with no intermediate image.  The geometry fields mean
+ * what they mean in ld_image_aug_t; an output pixel walks back to four taps the
+ * same way.  What differs:
+ *   taps    a tap inside the image loads three bytes, converts them to fp32 and
+ *           runs the photometric chain on that pixel; a tap on the canvas reads
+ *           fill[] as it is (Expand comes after the distortion).
+ *   chain   in the reference's order, every scalar a float32 rounded on the host:
+ *             1  x += delta                       if do_brightness
+ *             2  x *= alpha                       if do_contrast && contrast_mode == 1
+ *             3  BGR -> HSV                       if do_hsv
+ *             4  S *= saturation                  if do_saturation
+ *             5  H += hue; H > 360: H -= 360; H < 0: H += 360    if do_hue
+ *             6  HSV -> BGR                       if do_hsv
+ *             7  x *= alpha                       if do_contrast && contrast_mode == 0
+ *             8  x[c] = x[perm[c]]                (perm = 0, 1, 2: none)
+ *           No clipping anywhere.  do_hsv = 0 (with do_saturation = do_hue = 0)
+ *           is LoadImageFromFile(to_float32=True) without the distortion.
+ *   HSV     restated from OpenCV's published float formulas, fp32 throughout:
+ *             V = max(B, G, R); m = min(B, G, R); diff = V - m
+ *             S = diff / (|V| + FLT_EPSILON); k = 60 / (diff + FLT_EPSILON)
+ *             H = (G - B) * k             if V == R
+ *                 (B - R) * k + 120       else if V == G
+ *                 (R - G) * k + 240       else;          H < 0: H += 360
+ *           and back: S == 0 gives B = G = R = V; else h = H * (6 / 360);
+ *           h < 0: h += 6, else h >= 6: h -= 6; i = floor(h); f = h - i (i
+ *           outside 0..5: i = 0, f = 0); tab = {V, V * (1 - S),
+ *           V * (1 - S * f), V * (1 - S * (1 - f))}; (B, G, R) = tab[] at
+ *           {1,3,0} {1,0,2} {3,0,1} {0,2,1} {0,1,3} {2,1,0} for i = 0 .. 5.
+ *           The host keeps |hue| <= 360, so one wrap each way is enough.
+ *   resize  cv2's float INTER_LINEAR: the same source index and fraction f as the
+ *           8-bit path, coefficients 1 - f and f as floats, horizontal pass then
+ *           vertical pass, no rounding to 8 bits.
+ * Then BGR -> RGB when to_rgb and (v - mean) * std_inv; pad_val outside (out_h,
+ * out_w).  Every operation is a correctly rounded fp32 + - * /, a compare, a
+ * floor or an int conversion (built with -ffp-contract=off), so the output
+ * equals the numpy float32 restatement in tests/_photometric_oracle.py bit for
+ * bit.  Parity status: UNPINNED against cv2 itself (HSV conversions and float
+ * resize); the order of the chain and the float32 scalar rounding are pinned on
+ * the reference's own class (tests/golden/photometric.npz). */
+typedef struct {
+  const unsigned char* data;
+  int32_t src_h, src_w;
+  int32_t canvas_h, canvas_w, img_top, img_left;
+  int32_t win_y, win_x, win_h, win_w;
+  int32_t new_h, new_w;
+  int32_t crop_y, crop_x, out_h, out_w;
+  int32_t flip;
+  float fill[3];      /* B, G, R of Expand's canvas, float32 */
+  float delta, alpha, saturation, hue;
+  int32_t do_brightness, do_contrast, contrast_mode, do_saturation, do_hue, do_hsv;
+  int32_t perm[3];
+  int32_t reserved;
+} ld_image_photo_t;
+int ld_preprocess_batch_photo(const ld_image_photo_t* imgs, int N, int Hpad, int Wpad,
+                              const float* mean, const float* std_inv,
+                              const float* pad_val, int to_rgb, float* out,
+                              ld_stream_t stream);
+
 /* ---- baseline JPEG decode, host half (LoadImageFromFile -> mmcv.imfrombytes ->
  * cv2.imdecode, datasets/pipelines/loading.py:12-71) -------------------------
  * The serial half of a JPEG decode: bytes -> int16 coefficient blocks, the input

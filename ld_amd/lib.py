@@ -201,6 +201,25 @@ class ImageAugT(C.Structure):  # ld_image_aug_t
                 ('fill', C.c_uint8 * 4)]
 
 
+class ImagePhotoT(C.Structure):  # ld_image_photo_t
+    _fields_ = [('data', C.c_void_p), ('src_h', C.c_int32),
+                ('src_w', C.c_int32), ('canvas_h', C.c_int32),
+                ('canvas_w', C.c_int32), ('img_top', C.c_int32),
+                ('img_left', C.c_int32), ('win_y', C.c_int32),
+                ('win_x', C.c_int32), ('win_h', C.c_int32),
+                ('win_w', C.c_int32), ('new_h', C.c_int32),
+                ('new_w', C.c_int32), ('crop_y', C.c_int32),
+                ('crop_x', C.c_int32), ('out_h', C.c_int32),
+                ('out_w', C.c_int32), ('flip', C.c_int32),
+                ('fill', C.c_float * 3), ('delta', C.c_float),
+                ('alpha', C.c_float), ('saturation', C.c_float),
+                ('hue', C.c_float), ('do_brightness', C.c_int32),
+                ('do_contrast', C.c_int32), ('contrast_mode', C.c_int32),
+                ('do_saturation', C.c_int32), ('do_hue', C.c_int32),
+                ('do_hsv', C.c_int32), ('perm', C.c_int32 * 3),
+                ('reserved', C.c_int32)]
+
+
 class JpegInfoT(C.Structure):  # ld_jpeg_info_t
     _fields_ = [('width', C.c_int32), ('height', C.c_int32),
                 ('ncomp', C.c_int32), ('hmax', C.c_int32), ('vmax', C.c_int32),
@@ -318,6 +337,11 @@ SIGNATURES = {
                                           C.POINTER(C.c_float),
                                           C.POINTER(C.c_float), _i32, _vp,
                                           _vp]),
+    'ld_preprocess_batch_photo': (C.c_int, [_vp, _i32, _i32, _i32,
+                                            C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float),
+                                            C.POINTER(C.c_float), _i32, _vp,
+                                            _vp]),
     'ld_jpeg_parse': (C.c_int, [_vp, _sz, C.POINTER(JpegInfoT)]),
     'ld_jpeg_entropy_decode': (C.c_int, [_vp, _sz, C.POINTER(JpegInfoT), _vp]),
     'ld_jpeg_entropy_decode_batch': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32,

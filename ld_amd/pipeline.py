@@ -30,6 +30,14 @@ draws and transforms the boxes exactly as the reference does
 tests/golden/augment.npz), the kernel walks every output pixel back through
 crop, resize, window and canvas.  The plain pipeline keeps the plain launch.
 
+Float-image mode -- LoadImageFromFile(to_float32=True), with or without
+PhotoMetricDistortion (transforms.py:810-902) in front of the steps above --
+is a third launch (``ld_preprocess_batch_photo``): the host makes the
+distortion's draws in the reference's order (``photometric_draw``, pinned on
+the reference's own class in tests/golden/photometric.npz), the kernel runs
+the pointwise chain on each tap, fills Expand's canvas with the float mean and
+resizes in float32.
+
 There is no CPU fallback for the image arithmetic: DevicePipeline refuses to
 run without the HIP library and a device.
 """
@@ -209,6 +217,38 @@ def crop_bboxes(bboxes, offset_w, offset_h, img_shape, clip=True):
     return b, (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
 
 
+def photometric_draw(rng, brightness_delta=32, contrast_range=(0.5, 1.5),
+                     saturation_range=(0.5, 1.5), hue_delta=18):
+    """PhotoMetricDistortion.__call__'s draws (transforms.py:858-899), every
+    one of them in its order with the reference's calls: ``delta``, ``alpha``,
+    ``saturation``, ``hue`` as drawn (None when ``randint(2)`` skipped the
+    step), ``mode`` (1: contrast before the HSV step, 0: after it) and
+    ``perm`` (a tuple, or None).  The reference applies the Python floats in
+    place to a float32 array, where they act as float32 scalars; the rounding
+    is the descriptor's."""
+    d = dict(delta=None, mode=0, alpha=None, saturation=None, hue=None,
+             perm=None)
+    if rng.randint(2):
+        d['delta'] = float(rng.uniform(-brightness_delta, brightness_delta))
+    d['mode'] = int(rng.randint(2))
+    if d['mode'] == 1:
+        if rng.randint(2):
+            d['alpha'] = float(rng.uniform(contrast_range[0],
+                                           contrast_range[1]))
+    if rng.randint(2):
+        d['saturation'] = float(rng.uniform(saturation_range[0],
+                                            saturation_range[1]))
+    if rng.randint(2):
+        d['hue'] = float(rng.uniform(-hue_delta, hue_delta))
+    if d['mode'] == 0:
+        if rng.randint(2):
+            d['alpha'] = float(rng.uniform(contrast_range[0],
+                                           contrast_range[1]))
+    if rng.randint(2):
+        d['perm'] = tuple(int(v) for v in rng.permutation(3))
+    return d
+
+
 _STEP_RANK = {'Expand': 0, 'MinIoURandomCrop': 1, 'Resize': 2, 'RandomCrop': 3,
               'RandomFlip': 4, 'Normalize': 4, 'Pad': 5}
 
@@ -230,10 +270,30 @@ class DevicePipeline:
                  to_rgb=True, size_divisor=32, multiscale_mode='range',
                  ratio_range=None, bbox_clip_border=True, device=None,
                  crop=None, expand=None, min_iou_crop=None, pad_size=None,
-                 pad_val=0):
+                 pad_val=0, to_float32=False, photo=None,
+                 min_gt_bbox_wh=None):
         """``crop`` / ``expand`` / ``min_iou_crop``: the keyword dicts of the
         reference's RandomCrop / Expand / MinIoURandomCrop (or None);
-        ``pad_size`` (H, W) and ``pad_val``: Pad(size=, pad_val=)."""
+        ``pad_size`` (H, W) and ``pad_val``: Pad(size=, pad_val=).
+        ``to_float32``: LoadImageFromFile(to_float32=True), the float-image
+        mode (float Expand fill, float resize); ``photo``: the keyword dict
+        of PhotoMetricDistortion (or None), which needs that mode.
+        ``min_gt_bbox_wh``: FilterAnnotations' (w, h), applied first."""
+        if photo is not None and not to_float32:
+            # transforms.py:855 asserts img.dtype == np.float32
+            raise ValueError(
+                'photo= (PhotoMetricDistortion) needs to_float32=True: the '
+                'reference asserts a float32 image')
+        self.float_mode = bool(to_float32)
+        self.photo = None if photo is None else dict(
+            dict(brightness_delta=32, contrast_range=(0.5, 1.5),
+                 saturation_range=(0.5, 1.5), hue_delta=18), **photo)
+        if self.photo is not None and not abs(self.photo['hue_delta']) <= 360:
+            raise ValueError(
+                f"hue_delta {self.photo['hue_delta']}: the one wrap each way "
+                'of the reference needs |hue_delta| <= 360')
+        self.min_gt_bbox_wh = None if min_gt_bbox_wh is None else tuple(
+            float(v) for v in min_gt_bbox_wh)
         if pad_size is not None and size_divisor is not None:
             # transforms.py:495 asserts that only one of them is given
             raise ValueError(
@@ -256,8 +316,11 @@ class DevicePipeline:
         if self.expand is not None:
             m = self.expand['mean']
             m = m[::-1] if self.expand['to_rgb'] else m
+            # img.dtype is float32 after LoadImageFromFile(to_float32=True)
             self.expand_fill = tuple(
-                int(v) for v in np.full((3,), m, dtype=np.uint8))
+                float(v) for v in np.full((3,), m, dtype=np.float32)) \
+                if self.float_mode else tuple(
+                    int(v) for v in np.full((3,), m, dtype=np.uint8))
         self.min_iou_crop = None if min_iou_crop is None else dict(
             dict(min_ious=(0.1, 0.3, 0.5, 0.7, 0.9), min_crop_size=0.3,
                  bbox_clip_border=True), **min_iou_crop)
@@ -269,7 +332,8 @@ class DevicePipeline:
         # ld_preprocess_batch_aug; the plain pipeline keeps the plain launch
         self.augmented = bool(
             self.crop or self.expand or self.min_iou_crop or self.pad_size
-            or not self.keep_ratio or self.pad_val.any())
+            or not self.keep_ratio or self.pad_val.any() or self.float_mode
+            or self.min_gt_bbox_wh)
         self.img_scale = img_scale
         self.multiscale_mode = multiscale_mode
         self.ratio_range = ratio_range
@@ -291,11 +355,31 @@ class DevicePipeline:
         loading / formatting steps this class subsumes.  The optional
         augmentations are taken in one order only: [Expand],
         [MinIoURandomCrop], Resize, [RandomCrop], RandomFlip / Normalize in
-        either order, Pad last."""
+        either order, Pad last.  LoadImageFromFile(to_float32=True) selects
+        the float-image mode; PhotoMetricDistortion is taken only after it and
+        before every step of that list, FilterAnnotations only before both."""
         kw = {}
         prev = None
         for step in train_pipeline:
             t = step['type']
+            if t == 'LoadImageFromFile':
+                if step.get('to_float32', False):
+                    kw['to_float32'] = True
+                continue
+            if t == 'PhotoMetricDistortion':
+                # anywhere else the reference fails its float32 assertion or
+                # distorts the canvas too: not this launch
+                if not kw.get('to_float32') or prev is not None or \
+                        'photo' in kw:
+                    raise NotImplementedError(f'pipeline step {t}')
+                kw['photo'] = {k: v for k, v in step.items() if k != 'type'}
+                continue
+            if t == 'FilterAnnotations':
+                if prev is not None or 'photo' in kw or \
+                        'min_gt_bbox_wh' in kw:
+                    raise NotImplementedError(f'pipeline step {t}')
+                kw['min_gt_bbox_wh'] = step['min_gt_bbox_wh']
+                continue
             if t in _STEP_RANK:
                 if prev is not None and _STEP_RANK[t] < _STEP_RANK[prev]:
                     raise NotImplementedError(
@@ -330,9 +414,14 @@ class DevicePipeline:
                 kw['size_divisor'] = step.get('size_divisor')
                 kw['pad_size'] = step.get('size')
                 kw['pad_val'] = step.get('pad_val', 0)
-            elif t not in ('LoadImageFromFile', 'LoadAnnotations',
-                           'DefaultFormatBundle', 'Collect'):
+            elif t not in ('LoadAnnotations', 'DefaultFormatBundle',
+                           'Collect'):
                 raise NotImplementedError(f'pipeline step {t}')
+        if kw.get('to_float32') and 'size_divisor' not in kw:
+            # the stock SSD pipelines have no Pad step: collate pads to the
+            # batch maximum only.  (An 8-bit pipeline without Pad keeps the
+            # constructor's size_divisor, as it always has.)
+            kw['size_divisor'] = None
         return cls(device=device, **kw)
 
     @classmethod
@@ -462,7 +551,8 @@ class DevicePipeline:
 
     def plan_image(self, shape, rng=np.random, gt_bboxes=None, gt_labels=None,
                    gt_bboxes_ignore=None):
-        """One image through Expand -> MinIoURandomCrop -> Resize ->
+        """One image through [FilterAnnotations] -> [PhotoMetricDistortion]
+        -> Expand -> MinIoURandomCrop -> Resize ->
         RandomCrop -> RandomFlip on the host: every draw the reference makes,
         in its order, and its box arithmetic on the two bbox fields.  The plan
         carries the geometry the kernel needs (``canvas`` (h, w, top, left),
@@ -471,13 +561,29 @@ class DevicePipeline:
         transformed ``gt_bboxes`` / ``gt_labels`` / ``gt_bboxes_ignore`` and
         which input rows they are (``keep`` / ``keep_ignore``).  A RandomCrop
         that the reference answers with None gives ``dict(rejected=True)``;
-        no draw is made after it."""
+        no draw is made after it.  So does a FilterAnnotations that keeps no
+        box (loading.py:445-452), before any draw.  In float mode the plan
+        also carries ``photo``: the draws of ``photometric_draw``, made before
+        Expand's (None without PhotoMetricDistortion), and ``fill`` is the
+        float mean."""
         h, w = shape
         boxes = np.zeros((0, 4), np.float32) if gt_bboxes is None else \
             np.array(gt_bboxes, np.float32).reshape(-1, 4)
         ignore = np.zeros((0, 4), np.float32) if gt_bboxes_ignore is None \
             else np.array(gt_bboxes_ignore, np.float32).reshape(-1, 4)
         keep, keep_ig = np.arange(len(boxes)), np.arange(len(ignore))
+        # FilterAnnotations (loading.py:445-458): gt_bboxes only
+        if self.min_gt_bbox_wh is not None:
+            big = ((boxes[:, 2] - boxes[:, 0]) > self.min_gt_bbox_wh[0]) & \
+                ((boxes[:, 3] - boxes[:, 1]) > self.min_gt_bbox_wh[1])
+            if not big.any():
+                return dict(rejected=True, ori_shape=(h, w, 3))
+            boxes, keep = boxes[big], keep[big]
+        # PhotoMetricDistortion (transforms.py:858-899): its draws come first
+        extra = {}
+        if self.float_mode:
+            extra['photo'] = None if self.photo is None else \
+                photometric_draw(rng, **self.photo)
         # Expand (transforms.py:945-997)
         canvas = (h, w, 0, 0)
         if self.expand is not None:
@@ -562,7 +668,8 @@ class DevicePipeline:
                     resized=(new_h, new_w), crop=crop, fill=self.expand_fill,
                     mode=None if mode is None else float(mode),
                     gt_bboxes=boxes, gt_labels=labels,
-                    gt_bboxes_ignore=ignore, keep=keep, keep_ignore=keep_ig)
+                    gt_bboxes_ignore=ignore, keep=keep, keep_ignore=keep_ig,
+                    **extra)
 
     def transform_boxes(self, bboxes, plan):
         if 'gt_bboxes' in plan:
@@ -590,6 +697,37 @@ class DevicePipeline:
         fill = plan.get('fill', (0, 0, 0))
         for c in range(3):
             d.fill[c] = int(fill[c])
+
+    @staticmethod
+    def fill_photo_descriptor(d, plan, shape):
+        """The variant for an ``ld_image_photo_t``: the same geometry, the
+        fill as float32 and the draws of ``plan['photo']`` (missing or None:
+        the identity chain without the HSV round trip).  The c_float fields
+        round each drawn double to float32, as numpy does when the reference
+        applies it to its float32 image."""
+        fill = plan.get('fill', (0, 0, 0))
+        DevicePipeline.fill_descriptor(d, dict(plan, fill=(0, 0, 0)), shape)
+        for c in range(3):
+            d.fill[c] = float(fill[c])
+        ph = plan.get('photo')
+        on = ph is not None
+        get = (lambda k: ph[k]) if on else (lambda k: None)
+        for field, key, flag, neutral in (
+                ('delta', 'delta', 'do_brightness', 0.0),
+                ('alpha', 'alpha', 'do_contrast', 1.0),
+                ('saturation', 'saturation', 'do_saturation', 1.0),
+                ('hue', 'hue', 'do_hue', 0.0)):
+            v = get(key)
+            setattr(d, flag, int(v is not None))
+            setattr(d, field, neutral if v is None else float(v))
+        d.contrast_mode = int(ph['mode']) if on else 0
+        d.do_hsv = int(on)
+        perm = (get('perm') or (0, 1, 2))
+        if sorted(perm) != [0, 1, 2]:
+            raise ValueError(f'perm {perm} is not a permutation of 0, 1, 2')
+        for c in range(3):
+            d.perm[c] = int(perm[c])
+        d.reserved = 0
 
     def batch_shape(self, plans):
         """(Hpad, Wpad) of the batch tensor.  Pad(size_divisor) per image, then
@@ -686,8 +824,9 @@ class DevicePipeline:
     def _call_augmented(self, images, gt_bboxes, gt_labels, rng, plans, stream,
                         gt_bboxes_ignore):
         """``__call__`` of a pipeline with augmentations: the same staging
-        copy, then ONE ``ld_preprocess_batch_aug`` launch; the annotations
-        are the plans' own (transformed and selected by ``plan_image``)."""
+        copy, then ONE ``ld_preprocess_batch_aug`` launch (float mode: ONE
+        ``ld_preprocess_batch_photo`` launch); the annotations are the
+        plans' own (transformed and selected by ``plan_image``)."""
         from . import lib as L
         lib = L.get_lib()  # raises when the HIP library is missing
         if self.device.type != 'cuda':
@@ -713,12 +852,14 @@ class DevicePipeline:
                 raise ValueError('images must be uint8 HWC with 3 channels')
             stage[int(o):int(o) + s].copy_(t.reshape(-1))
         raw = stage.to(self.device, non_blocking=True)
-        desc = (L.ImageAugT * N)()
+        desc = ((L.ImagePhotoT if self.float_mode else L.ImageAugT) * N)()
+        fill = self.fill_photo_descriptor if self.float_mode else \
+            self.fill_descriptor
         for i, (p, (h, w)) in enumerate(zip(plans, shapes)):
             desc[i].data = raw.data_ptr() + int(offs[i])
             desc[i].src_h, desc[i].src_w = h, w
             desc[i].flip = int(p['flip'])
-            self.fill_descriptor(desc[i], p, (h, w))
+            fill(desc[i], p, (h, w))
         dbytes = torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8)
         ddesc = dbytes.pin_memory().to(self.device, non_blocking=True)
         out = torch.empty(N, 3, Hpad, Wpad, dtype=torch.float32,
@@ -728,10 +869,11 @@ class DevicePipeline:
         mean = (C.c_float * 3)(*self.mean.tolist())
         sinv = (C.c_float * 3)(*self.std_inv.tolist())
         pad = (C.c_float * 3)(*self.pad_val.tolist())
-        L.check(lib.ld_preprocess_batch_aug(
+        entry = 'ld_preprocess_batch_photo' if self.float_mode else \
+            'ld_preprocess_batch_aug'
+        L.check(getattr(lib, entry)(
             ddesc.data_ptr(), N, Hpad, Wpad, mean, sinv, pad,
-            int(self.to_rgb), out.data_ptr(), s.cuda_stream),
-            'ld_preprocess_batch_aug')
+            int(self.to_rgb), out.data_ptr(), s.cuda_stream), entry)
         div = self.size_divisor or 1
         metas = []
         for p in plans:
