@@ -135,6 +135,36 @@ typedef struct {
 #define LD_LOSS_BBOX_IOU_LINEAR 2 /* IoULoss(linear=True): 1 - IoU */
 #define LD_LOSS_BBOX_DIOU 3
 #define LD_LOSS_BBOX_CIOU 4
+/* Plain ATSSHead / RetinaHead (atss_head.py:145-296, anchor_head.py:376-495):
+ * the reg maps carry the 4 DeltaXYWH deltas of an anchor instead of 68
+ * distribution logits.  Combined with LD_LOSS_ATSS or LD_LOSS_RETINA (which keep
+ * their class, centerness and normaliser rules); the block is then run as
+ * ld_loss_delta_prepass -> ld_loss_delta_pos -> ld_loss_main_parts(
+ * LD_LOSS_PART_CLS) [-> ld_loss_centerness] -> ld_loss_finalize: no REG / IM
+ * launch, no teacher maps, the DFL, LD, VLR-LD, KD and IM rows of the table are
+ * zero (set lw_kd = 0).  The coder travels beside hp in an ld_delta_t. */
+#define LD_LOSS_DELTA 32
+
+/* DeltaXYWHBBoxCoder (delta_xywh_bbox_coder.py:26-237) and what the box term of
+ * an LD_LOSS_DELTA block does with it. */
+typedef struct {
+  float means[4], stds[4]; /* target_means, target_stds */
+  float max_ratio;         /* |log(wh_ratio_clip)|: the clamp of dw, dh in decode */
+  float beta;              /* SmoothL1Loss beta (LD_DELTA_SMOOTH_L1) */
+  int32_t num_base;        /* anchors per cell of the explicit anchor list; 0 = the
+                              implicit square anchor of side anchor_scale * stride */
+  int32_t box_term;        /* LD_DELTA_* below */
+} ld_delta_t;
+/* the box loss of the positives:
+ *   DECODED    hp's LD_LOSS_BBOX_* loss on delta2bbox(anchor, pred) against the
+ *              target box (LD_LOSS_ATSS: the target encoded and decoded again,
+ *              atss_head.py:193-205; LD_LOSS_RETINA: reg_decoded_bbox=True,
+ *              anchor_head.py:414-424)
+ *   L1 / SMOOTH_L1  on pred - bbox2delta(anchor, gt), summed over the four
+ *              deltas (reg_decoded_bbox=False; LD_LOSS_RETINA only) */
+#define LD_DELTA_DECODED 0
+#define LD_DELTA_L1 1
+#define LD_DELTA_SMOOTH_L1 2
 
 /* ---- library ------------------------------------------------------------ */
 /* ABI version of this header; bump on any signature change. */
@@ -332,6 +362,35 @@ int ld_loss_main_parts(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                        void* workspace, size_t workspace_bytes, int parts,
                        ld_stream_t stream);
 
+/* The two launches an LD_LOSS_DELTA block has of its own (hp->flags must carry
+ * LD_LOSS_DELTA and exactly one of LD_LOSS_ATSS / LD_LOSS_RETINA).
+ * reg / grad_reg: (N, 4, H_l, W_l) maps (LD_LOSS_RETINA: the (N * B, 4, ...)
+ * pseudo-image views).  anchors: the explicit (num_anchors * num_base, 4) list,
+ * row (cell * num_base + b), when delta->num_base > 0 (pseudo-image n uses base
+ * anchor n % num_base); NULL for the implicit square anchor.  bbox_targets hold
+ * the matched GT boxes in pixels, as the target launches write them.
+ *
+ * prepass: score = the ATSS centerness target of the positives from the anchor
+ * centre and the encoded-then-decoded GT (atss_head.py:298-313; zero with
+ * LD_LOSS_RETINA), weight_targets = 0, norm as ld_loss_prepass leaves it.
+ * pos: the box term, forward and gradient through the decode -- the gradient
+ * of a clamped dw / dh is zero -- written dense into grad_reg (zeros away from
+ * the positives), and the class-softmax statistics ld_loss_main_parts(CLS)
+ * reads.  Same workspace as the other parts. */
+int ld_loss_delta_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                          const ld_delta_t* delta, const float* anchors,
+                          const int64_t* labels, const float* bbox_targets,
+                          const int32_t* counts, float* weight_targets, float* score,
+                          float* norm, void* workspace, size_t workspace_bytes,
+                          ld_stream_t stream);
+int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                      const ld_delta_t* delta, const float* anchors,
+                      const ld_maps_t* cls, const ld_maps_t* reg,
+                      const int64_t* labels, const float* bbox_targets,
+                      const float* score, const float* norm, const float* upstream,
+                      const ld_maps_t* grad_reg, void* workspace,
+                      size_t workspace_bytes, ld_stream_t stream);
+
 /* The 'gibox' imitation region (LDHead.get_gi_region, ld_head.py:613-637;
  * LDv2Head: ld_gflv2.py:619-644 with hp->flags & LD_LOSS_PROB_CLS): per level,
  * over all cells of all images, the General-Instance score max_c |teacher -
@@ -398,6 +457,26 @@ int ld_diou_rows(const float* pred, const float* target, const float* weight,
 int ld_ciou_rows(const float* pred, const float* target, const float* weight,
                  int64_t rows, float eps, float gscale, float* loss_rows,
                  float* grad, ld_stream_t stream);
+/* l1_loss / smooth_l1_loss, smooth_l1_loss.py:9-56, ELEMENT-wise: pred, target,
+ * weight (nullable), loss and grad all hold n floats; loss[i] = weight[i] *
+ * l(pred[i] - target[i]), grad[i] = gscale * weight[i] * l'(...) (0 at a zero
+ * difference; |d| < beta takes the quadratic branch, |d| == beta the linear). */
+int ld_l1_rows(const float* pred, const float* target, const float* weight,
+               int64_t n, float gscale, float* loss, float* grad,
+               ld_stream_t stream);
+int ld_smooth_l1_rows(const float* pred, const float* target, const float* weight,
+                      int64_t n, float beta, float gscale, float* loss,
+                      float* grad, ld_stream_t stream);
+/* DeltaXYWHBBoxCoder.encode / decode (bbox2delta / delta2bbox,
+ * delta_xywh_bbox_coder.py:87-237) on (rows, 4) boxes.  decode: max_hw =
+ * host float[2] (height, width) clips the boxes to [0, w] x [0, h]; NULL = no
+ * clip (max_shape=None or clip_border=False). */
+int ld_delta_encode_rows(const ld_delta_t* delta, const float* boxes,
+                         const float* gt, int64_t rows, float* deltas,
+                         ld_stream_t stream);
+int ld_delta_decode_rows(const ld_delta_t* delta, const float* boxes,
+                         const float* deltas, int64_t rows, const float* max_hw,
+                         float* out, ld_stream_t stream);
 /* Integral.forward, gfl_head.py:32-44: (rows, 4*(reg_max+1)) -> (rows, 4);
  * backward: grad_in (rows,4) -> grad (rows, 68) */
 int ld_integral_rows(const float* x, int64_t rows, float* out,
@@ -1500,17 +1579,27 @@ int ld_get_bboxes_voting(const ld_geom_t* g, const ld_maps_t* cls, const ld_maps
  * ``num_base`` > 1 (RetinaGFLHead._get_bboxes, retina_gfl_head.py:301-412): the
  * maps are (N, num_base * C, H, W) / (N, num_base * 68, H, W); candidates are
  * the rows (cell, base anchor) in that order, top-k per level over all of
- * them, decoded about the shared cell centre.  Workspace: the _ex_ size. */
+ * them, decoded about the shared cell centre.  Workspace: the _ex_ size.
+ * LD_INFER_DELTA (ATSSHead / RetinaHead._get_bboxes, atss_head.py:376-508,
+ * anchor_head.py:591-727): the reg maps are (N, num_base * 4, H, W) DeltaXYWH
+ * deltas; a candidate is decoded with delta2bbox about its anchor and clipped to
+ * img_shape (``delta``: the coder, required; ``anchors``: the explicit
+ * (cells * num_base, 4) list in candidate-row order, or NULL with num_base = 1
+ * for the square anchor of side anchor_scale * stride).  reg_max is ignored.
+ * Everything around the decode -- keys, top-k, centerness factor, NMS, rescale
+ * -- is unchanged.  Without the flag ``delta`` / ``anchors`` are not read. */
 #define LD_INFER_VOTING 1
 #define LD_INFER_PROB 2
 #define LD_INFER_POINTS 4
+#define LD_INFER_DELTA 16 /* 8 is LD_AUG_RESCALE of ld_aug_merge_nms */
 size_t ld_get_bboxes_ex_workspace_bytes(const ld_geom_t* g, int num_classes,
                                        int num_base, int nms_pre);
 int ld_get_bboxes_ex(const ld_geom_t* g, const ld_maps_t* cls, const ld_maps_t* reg,
                      const ld_maps_t* ctr, int num_classes, int num_base,
                      int reg_max, const float* img_hw,
                      const float* scale_factors, int nms_pre, float score_thr,
-                     float iou_thr, int max_per_img, int flags, float* dets,
+                     float iou_thr, int max_per_img, int flags,
+                     const ld_delta_t* delta, const float* anchors, float* dets,
                      int64_t* labels, int32_t* counts, void* workspace,
                      size_t workspace_bytes, ld_stream_t stream);
 /* get_bboxes(with_nms=False) of the same heads: stages 1-3 only (per-level top
@@ -1524,7 +1613,8 @@ int ld_get_bboxes_pre_nms(const ld_geom_t* g, const ld_maps_t* cls,
                           const ld_maps_t* reg, const ld_maps_t* ctr,
                           int num_classes, int num_base, int reg_max,
                           const float* img_hw, const float* scale_factors,
-                          int nms_pre, int flags, float* boxes, float* scores,
+                          int nms_pre, int flags, const ld_delta_t* delta,
+                          const float* anchors, float* boxes, float* scores,
                           float* factors, void* workspace, size_t workspace_bytes,
                           ld_stream_t stream);
 

@@ -24,6 +24,7 @@ from . import registry  # noqa: F401,E402
 from .config import Config, ConfigDict  # noqa: F401
 from .lib import LdError  # noqa: F401
 from . import core, losses, resnet, fpn, heads, detectors  # noqa: F401,E402
+from . import plain_heads  # noqa: F401,E402
 from .registry import (build_backbone, build_detector, build_head,  # noqa
                        build_loss, build_neck)
 from .evaluation import MapAccumulator, eval_map  # noqa: F401,E402

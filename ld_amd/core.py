@@ -1,7 +1,8 @@
 """mmdet.core pieces on the LD path with their reference names and call
 signatures: AnchorGenerator, BboxOverlaps2D,
 ATSSAssigner (+ get_vlr_region), PseudoSampler, AssignResult, SamplingResult,
-DeltaXYWHBBoxCoder (constructed by AnchorHead's default, never called here),
+DeltaXYWHBBoxCoder (ld_delta_encode_rows / ld_delta_decode_rows; inside the
+plain heads the fused loss block and get_bboxes apply it themselves),
 reduce_mean, distance2bbox / bbox2distance.  Arithmetic goes through libldhip.so.
 """
 import ctypes as C
@@ -314,18 +315,68 @@ class PseudoSampler:
 
 @BBOX_CODERS.register_module()
 class DeltaXYWHBBoxCoder:
-    """Constructed by AnchorHead's default bbox_coder (anchor_head.py:45-49)
-    but never called on the GFL/LD path: registrable stub."""
+    """core/bbox/coder/delta_xywh_bbox_coder.py:9-237 on the device
+    (ld_delta_encode_rows / ld_delta_decode_rows, fp32).  Constants of the
+    graph: no gradient flows through ``encode`` / ``decode`` (the heads' loss
+    block differentiates the decode itself)."""
 
     def __init__(self, target_means=(0., 0., 0., 0.),
                  target_stds=(1., 1., 1., 1.), clip_border=True):
         self.means, self.stds = target_means, target_stds
         self.clip_border = clip_border
 
-    def encode(self, bboxes, gt_bboxes):
-        raise NotImplementedError('DeltaXYWHBBoxCoder is not on the LD path')
+    def delta_t(self, wh_ratio_clip=16 / 1000, num_base=0, box_term='decoded',
+                beta=1.0):
+        """The coder as the ld_delta_t the kernels take."""
+        if len(self.means) != 4 or len(self.stds) != 4:
+            raise ValueError('DeltaXYWHBBoxCoder: four target_means / '
+                             'target_stds')
+        d = L.DeltaT()
+        for k in range(4):
+            d.means[k], d.stds[k] = float(self.means[k]), float(self.stds[k])
+        d.max_ratio = abs(math.log(wh_ratio_clip))
+        d.beta, d.num_base = float(beta), int(num_base)
+        d.box_term = L.LD_DELTA_TERMS[box_term]
+        return d
 
-    decode = encode
+    @staticmethod
+    def _rows(t, name):
+        if t.dim() != 2 or t.shape[1] != 4:
+            raise NotImplementedError(
+                f'DeltaXYWHBBoxCoder: {name} of shape {tuple(t.shape)}; the '
+                'row kernels take (n, 4)')
+        return L.require_device(t.detach().contiguous(), torch.float32, name)
+
+    def encode(self, bboxes, gt_bboxes):
+        assert bboxes.size(0) == gt_bboxes.size(0)
+        assert bboxes.size(-1) == gt_bboxes.size(-1) == 4
+        b, g = self._rows(bboxes, 'bboxes'), self._rows(gt_bboxes, 'gt_bboxes')
+        out = torch.empty_like(b)
+        if b.shape[0] == 0:
+            return out
+        L.check(L.get_lib().ld_delta_encode_rows(
+            C.byref(self.delta_t()), L.ptr(b), L.ptr(g), b.shape[0],
+            L.ptr(out), L.stream_ptr(b.device)), 'ld_delta_encode_rows')
+        return out
+
+    def decode(self, bboxes, pred_bboxes, max_shape=None,
+               wh_ratio_clip=16 / 1000):
+        assert pred_bboxes.size(0) == bboxes.size(0)
+        b = self._rows(bboxes, 'bboxes')
+        d = self._rows(pred_bboxes, 'pred_bboxes')
+        hw = None
+        if self.clip_border and max_shape is not None:
+            if isinstance(max_shape, torch.Tensor):
+                max_shape = max_shape.reshape(-1).tolist()
+            hw = (C.c_float * 2)(float(max_shape[0]), float(max_shape[1]))
+        out = torch.empty_like(b)
+        if b.shape[0] == 0:
+            return out
+        L.check(L.get_lib().ld_delta_decode_rows(
+            C.byref(self.delta_t(wh_ratio_clip)), L.ptr(b), L.ptr(d),
+            b.shape[0], hw, L.ptr(out), L.stream_ptr(b.device)),
+            'ld_delta_decode_rows')
+        return out
 
 
 # ---------------------------------------------------------- MaxIoU assigner --

@@ -251,12 +251,17 @@ __global__ __launch_bounds__(kSortThreads) void infer_topk_sort_kernel(
 }
 
 // ---- 3. decode -----------------------------------------------------------------
+// DELTA (LD_INFER_DELTA): the reg maps hold B * 4 DeltaXYWH deltas; the candidate
+// is decoded about its anchor -- row (level's first cell * B + a) of `anchors`,
+// or the square of side anchor_scale * stride -- and clipped to the image
+// (delta2bbox with max_shape, atss_head.py:470-480, anchor_head.py:690-700).
+template <bool DELTA>
 __global__ __launch_bounds__(256) void infer_decode_kernel(
     Plan p, ld_maps_t cls, ld_maps_t reg, ld_maps_t ctr,
     const unsigned long long* keys, const float* img_hw, const float* scale_factors,
     float score_thr, float* boxes,
     float* scores, unsigned long long* cand, int* cand_count, unsigned* max_coord,
-    float* factors) {
+    float* factors, ld_delta_t dc, const float* anchors, int anchor_scale) {
   const int n = blockIdx.y;
   const int slot = blockIdx.x * 256 + threadIdx.x;
   if (slot >= p.Ktot) return;
@@ -276,21 +281,45 @@ __global__ __launch_bounds__(256) void infer_decode_kernel(
   // FCOS points: + stride // 2 (fcos_gfl_head.py:548-558)
   const int half = p.points ? s / 2 : 0;
   const float cx = (float)(x * s + half), cy = (float)(y * s + half);
-  // Integral * stride (gfl_head.py:32-44, :405)
   const float* rbase = reg.ptr[l] + (size_t)n * reg.stride_n[l] +
-                       (size_t)b * 68 * reg.stride_c[l] + cell;
+                       (size_t)b * (DELTA ? 4 : 68) * reg.stride_c[l] + cell;
   float d[4];
-#pragma unroll
-  for (int side = 0; side < 4; ++side) {
-    float sv[17], pv[17];
-#pragma unroll
-    for (int k = 0; k < 17; ++k)
-      sv[k] = rbase[(size_t)(side * 17 + k) * reg.stride_c[l]];
-    d[side] = softmax_expect<17>(sv, pv) * (float)s;
-  }
-  // distance2bbox + clamp to the image (transforms.py:135-154)
   const float Hi = img_hw[n * 2 + 0], Wi = img_hw[n * 2 + 1];
-  float bx[4] = {cx - d[0], cy - d[1], cx + d[2], cy + d[3]};
+  float bx[4];
+  if (DELTA) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = rbase[(size_t)k * reg.stride_c[l]];
+    ld::Box an;
+    if (anchors) {
+      size_t first = 0;  // anchors of the levels before l
+      for (int i = 0; i < l; ++i) first += (size_t)p.A[i];
+      const float4 q = reinterpret_cast<const float4*>(anchors)[first + a];
+      an = ld::Box{q.x, q.y, q.z, q.w};
+    } else {
+      an = ld::anchor_box(x, y, s, 0.5f * (float)(anchor_scale * s));
+    }
+    const ld::Box o = ld::delta2bbox(an, d, dc.means, dc.stds, dc.max_ratio, nullptr);
+    bx[0] = o.x1;
+    bx[1] = o.y1;
+    bx[2] = o.x2;
+    bx[3] = o.y2;
+  } else {
+    // Integral * stride (gfl_head.py:32-44, :405)
+#pragma unroll
+    for (int side = 0; side < 4; ++side) {
+      float sv[17], pv[17];
+#pragma unroll
+      for (int k = 0; k < 17; ++k)
+        sv[k] = rbase[(size_t)(side * 17 + k) * reg.stride_c[l]];
+      d[side] = softmax_expect<17>(sv, pv) * (float)s;
+    }
+    // distance2bbox (transforms.py:135-154)
+    bx[0] = cx - d[0];
+    bx[1] = cy - d[1];
+    bx[2] = cx + d[2];
+    bx[3] = cy + d[3];
+  }
+  // clamp to the image
   bx[0] = fminf(fmaxf(bx[0], 0.f), Wi);
   bx[1] = fminf(fmaxf(bx[1], 0.f), Hi);
   bx[2] = fminf(fmaxf(bx[2], 0.f), Wi);
@@ -680,7 +709,9 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
                            ld_stream_t stream_, bool voting, bool prob = false,
                            const ld_maps_t* ctr = nullptr, bool points = false,
                            int num_base = 1, float* pre_boxes = nullptr,
-                           float* pre_scores = nullptr, float* pre_factors = nullptr) {
+                           float* pre_scores = nullptr, float* pre_factors = nullptr,
+                           const ld_delta_t* delta = nullptr,
+                           const float* anchors = nullptr) {
   Plan p;
   if (int e = make_plan(g, num_classes, nms_pre, &p, num_base)) return e;
   p.prob = prob ? 1 : 0;
@@ -692,7 +723,13 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
   if (!cls || !reg || !img_hw) return LD_EINVAL;
   if (pre_only ? !pre_scores : (!dets || !labels || !counts)) return LD_EINVAL;
   if (pre_only) max_per_img = 1;  // unused
-  if (reg_max != 16) return LD_EUNSUPPORTED;  // 17-bin Integral only
+  if (!delta && reg_max != 16) return LD_EUNSUPPORTED;  // 17-bin Integral only
+  if (delta) {
+    if (points || !(delta->max_ratio >= 0.0f)) return LD_EINVAL;
+    // an explicit list gives every (cell, base) row its anchor; the implicit
+    // square anchor exists for one anchor per cell only
+    if (!anchors && num_base != 1) return LD_EINVAL;
+  }
   if (max_per_img < 1 || max_per_img > kMaxKeep) return LD_EUNSUPPORTED;
   // a negative threshold would suppress ACROSS classes in the reference (IoU 0
   // of class-shifted boxes > thr); only same-class pairs are compared here
@@ -734,9 +771,16 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
       LD_LAUNCH(infer_topk_sort_kernel, dim3(nsorted, p.N),
                          dim3(kSortThreads), 0, stream, p, keys);
   }
-  LD_LAUNCH(infer_decode_kernel, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
-                     stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors, score_thr,
-                     boxes, scores, cand, count, maxc, pre_factors);
+  if (delta)
+    LD_LAUNCH(infer_decode_kernel<true>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
+                       stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors,
+                       score_thr, boxes, scores, cand, count, maxc, pre_factors, *delta,
+                       anchors, g->anchor_scale);
+  else
+    LD_LAUNCH(infer_decode_kernel<false>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
+                       stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors,
+                       score_thr, boxes, scores, cand, count, maxc, pre_factors,
+                       ld_delta_t{}, (const float*)nullptr, 0);
   if (pre_only) {
     // with_nms=False: the per-level selection + decode is the result
     if ((err = hipMemcpyAsync(pre_boxes, boxes, (size_t)p.N * p.Ktot * 4 * sizeof(float),
@@ -784,15 +828,20 @@ extern "C" int ld_get_bboxes_ex(const ld_geom_t* g, const ld_maps_t* cls,
                                 int num_classes, int num_base, int reg_max,
                                 const float* img_hw, const float* scale_factors,
                                 int nms_pre, float score_thr, float iou_thr,
-                                int max_per_img, int flags, float* dets,
-                                int64_t* labels, int32_t* counts, void* workspace,
+                                int max_per_img, int flags, const ld_delta_t* delta,
+                                const float* anchors, float* dets, int64_t* labels,
+                                int32_t* counts, void* workspace,
                                 size_t workspace_bytes, ld_stream_t stream) {
-  if (flags & ~(LD_INFER_VOTING | LD_INFER_PROB | LD_INFER_POINTS)) return LD_EINVAL;
+  if (flags & ~(LD_INFER_VOTING | LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA))
+    return LD_EINVAL;
+  const bool dl = (flags & LD_INFER_DELTA) != 0;
+  if (dl && !delta) return LD_EINVAL;
   return get_bboxes_impl(g, cls, reg, num_classes, reg_max, img_hw, scale_factors,
                          nms_pre, score_thr, iou_thr, max_per_img, dets, labels,
                          counts, workspace, workspace_bytes, stream,
                          (flags & LD_INFER_VOTING) != 0, (flags & LD_INFER_PROB) != 0,
-                         ctr, (flags & LD_INFER_POINTS) != 0, num_base);
+                         ctr, (flags & LD_INFER_POINTS) != 0, num_base, nullptr, nullptr,
+                         nullptr, dl ? delta : nullptr, dl ? anchors : nullptr);
 }
 
 extern "C" int ld_get_bboxes_num_selected(const ld_geom_t* g, int num_base, int nms_pre) {
@@ -805,15 +854,19 @@ extern "C" int ld_get_bboxes_pre_nms(const ld_geom_t* g, const ld_maps_t* cls,
                                      const ld_maps_t* reg, const ld_maps_t* ctr,
                                      int num_classes, int num_base, int reg_max,
                                      const float* img_hw, const float* scale_factors,
-                                     int nms_pre, int flags, float* boxes, float* scores,
+                                     int nms_pre, int flags, const ld_delta_t* delta,
+                                     const float* anchors, float* boxes, float* scores,
                                      float* factors, void* workspace,
                                      size_t workspace_bytes, ld_stream_t stream) {
-  if (flags & ~(LD_INFER_PROB | LD_INFER_POINTS)) return LD_EINVAL;
+  if (flags & ~(LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA)) return LD_EINVAL;
   if (!boxes || !scores || (factors && !ctr)) return LD_EINVAL;
+  const bool dl = (flags & LD_INFER_DELTA) != 0;
+  if (dl && !delta) return LD_EINVAL;
   return get_bboxes_impl(g, cls, reg, num_classes, reg_max, img_hw, scale_factors,
                          nms_pre, 0.0f, 0.5f, 1, nullptr, nullptr, nullptr, workspace,
                          workspace_bytes, stream, false, (flags & LD_INFER_PROB) != 0, ctr,
-                         (flags & LD_INFER_POINTS) != 0, num_base, boxes, scores, factors);
+                         (flags & LD_INFER_POINTS) != 0, num_base, boxes, scores, factors,
+                         dl ? delta : nullptr, dl ? anchors : nullptr);
 }
 
 // ---- test-time augmentation: merge the views, then multiclass_nms ----------------

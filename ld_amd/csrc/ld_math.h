@@ -519,4 +519,72 @@ LD_HD float clamp_dist(float d, float reg_max) {
   return fminf_(fmaxf_(d, 0.0f), reg_max - 0.1f);
 }
 
+// ---- DeltaXYWHBBoxCoder (core/bbox/coder/delta_xywh_bbox_coder.py) ----------
+// bbox2delta, :87-130: deltas of `gt` about `roi`, in the reference's op order.
+LD_HD void bbox2delta(const Box& roi, const Box& gt, const float* means,
+                      const float* stds, float* d /* [4] out */) {
+  const float px = (roi.x1 + roi.x2) * 0.5f, py = (roi.y1 + roi.y2) * 0.5f;
+  const float pw = roi.x2 - roi.x1, ph = roi.y2 - roi.y1;
+  const float gx = (gt.x1 + gt.x2) * 0.5f, gy = (gt.y1 + gt.y2) * 0.5f;
+  const float gw = gt.x2 - gt.x1, gh = gt.y2 - gt.y1;
+  d[0] = ((gx - px) / pw - means[0]) / stds[0];
+  d[1] = ((gy - py) / ph - means[1]) / stds[1];
+  d[2] = (logf(gw / pw) - means[2]) / stds[2];
+  d[3] = (logf(gh / ph) - means[3]) / stds[3];
+}
+
+// delta2bbox, :133-220 without the max_shape clip: denormalise, clamp dw / dh at
+// +-max_ratio = |log(wh_ratio_clip)|, shift the centre, scale the size.  `jac`
+// (nullable, [4]): d centre_x / d d0, d centre_y / d d1, d half_w / d d2,
+// d half_h / d d3 -- the last two are 0 where the clamp cut (torch.clamp passes
+// the gradient on the closed interval [-max_ratio, max_ratio]).
+LD_HD Box delta2bbox(const Box& roi, const float* d, const float* means,
+                     const float* stds, float max_ratio, float* jac) {
+  const float dx = d[0] * stds[0] + means[0], dy = d[1] * stds[1] + means[1];
+  const float dw0 = d[2] * stds[2] + means[2], dh0 = d[3] * stds[3] + means[3];
+  const float dw = fminf_(fmaxf_(dw0, -max_ratio), max_ratio);
+  const float dh = fminf_(fmaxf_(dh0, -max_ratio), max_ratio);
+  const float px = (roi.x1 + roi.x2) * 0.5f, py = (roi.y1 + roi.y2) * 0.5f;
+  const float pw = roi.x2 - roi.x1, ph = roi.y2 - roi.y1;
+  const float gw = pw * expf(dw), gh = ph * expf(dh);
+  const float gx = px + pw * dx, gy = py + ph * dy;
+  if (jac) {
+    jac[0] = pw * stds[0];
+    jac[1] = ph * stds[1];
+    jac[2] = (dw0 < -max_ratio || dw0 > max_ratio) ? 0.0f : 0.5f * gw * stds[2];
+    jac[3] = (dh0 < -max_ratio || dh0 > max_ratio) ? 0.0f : 0.5f * gh * stds[3];
+  }
+  return Box{gx - gw * 0.5f, gy - gh * 0.5f, gx + gw * 0.5f, gy + gh * 0.5f};
+}
+
+// the clip of :222-235: x to [0, w], y to [0, h]
+LD_HD Box clip_box(const Box& b, float h, float w) {
+  return Box{fminf_(fmaxf_(b.x1, 0.0f), w), fminf_(fmaxf_(b.y1, 0.0f), h),
+             fminf_(fmaxf_(b.x2, 0.0f), w), fminf_(fmaxf_(b.y2, 0.0f), h)};
+}
+
+// d loss / d delta[k] from d loss / d (x1, y1, x2, y2) of the decoded box
+LD_HD void delta2bbox_grad(const float* g /* [4] */, const float* jac, float* gd) {
+  gd[0] = (g[0] + g[2]) * jac[0];
+  gd[1] = (g[1] + g[3]) * jac[1];
+  gd[2] = (g[2] - g[0]) * jac[2];
+  gd[3] = (g[3] - g[1]) * jac[3];
+}
+
+// l1_loss / smooth_l1_loss element, losses/smooth_l1_loss.py:9-56; d = pred -
+// target.  Returns the loss, writes its derivative (sign(0) = 0 as torch.abs).
+LD_HD float l1_elem(float d, float* dl) {
+  *dl = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+  return fabsf(d);
+}
+LD_HD float smooth_l1_elem(float d, float beta, float* dl) {
+  const float a = fabsf(d);
+  if (a < beta) {
+    *dl = d / beta;
+    return 0.5f * a * a / beta;
+  }
+  *dl = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+  return a - 0.5f * beta;
+}
+
 }  // namespace ld

@@ -1053,6 +1053,144 @@ __global__ __launch_bounds__(kBlk) void loss_ctr_dense_kernel(
   if (threadIdx.x == 0) partial[part_idx(S_WSUM, 0, bm, c.n)] = s_ctr;
 }
 
+// ------------------------ plain heads: 4 DeltaXYWH channels (LD_LOSS_DELTA) ---
+// ATSSHead / RetinaHead.loss_single (atss_head.py:145-218, anchor_head.py:
+// 376-425) on (N, 4, H, W) delta maps.  The anchor of a cell is the implicit
+// square (ATSS) or row (cell * B + b) of the explicit list, b = pseudo-image %
+// B (Retina); bbox_targets hold the matched GT box in pixels.
+__device__ __forceinline__ Box delta_anchor(const ld_geom_t& g, const ld_delta_t& dc,
+                                            const float* __restrict__ anchors,
+                                            const Cell& c) {
+  if (dc.num_base > 0) {
+    const int b = c.n % dc.num_base;
+    const float4 q =
+        reinterpret_cast<const float4*>(anchors)[(size_t)c.a * dc.num_base + b];
+    return Box{q.x, q.y, q.z, q.w};
+  }
+  const ld_level_t lv = g.lv[c.l];
+  return ld::anchor_box(c.x, c.y, lv.stride,
+                        0.5f * (float)(g.anchor_scale * lv.stride));
+}
+
+// the box the decoded prediction is compared with: the GT itself
+// (reg_decoded_bbox=True) or, for ATSS, the GT encoded and decoded again
+__device__ __forceinline__ Box delta_target(const ld_loss_hp_t& hp, const ld_delta_t& dc,
+                                            const Box& anchor, const float4& t) {
+  const Box gt{t.x, t.y, t.z, t.w};
+  if (!(hp.flags & LD_LOSS_ATSS)) return gt;
+  float td[4];
+  ld::bbox2delta(anchor, gt, dc.means, dc.stds, td);
+  return ld::delta2bbox(anchor, td, dc.means, dc.stds, dc.max_ratio, nullptr);
+}
+
+__global__ __launch_bounds__(kWave) void loss_delta_prepass_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, ld_delta_t dc, BlockMap bm,
+    const float* __restrict__ anchors, const int64_t* __restrict__ labels,
+    const float* __restrict__ bbox_targets, float* __restrict__ weight_targets,
+    float* __restrict__ score, float* __restrict__ partial) {
+  const Cell c = locate(geom, bm);
+  float sc = 0.0f;
+  if (c.active) {
+    const int64_t lab = labels[c.o];
+    if ((hp.flags & LD_LOSS_ATSS) && lab >= 0 && lab < hp.num_classes) {
+      // centerness_target, atss_head.py:298-313
+      const Box an = delta_anchor(geom, dc, anchors, c);
+      const Box gt =
+          delta_target(hp, dc, an, reinterpret_cast<const float4*>(bbox_targets)[c.o]);
+      const float ax = (an.x2 + an.x1) / 2.0f, ay = (an.y2 + an.y1) / 2.0f;
+      const float l_ = ax - gt.x1, t_ = ay - gt.y1, r_ = gt.x2 - ax, b_ = gt.y2 - ay;
+      sc = sqrtf((fminf(l_, r_) / fmaxf(l_, r_)) * (fminf(t_, b_) / fmaxf(t_, b_)));
+    }
+    weight_targets[c.o] = 0.0f;
+    score[c.o] = sc;
+  }
+  const float s = wave_sum(sc);
+  if (threadIdx.x == 0)
+    partial[(size_t)S_WSUM * gridDim.y * bm.blocks_per_img +
+            (size_t)c.n * bm.blocks_per_img + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kBlk) void loss_delta_pos_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, ld_delta_t dc, BlockMap bm,
+    const float* __restrict__ anchors, ld_maps_t cls, ld_maps_t reg,
+    const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
+    const float* __restrict__ score, const float* __restrict__ norm,
+    const float* __restrict__ upstream, ld_maps_t grad_reg, float* __restrict__ posrec,
+    float* __restrict__ partial) {
+  __shared__ float lds4[4];
+  const Cell c = locate256(geom, bm);
+  float s_bbox = 0.0f;
+  if (c.active) {
+    const int64_t lab = labels[c.o];
+    float gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (lab >= 0 && lab < hp.num_classes) {
+      const float up_bbox = upstream ? upstream[1 * geom.num_levels + c.l] : 1.0f;
+      const float inv_avg = 1.0f / avg_divisor(hp, norm);
+      const Box an = delta_anchor(geom, dc, anchors, c);
+      const float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
+      float d[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[k] = *chan_ptr(reg, c, k);
+      if (dc.box_term == LD_DELTA_DECODED) {
+        // centerness target (ATSS) / bbox_weights = 1 (Retina)
+        const float wt = (hp.flags & LD_LOSS_ATSS) ? score[c.o] : 1.0f;
+        const float c_bbox = up_bbox * hp.lw_bbox * wt * inv_avg;
+        float jac[4], iou, g[4], gl;
+        const Box box = ld::delta2bbox(an, d, dc.means, dc.stds, dc.max_ratio, jac);
+        const Box tgt = delta_target(hp, dc, an, t);
+        switch ((hp.flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) {
+          case LD_LOSS_BBOX_IOU:
+            gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, false, &iou, g);
+            break;
+          case LD_LOSS_BBOX_IOU_LINEAR:
+            gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, true, &iou, g);
+            break;
+          case LD_LOSS_BBOX_DIOU:
+            gl = ld::diou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+            break;
+          case LD_LOSS_BBOX_CIOU:
+            gl = ld::ciou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+            break;
+          default:
+            gl = ld::giou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
+        }
+        s_bbox = wt * gl;
+        ld::delta2bbox_grad(g, jac, gd);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gd[k] *= c_bbox;
+      } else {
+        // L1Loss / SmoothL1Loss on the deltas (anchor_head.py:414-424)
+        const float c_bbox = up_bbox * hp.lw_bbox * inv_avg;
+        float td[4];
+        ld::bbox2delta(an, Box{t.x, t.y, t.z, t.w}, dc.means, dc.stds, td);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          float dl;
+          s_bbox += dc.box_term == LD_DELTA_L1
+                        ? ld::l1_elem(d[k] - td[k], &dl)
+                        : ld::smooth_l1_elem(d[k] - td[k], dc.beta, &dl);
+          gd[k] = c_bbox * dl;
+        }
+      }
+      // softmax statistics of the class logits for the CLS part (its KD term
+      // has weight zero here; student == teacher)
+      const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
+      const float invT = 1.0f / hp.T_kd;
+      float ms = *chan_ptr(cls, c, 0);
+      for (int ch = 1; ch < C; ++ch) ms = fmaxf(ms, *chan_ptr(cls, c, ch));
+      float zs = 0.0f;
+      for (int ch = 0; ch < C; ++ch) zs += expf((*chan_ptr(cls, c, ch) - ms) * invT);
+      float4* rec = reinterpret_cast<float4*>(posrec + c.o * kPosRec);
+      rec[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      rec[1] = make_float4(ms, zs, ms, zs);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *chan_ptr_w(grad_reg, c, k) = gd[k];
+  }
+  s_bbox = block_sum(s_bbox, lds4);
+  if (threadIdx.x == 0) partial[part_idx(S_BBOX, 0, bm, c.n)] = s_bbox;
+}
+
 // ------------------------------------------------------------ finalise ------
 // Fixed-order sum of the per-block partials of level l: [slot][z][n][b].
 __global__ __launch_bounds__(kWave) void loss_finalize_kernel(
@@ -1072,7 +1210,10 @@ __global__ __launch_bounds__(kWave) void loss_finalize_kernel(
                   : (k == S_CLS || k == S_KD)  ? zcls
                   : k == S_IM                  ? zim
                                                : 4;
-    if (k == S_WSUM && !(hp.flags & LD_LOSS_ATSS)) {
+    // LD_LOSS_DELTA: no REG / IM launch has written these slots
+    const bool unwritten = (hp.flags & LD_LOSS_DELTA) &&
+                           (k == S_DFL || k == S_LD || k == S_VLR || k == S_IM);
+    if ((k == S_WSUM && !(hp.flags & LD_LOSS_ATSS)) || unwritten) {
       acc[k] = 0.0f;
       continue;
     }
@@ -1404,6 +1545,8 @@ extern "C" int ld_loss_main_parts(
       ((hp->flags & (LD_LOSS_ATSS | LD_LOSS_FCOS | LD_LOSS_PROB_CLS)) ||
        hp->T_ld != hp->T_ld_vlr))
     return LD_EINVAL;
+  // the 4-channel reg maps of a delta block are not what POS / REG read
+  if ((hp->flags & LD_LOSS_DELTA) && (parts & ~LD_LOSS_PART_CLS)) return LD_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   const LossWs w = loss_ws(*geom);
   const BlockMap& bm = w.bm256;
@@ -1485,6 +1628,78 @@ extern "C" int ld_loss_centerness(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   LD_LAUNCH(loss_ctr_dense_kernel, dim3(w.bm256.blocks_per_img, geom->num_imgs),
                      dim3(kBlk), 0, (hipStream_t)stream_, *geom, *hp, w.bm256, *ctr,
                      labels, score, norm, upstream, *grad_ctr, partial);
+  return (int)hipGetLastError();
+}
+
+namespace {
+int check_delta(const ld_loss_hp_t* hp, const ld_delta_t* dc, const float* anchors) {
+  if (!dc) return LD_EINVAL;
+  const int head = hp->flags & (LD_LOSS_ATSS | LD_LOSS_RETINA);
+  if (!(hp->flags & LD_LOSS_DELTA) || (head != LD_LOSS_ATSS && head != LD_LOSS_RETINA) ||
+      (hp->flags & (LD_LOSS_FCOS | LD_LOSS_PROB_CLS)))
+    return LD_EINVAL;
+  if (dc->num_base < 0 || (dc->num_base > 0) != (anchors != nullptr)) return LD_EINVAL;
+  if (!(dc->max_ratio >= 0.0f)) return LD_EINVAL;
+  if (dc->box_term < LD_DELTA_DECODED || dc->box_term > LD_DELTA_SMOOTH_L1)
+    return LD_EINVAL;
+  if (dc->box_term != LD_DELTA_DECODED && head != LD_LOSS_RETINA) return LD_EINVAL;
+  if (dc->box_term == LD_DELTA_SMOOTH_L1 && !(dc->beta > 0.0f)) return LD_EINVAL;
+  for (int k = 0; k < 4; ++k)
+    if (!(dc->stds[k] > 0.0f)) return LD_EINVAL;
+  return 0;
+}
+}  // namespace
+
+extern "C" int ld_loss_delta_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                                     const ld_delta_t* delta, const float* anchors,
+                                     const int64_t* labels, const float* bbox_targets,
+                                     const int32_t* counts, float* weight_targets,
+                                     float* score, float* norm, void* workspace,
+                                     size_t workspace_bytes, ld_stream_t stream_) {
+  if (int e = check_geom(geom)) return e;
+  if (int e = check_hp(hp)) return e;
+  if (int e = check_delta(hp, delta, anchors)) return e;
+  if (!labels || !bbox_targets || !counts || !weight_targets || !score || !norm)
+    return LD_EINVAL;
+  if (delta->num_base > 0 && geom->num_imgs % delta->num_base != 0) return LD_EINVAL;
+  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
+    return LD_ENOSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const BlockMap bm = make_block_map(*geom, kWave);
+  float* partial = (float*)workspace;
+  LD_LAUNCH(loss_delta_prepass_kernel, dim3(bm.blocks_per_img, geom->num_imgs),
+                     dim3(kWave), 0, stream, *geom, *hp, *delta, bm, anchors, labels,
+                     bbox_targets, weight_targets, score, partial);
+  const int nparts = geom->num_imgs * bm.blocks_per_img;
+  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
+                     partial + (size_t)S_WSUM * nparts, counts,
+                     geom->num_imgs + 2 * geom->num_levels, norm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                                 const ld_delta_t* delta, const float* anchors,
+                                 const ld_maps_t* cls, const ld_maps_t* reg,
+                                 const int64_t* labels, const float* bbox_targets,
+                                 const float* score, const float* norm,
+                                 const float* upstream, const ld_maps_t* grad_reg,
+                                 void* workspace, size_t workspace_bytes,
+                                 ld_stream_t stream_) {
+  if (int e = check_geom(geom)) return e;
+  if (int e = check_hp(hp)) return e;
+  if (int e = check_delta(hp, delta, anchors)) return e;
+  if (!cls || !reg || !labels || !bbox_targets || !score || !norm || !grad_reg)
+    return LD_EINVAL;
+  if (delta->num_base > 0 && geom->num_imgs % delta->num_base != 0) return LD_EINVAL;
+  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
+    return LD_ENOSPACE;
+  const LossWs w = loss_ws(*geom);
+  float* partial = (float*)workspace + w.pre_floats;
+  float* posrec = partial + w.main_floats;
+  LD_LAUNCH(loss_delta_pos_kernel, dim3(w.bm256.blocks_per_img, geom->num_imgs),
+                     dim3(kBlk), 0, (hipStream_t)stream_, *geom, *hp, *delta, w.bm256,
+                     anchors, *cls, *reg, labels, bbox_targets, score, norm, upstream,
+                     *grad_reg, posrec, partial);
   return (int)hipGetLastError();
 }
 

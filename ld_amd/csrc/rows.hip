@@ -147,6 +147,51 @@ __global__ void box_rows_kernel(const float* __restrict__ pred,
         gscale * w * g[0], gscale * w * g[1], gscale * w * g[2], gscale * w * g[3]);
 }
 
+// l1_loss / smooth_l1_loss, smooth_l1_loss.py:9-56, one thread per ELEMENT
+template <bool SMOOTH>
+__global__ void l1_rows_kernel(const float* __restrict__ pred,
+                               const float* __restrict__ target,
+                               const float* __restrict__ weight, int64_t n, float beta,
+                               float gscale, float* __restrict__ loss,
+                               float* __restrict__ grad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float d = pred[i] - target[i];
+  float dl;
+  const float l = SMOOTH ? ld::smooth_l1_elem(d, beta, &dl) : ld::l1_elem(d, &dl);
+  const float w = weight ? weight[i] : 1.0f;
+  loss[i] = w * l;
+  if (grad) grad[i] = gscale * w * dl;
+}
+
+// DeltaXYWHBBoxCoder.encode / decode, delta_xywh_bbox_coder.py:87-237
+__global__ void delta_encode_rows_kernel(ld_delta_t dc, const float* __restrict__ boxes,
+                                         const float* __restrict__ gt, int64_t rows,
+                                         float* __restrict__ deltas) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const float4 b = reinterpret_cast<const float4*>(boxes)[r];
+  const float4 g = reinterpret_cast<const float4*>(gt)[r];
+  float d[4];
+  ld::bbox2delta(Box{b.x, b.y, b.z, b.w}, Box{g.x, g.y, g.z, g.w}, dc.means, dc.stds, d);
+  reinterpret_cast<float4*>(deltas)[r] = make_float4(d[0], d[1], d[2], d[3]);
+}
+
+__global__ void delta_decode_rows_kernel(ld_delta_t dc, const float* __restrict__ boxes,
+                                         const float* __restrict__ deltas, int64_t rows,
+                                         int clip, float max_h, float max_w,
+                                         float* __restrict__ out) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const float4 b = reinterpret_cast<const float4*>(boxes)[r];
+  const float4 q = reinterpret_cast<const float4*>(deltas)[r];
+  const float d[4] = {q.x, q.y, q.z, q.w};
+  Box o = ld::delta2bbox(Box{b.x, b.y, b.z, b.w}, d, dc.means, dc.stds, dc.max_ratio,
+                         nullptr);
+  if (clip) o = ld::clip_box(o, max_h, max_w);
+  reinterpret_cast<float4*>(out)[r] = make_float4(o.x1, o.y1, o.x2, o.y2);
+}
+
 // Integral.forward, gfl_head.py:32-44
 __global__ void integral_rows_kernel(const float* __restrict__ x, int64_t rows,
                                      float* __restrict__ out) {
@@ -321,6 +366,50 @@ extern "C" int ld_ciou_rows(const float* pred, const float* target,
   return (int)hipGetLastError();
 }
 
+extern "C" int ld_l1_rows(const float* pred, const float* target, const float* weight,
+                          int64_t n, float gscale, float* loss, float* grad,
+                          ld_stream_t stream) {
+  if (!pred || !target || !loss || n < 0) return LD_EINVAL;
+  if (n == 0) return 0;
+  LD_LAUNCH(l1_rows_kernel<false>, grid_for(n, 256), dim3(256), 0, LD_STREAM, pred,
+                     target, weight, n, 1.0f, gscale, loss, grad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_smooth_l1_rows(const float* pred, const float* target,
+                                 const float* weight, int64_t n, float beta,
+                                 float gscale, float* loss, float* grad,
+                                 ld_stream_t stream) {
+  if (!pred || !target || !loss || n < 0 || !(beta > 0.0f)) return LD_EINVAL;
+  if (n == 0) return 0;
+  LD_LAUNCH(l1_rows_kernel<true>, grid_for(n, 256), dim3(256), 0, LD_STREAM, pred,
+                     target, weight, n, beta, gscale, loss, grad);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_delta_encode_rows(const ld_delta_t* delta, const float* boxes,
+                                    const float* gt, int64_t rows, float* deltas,
+                                    ld_stream_t stream) {
+  if (!delta || !boxes || !gt || !deltas || rows < 0) return LD_EINVAL;
+  if (rows == 0) return 0;
+  LD_LAUNCH(delta_encode_rows_kernel, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                     *delta, boxes, gt, rows, deltas);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_delta_decode_rows(const ld_delta_t* delta, const float* boxes,
+                                    const float* deltas, int64_t rows,
+                                    const float* max_hw, float* out,
+                                    ld_stream_t stream) {
+  if (!delta || !boxes || !deltas || !out || rows < 0 || !(delta->max_ratio >= 0.0f))
+    return LD_EINVAL;
+  if (rows == 0) return 0;
+  LD_LAUNCH(delta_decode_rows_kernel, grid_for(rows, 128), dim3(128), 0, LD_STREAM,
+                     *delta, boxes, deltas, rows, max_hw ? 1 : 0,
+                     max_hw ? max_hw[0] : 0.0f, max_hw ? max_hw[1] : 0.0f, out);
+  return (int)hipGetLastError();
+}
+
 extern "C" int ld_integral_rows(const float* x, int64_t rows, float* out,
                                 ld_stream_t stream) {
   if (!x || !out || rows < 0) return LD_EINVAL;
@@ -366,5 +455,5 @@ extern "C" int ld_sum(const float* x, int64_t n, float* out, void* workspace,
   return (int)hipGetLastError();
 }
 
-extern "C" int ld_abi_version(void) { return 23; }
+extern "C" int ld_abi_version(void) { return 24; }
 extern "C" const char* ld_target_arch(void) { return "gfx950"; }

@@ -13,6 +13,9 @@ Class layout (plain inheritance, one private base):
       |    +- GFocalHead  <- LDv2Head (_FeatureLD)
       +- FCOSGFLHead      <- LDFCOSHead (_SideLD)
       +- RetinaGFLHead    <- LDRetinaHead (_SideLD)
+      +- ATSSHead, RetinaHead   plain_heads.py (_DeltaBox: 4 deltas per
+                                anchor); they share _ATSSFamily / _RetinaFamily
+                                with ATSSGFLHead / RetinaGFLHead
 
 A head states its constructor, its predictor convs (``_predictors``), its
 targets and what differs in ``_hp`` / ``_check_loss_cfg``.  ``_FeatureLD`` is
@@ -282,6 +285,46 @@ class _DenseHead(BBoxTestMixin, nn.Module):
     _plain_keys = ('loss_cls', 'loss_bbox', 'loss_dfl')
 
     # ------------------------------------------------------------- layers --
+    # channels per anchor of the box branch
+    @property
+    def _reg_out(self):
+        return 4 * (self.reg_max + 1)
+
+    def _init_anchor_head(self, num_classes, in_channels, feat_channels,
+                          stacked_convs, conv_cfg, norm_cfg, anchor_generator,
+                          bbox_coder, reg_decoded_bbox, loss_cls, loss_bbox,
+                          train_cfg, test_cfg):
+        """AnchorHead.__init__ (anchor_head.py:31-96) with the tower arguments
+        its subclasses add; ends with the head's ``_init_layers()``."""
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = (stacked_convs,
+                                                            conv_cfg, norm_cfg)
+        self.in_channels, self.num_classes = in_channels, num_classes
+        self.feat_channels = feat_channels
+        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
+        self.sampling = loss_cls['type'] not in [
+            'FocalLoss', 'GHMC', 'QualityFocalLoss']
+        self.cls_out_channels = num_classes if self.use_sigmoid_cls \
+            else num_classes + 1
+        if self.cls_out_channels <= 0:
+            raise ValueError(f'num_classes={num_classes} is too small')
+        self.reg_decoded_bbox = reg_decoded_bbox
+        self.bbox_coder = build_bbox_coder(bbox_coder)
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_bbox = build_loss(loss_bbox)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        if self.train_cfg:
+            self.assigner = build_assigner(self.train_cfg.assigner)
+            self.sampler = build_sampler(dict(type='PseudoSampler'),
+                                         context=self)
+        self.fp16_enabled = False
+        self.anchor_generator = build_anchor_generator(anchor_generator)
+        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+        # d(total)/d(loss_k) == 1 is promised by BaseDetector._parse_losses;
+        # SGDTrainer.step sets this for the duration of a train step so the
+        # backward reuses the gradient the fused forward launch already produced
+        self.unit_upstream = False
+        self._init_layers()
+
     def _build_towers(self):
         """The cls / reg conv stacks (gfl_head.py:102-121 and the same loop of
         atss_gfl_head.py, fcos_gfl_head.py and retina_gfl_head.py)."""
@@ -397,7 +440,8 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         its loss modules, no DFL, no distillation; a subclass passes what
         differs."""
         kw = dict(
-            num_classes=self.num_classes, reg_max=self.reg_max, topk=9,
+            num_classes=self.num_classes,
+            reg_max=getattr(self, 'reg_max', 16), topk=9,
             feat_channels=self.feat_channels,
             lw_cls=self.loss_cls.loss_weight, qfl_beta=2.0,
             lw_bbox=self.loss_bbox.loss_weight,
@@ -469,6 +513,31 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         assert len(sizes) == num_levels
         return sizes
 
+    def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
+                            gt_labels, hp, device):
+        """AnchorHead.get_anchors + LDHead.get_targets for the whole batch in
+        two launches (ld_head.py:377-577)."""
+        strides = [s[0] for s in self.anchor_generator.strides]
+        if not self.anchor_generator.single_square:
+            # the implicit-anchor kernels build the one square anchor of a cell
+            # from an INTEGER scale (octave_base_scale * stride)
+            raise NotImplementedError(
+                f'{type(self).__name__}: one anchor per cell with a non-integer '
+                'scale or ratio != 1 (anchor_generator.py:78-98); the '
+                'single-anchor target kernels take ratios=[1.0] with an integer '
+                'octave_base_scale')
+        if gt_labels is None:
+            gt_labels = [b.new_zeros(b.shape[0], dtype=torch.long)
+                         for b in gt_bboxes]
+        return LB.atss_targets(featmap_sizes, strides, img_metas, gt_bboxes,
+                               gt_labels, hp, device,
+                               self.anchor_generator.anchor_scale)
+
+    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
+        sizes = self._level_sizes(cls_scores, self.anchor_generator.num_levels)
+        return self.get_targets_batched(sizes, img_metas, gt_bboxes, gt_labels,
+                                        hp, cls_scores[0].device)
+
     def _run_block(self, hp, targets, outs, teacher, feats=None, extra=(),
                    reduce_norm=True, want=None):
         """The fused loss block on ``outs`` = (cls_scores, bbox_preds).
@@ -530,7 +599,7 @@ class _DenseHead(BBoxTestMixin, nn.Module):
     # ---------------------------------------------------------- inference --
     def _get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg, rescale,
                     with_nms, prob, centernesses=None, points=False,
-                    strides=None, num_base=1):
+                    strides=None, num_base=1, delta=None):
         cfg = self.test_cfg if cfg is None else cfg
         if cfg is None:
             raise ValueError('get_bboxes needs a test_cfg')
@@ -558,10 +627,14 @@ class _DenseHead(BBoxTestMixin, nn.Module):
             strides, shapes, sfs, nms_pre=get('nms_pre', -1),
             score_thr=get('score_thr'), iou_thr=nms['iou_threshold'],
             max_per_img=get('max_per_img'), num_classes=self.cls_out_channels,
-            reg_max=self.reg_max, voting=nms_type == 'voting_cluster_diounms',
+            reg_max=getattr(self, 'reg_max', 16),
+            voting=nms_type == 'voting_cluster_diounms',
             prob=prob, centernesses=None if centernesses is None else
             [c.detach() for c in centernesses], points=points,
-            num_base=num_base, with_nms=with_nms)
+            num_base=num_base, with_nms=with_nms,
+            delta=delta and delta(cls_scores), **(
+                dict(anchor_scale=self.anchor_generator.anchor_scale or 8)
+                if delta else {}))
 
 
 @HEADS.register_module()
@@ -588,37 +661,15 @@ class GFLHead(_DenseHead):
                  loss_bbox=dict(type='GIoULoss', loss_weight=2.0),
                  train_cfg=None, test_cfg=None):
         super().__init__()
-        self.stacked_convs, self.conv_cfg, self.norm_cfg = (stacked_convs,
-                                                            conv_cfg, norm_cfg)
         self.reg_max = reg_max
-        self.in_channels, self.num_classes = in_channels, num_classes
-        self.feat_channels = feat_channels
-        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
-        self.cls_out_channels = num_classes if self.use_sigmoid_cls \
-            else num_classes + 1
-        if self.cls_out_channels <= 0:
-            raise ValueError(f'num_classes={num_classes} is too small')
-        self.reg_decoded_bbox = reg_decoded_bbox
-        self.bbox_coder = build_bbox_coder(bbox_coder)
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_bbox = build_loss(loss_bbox)
-        self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        if self.train_cfg:
-            self.assigner = build_assigner(self.train_cfg.assigner)
-            self.sampler = build_sampler(dict(type='PseudoSampler'),
-                                         context=self)
+        self._init_anchor_head(num_classes, in_channels, feat_channels,
+                               stacked_convs, conv_cfg, norm_cfg,
+                               anchor_generator, bbox_coder, reg_decoded_bbox,
+                               loss_cls, loss_bbox, train_cfg, test_cfg)
         self.sampling = False  # gfl_head.py:93 overrides AnchorHead's value
-        self.fp16_enabled = False
-        self.anchor_generator = build_anchor_generator(anchor_generator)
-        self.num_anchors = self.anchor_generator.num_base_anchors[0]
-        self._init_layers()
         # after the layers, like the reference (state_dict key order)
         self.integral = Integral(self.reg_max)
         self.loss_dfl = build_loss(loss_dfl)
-        # d(total)/d(loss_k) == 1 is promised by BaseDetector._parse_losses;
-        # SGDTrainer.step sets this for the duration of a train step so the
-        # backward reuses the gradient the fused forward launch already produced
-        self.unit_upstream = False
 
     def _init_layers(self):
         """gfl_head.py:102-133."""
@@ -658,31 +709,6 @@ class GFLHead(_DenseHead):
                 f'{_BOX_LOSSES} (got {type(self.loss_cls).__name__}, '
                 f'{type(self.loss_bbox).__name__})')
         self._check_train_cfg()
-
-    def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
-                            gt_labels, hp, device):
-        """AnchorHead.get_anchors + LDHead.get_targets for the whole batch in
-        two launches (ld_head.py:377-577)."""
-        strides = [s[0] for s in self.anchor_generator.strides]
-        if not self.anchor_generator.single_square:
-            # the implicit-anchor kernels build the one square anchor of a cell
-            # from an INTEGER scale (octave_base_scale * stride)
-            raise NotImplementedError(
-                f'{type(self).__name__}: one anchor per cell with a non-integer '
-                'scale or ratio != 1 (anchor_generator.py:78-98); the '
-                'single-anchor target kernels take ratios=[1.0] with an integer '
-                'octave_base_scale')
-        if gt_labels is None:
-            gt_labels = [b.new_zeros(b.shape[0], dtype=torch.long)
-                         for b in gt_bboxes]
-        return LB.atss_targets(featmap_sizes, strides, img_metas, gt_bboxes,
-                               gt_labels, hp, device,
-                               self.anchor_generator.anchor_scale)
-
-    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
-        sizes = self._level_sizes(cls_scores, self.anchor_generator.num_levels)
-        return self.get_targets_batched(sizes, img_metas, gt_bboxes, gt_labels,
-                                        hp, cls_scores[0].device)
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas,
              gt_bboxes_ignore=None):
@@ -812,16 +838,73 @@ class _SideLD:
                     lw_kd=self.loss_kd.loss_weight, T_kd=self.loss_kd.T)
 
 
-@HEADS.register_module()
-class ATSSGFLHead(GFLHead):
-    """atss_gfl_head.py:52-185: the ATSS head with a general-distribution box
-    branch -- GFLHead's two towers, ``atss_cls`` / ``atss_reg`` /
+class _ATSSFamily:
+    """What ATSSGFLHead and the plain ATSSHead share (atss_gfl_head.py:52-185,
+    atss_head.py:15-143): GFLHead's two towers, ``atss_cls`` / ``atss_reg`` /
     ``atss_centerness`` output convs (state_dict names of the reference),
-    FocalLoss + centerness-weighted GIoU + centerness BCE.  forward returns
-    (cls_scores, bbox_preds, centernesses)."""
+    FocalLoss + centerness-weighted box loss + centerness BCE.  forward
+    returns (cls_scores, bbox_preds, centernesses); the box branch has
+    ``_reg_out`` channels."""
     _predictors = ('atss_cls', 'atss_reg', 'atss_centerness')
     _loss_keys, _loss_rows = ATSS_LOSS_KEYS, _ATSS_ROWS
     _plain_keys = ('loss_cls', 'loss_bbox', 'loss_centerness')
+
+    def _init_layers(self):
+        """atss_gfl_head.py:90-125, atss_head.py:62-106."""
+        self._build_towers()
+        assert self.num_anchors == 1, 'one square anchor per position'
+        self.atss_cls = Conv2d(self.feat_channels,
+                               self.num_anchors * self.cls_out_channels, 3,
+                               padding=1)
+        self.atss_reg = Conv2d(self.feat_channels,
+                               self.num_anchors * self._reg_out, 3, padding=1)
+        self.atss_centerness = Conv2d(self.feat_channels, self.num_anchors, 3,
+                                      padding=1)
+        self._build_scales(self.anchor_generator.strides)
+
+    def forward(self, feats):
+        """atss_gfl_head.py:139-183, atss_head.py:108-143."""
+        return self._predict(*self._trunk(feats))
+
+    def _predict(self, cls_feat, reg_feat, levels):
+        cls3, _ = self.atss_cls.forward3(cls_feat, levels)
+        reg3, _ = self.atss_reg.forward3(reg_feat, levels)
+        ctr3, _ = self.atss_centerness.forward3(reg_feat, levels)
+        reg3 = self._scale(reg3, levels)
+        return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
+                Y.split_levels(ctr3, levels))
+
+    def _check_loss_cfg(self):
+        self._check_focal_cfg('ATSS', centerness=True)
+        self._check_train_cfg()
+
+    def _atss_hp(self):
+        return dict(lw_dfl=0.0, lw_ctr=self.loss_centerness.loss_weight,
+                    focal_alpha=self.loss_cls.alpha, qfl_beta=2.0,
+                    flags=L.LD_LOSS_ATSS)
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
+             img_metas, gt_bboxes_ignore=None):
+        """atss_gfl_head.py:187-310, atss_head.py:221-296: loss_cls, loss_bbox,
+        loss_centerness."""
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, extra=centernesses)
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
+                   cfg=None, rescale=False, with_nms=True):
+        """atss_gfl_head.py:420-575, atss_head.py:376-508: GFLHead's pipeline
+        with the top-k key max_c score_c * sigmoid(centerness) and the
+        centerness as multiclass_nms' score factor (applied after the
+        threshold test)."""
+        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
+                                rescale, with_nms, prob=False,
+                                centernesses=centernesses)
+
+
+@HEADS.register_module()
+class ATSSGFLHead(_ATSSFamily, GFLHead):
+    """atss_gfl_head.py:52-185: the ATSS head with a general-distribution box
+    branch."""
 
     def __init__(self, num_classes, in_channels, stacked_convs=4,
                  conv_cfg=None,
@@ -842,56 +925,10 @@ class ATSSGFLHead(GFLHead):
                          reg_max=reg_max, **kwargs)
         self.loss_centerness = build_loss(loss_centerness)
 
-    def _init_layers(self):
-        """atss_gfl_head.py:90-125."""
-        self._build_towers()
-        assert self.num_anchors == 1, 'one square anchor per position'
-        self.atss_cls = Conv2d(self.feat_channels,
-                               self.num_anchors * self.cls_out_channels, 3,
-                               padding=1)
-        self.atss_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3,
-                               padding=1)
-        self.atss_centerness = Conv2d(self.feat_channels, self.num_anchors, 3,
-                                      padding=1)
-        self._build_scales(self.anchor_generator.strides)
-
-    def forward(self, feats):
-        """atss_gfl_head.py:139-183."""
-        return self._predict(*self._trunk(feats))
-
-    def _predict(self, cls_feat, reg_feat, levels):
-        cls3, _ = self.atss_cls.forward3(cls_feat, levels)
-        reg3, _ = self.atss_reg.forward3(reg_feat, levels)
-        ctr3, _ = self.atss_centerness.forward3(reg_feat, levels)
-        reg3 = self._scale(reg3, levels)
-        return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
-                Y.split_levels(ctr3, levels))
-
-    def _check_loss_cfg(self):
-        self._check_focal_cfg('ATSS', centerness=True)
-        self._check_train_cfg()
-
     def _hp(self, **over):
-        kw = dict(lw_dfl=0.0, lw_ctr=self.loss_centerness.loss_weight,
-                  focal_alpha=self.loss_cls.alpha, qfl_beta=2.0,
-                  flags=L.LD_LOSS_ATSS)
+        kw = self._atss_hp()
         kw.update(over)
         return super()._hp(**kw)
-
-    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
-             img_metas, gt_bboxes_ignore=None):
-        """atss_gfl_head.py:187-310: loss_cls, loss_bbox, loss_centerness."""
-        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
-                          img_metas, extra=centernesses)
-
-    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
-                   cfg=None, rescale=False, with_nms=True):
-        """atss_gfl_head.py:420-575: GFLHead's pipeline with the top-k key
-        max_c score_c * sigmoid(centerness) and the centerness as
-        multiclass_nms' score factor (applied after the threshold test)."""
-        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
-                                rescale, with_nms, prob=False,
-                                centernesses=centernesses)
 
 
 @HEADS.register_module()
@@ -1042,101 +1079,47 @@ class LDFCOSHead(_SideLD, FCOSGFLHead):
                           **self._ld_hp())
 
 
-@HEADS.register_module()
-class RetinaGFLHead(_DenseHead):
-    """retina_gfl_head.py:50-330 over anchor_head.py:14-173: the RetinaNet head
-    (ratios x scales anchors per cell, conv + ReLU towers without a norm
-    layer) with a general-distribution box branch.  ``atss_cls`` /
-    ``atss_reg`` predictor names as in the reference; forward returns
-    (cls_scores (N, B * C, H, W), bbox_preds (N, B * 68, H, W)) lists.
+class _RetinaFamily:
+    """What RetinaGFLHead and the plain RetinaHead share (retina_gfl_head.py:
+    50-330, retina_head.py:8-114 over anchor_head.py:14-173): ratios x scales
+    anchors per cell, conv + ReLU towers, the two predictors named by
+    ``_predictors``; forward returns (cls_scores (N, B * C, H, W), bbox_preds
+    (N, B * _reg_out, H, W)) lists.
 
     Loss execution: the B anchors of a cell are B pseudo-images of the fused
     one-anchor-per-cell loss block (an (N, B * C, H, W) map IS the (N * B, C,
     H, W) map of them), targets come from ld_retina_targets."""
-    _predictors = ('atss_cls', 'atss_reg')
     _loss_keys, _loss_rows = RETINA_LOSS_KEYS, _RETINA_ROWS
     _plain_keys = ('loss_cls', 'loss_bbox')
 
-    def __init__(self, num_classes, in_channels, stacked_convs=4,
-                 conv_cfg=None, norm_cfg=None, reg_max=16, feat_channels=256,
-                 anchor_generator=dict(type='AnchorGenerator',
-                                       octave_base_scale=4,
-                                       scales_per_octave=3,
-                                       ratios=[0.5, 1.0, 2.0],
-                                       strides=[8, 16, 32, 64, 128]),
-                 bbox_coder=dict(type='DeltaXYWHBBoxCoder',
-                                 target_means=(.0, .0, .0, .0),
-                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
-                 reg_decoded_bbox=False,
-                 loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True,
-                               loss_weight=1.0),
-                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0,
-                                loss_weight=1.0),
-                 train_cfg=None, test_cfg=None):
-        super().__init__()
-        self.stacked_convs, self.conv_cfg, self.norm_cfg = (stacked_convs,
-                                                            conv_cfg, norm_cfg)
-        self.reg_max = reg_max
-        self.in_channels, self.num_classes = in_channels, num_classes
-        self.feat_channels = feat_channels
-        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
-        self.sampling = loss_cls['type'] not in [
-            'FocalLoss', 'GHMC', 'QualityFocalLoss']
-        self.cls_out_channels = num_classes if self.use_sigmoid_cls \
-            else num_classes + 1
-        self.reg_decoded_bbox = reg_decoded_bbox
-        self.bbox_coder = build_bbox_coder(bbox_coder)
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_bbox = build_loss(loss_bbox)
-        self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        if self.train_cfg:
-            self.assigner = build_assigner(self.train_cfg.assigner)
-            self.sampler = build_sampler(dict(type='PseudoSampler'),
-                                         context=self)
-        self.fp16_enabled = False
-        self.anchor_generator = build_anchor_generator(anchor_generator)
-        self.num_anchors = self.anchor_generator.num_base_anchors[0]
-        self._init_layers()
-        # after the layers, like the reference (state_dict key order)
-        self.integral = Integral(self.reg_max)
-        self.unit_upstream = False
-
     def _init_layers(self):
-        """retina_gfl_head.py:231-264 (no per-level Scale)."""
+        """retina_gfl_head.py:231-264, retina_head.py:60-93 (no per-level
+        Scale)."""
         self._build_towers()
-        self.atss_cls = Conv2d(self.feat_channels,
-                               self.num_anchors * self.cls_out_channels, 3,
-                               padding=1)
-        self.atss_reg = Conv2d(self.feat_channels,
-                               self.num_anchors * (self.reg_max + 1) * 4, 3,
-                               padding=1)
+        cls_name, reg_name = self._predictors
+        setattr(self, cls_name, Conv2d(
+            self.feat_channels, self.num_anchors * self.cls_out_channels, 3,
+            padding=1))
+        setattr(self, reg_name, Conv2d(
+            self.feat_channels, self.num_anchors * self._reg_out, 3,
+            padding=1))
 
     def forward(self, feats):
-        """retina_gfl_head.py:276-299."""
+        """retina_gfl_head.py:276-299, retina_head.py:95-114."""
         return self._predict(*self._trunk(feats))
 
     def _predict(self, cls_feat, reg_feat, levels):
-        cls3, _ = self.atss_cls.forward3(cls_feat, levels)
-        reg3, _ = self.atss_reg.forward3(reg_feat, levels)
+        cls_name, reg_name = self._predictors
+        cls3, _ = getattr(self, cls_name).forward3(cls_feat, levels)
+        reg3, _ = getattr(self, reg_name).forward3(reg_feat, levels)
         return Y.split_levels(cls3, levels), Y.split_levels(reg3, levels)
 
     # ---------------------------------------------------------------- loss --
-    def _check_loss_cfg(self):
-        if not self.reg_decoded_bbox:
-            raise NotImplementedError(
-                'the fused RetinaGFL loss block evaluates its box loss on '
-                'decoded boxes (reg_decoded_bbox=True)')
-        self._check_focal_cfg('RetinaGFL', centerness=False)
-        self._check_train_cfg()
+    def _check_assigner(self):
         if type(self.assigner).__name__ != 'MaxIoUAssigner':
             raise NotImplementedError(
-                f'{type(self.assigner).__name__}: the RetinaGFL targets kernel '
+                f'{type(self.assigner).__name__}: the Retina targets kernel '
                 'implements MaxIoUAssigner')
-
-    def _hp(self, **over):
-        kw = dict(focal_alpha=self.loss_cls.alpha, flags=L.LD_LOSS_RETINA)
-        kw.update(over)
-        return super()._hp(**kw)
 
     def get_targets_batched(self, featmap_sizes, img_metas, gt_bboxes,
                             gt_labels, device, want_gt_inds=False):
@@ -1166,9 +1149,9 @@ class RetinaGFLHead(_DenseHead):
 
     def _run_block(self, hp, targets, outs, teacher, **kw):
         """The block runs on the pseudo-image views.  num_total_samples is the
-        LOCAL count (ld_retina.py:228-229): no cross-rank reduction of the
-        normaliser."""
-        C_, R4 = self.cls_out_channels, 4 * (self.reg_max + 1)
+        LOCAL count (ld_retina.py:228-229, anchor_head.py:476-477): no
+        cross-rank reduction of the normaliser."""
+        C_, R4 = self.cls_out_channels, self._reg_out
         outs = self._pseudo(outs[0], C_), self._pseudo(outs[1], R4)
         teacher = (self._pseudo(teacher[0], C_), self._pseudo(teacher[1], R4),
                    None)
@@ -1177,18 +1160,67 @@ class RetinaGFLHead(_DenseHead):
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas,
              gt_bboxes_ignore=None):
-        """retina_gfl_head.py:157-229: loss_cls, loss_bbox."""
+        """retina_gfl_head.py:157-229, anchor_head.py:427-495: loss_cls,
+        loss_bbox."""
         return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
                           img_metas)
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None,
                    rescale=False, with_nms=True):
-        """anchor_head.py:497-589 + retina_gfl_head.py:301-412: sigmoid scores,
-        Integral * stride, per-level top-nms_pre over all (cell, base anchor)
-        rows, decode about the cell centre, multiclass_nms."""
+        """anchor_head.py:497-727 + retina_gfl_head.py:301-412: sigmoid scores,
+        per-level top-nms_pre over all (cell, base anchor) rows, decode,
+        multiclass_nms."""
         return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
                                 rescale, with_nms, prob=False,
                                 num_base=self.num_anchors)
+
+
+@HEADS.register_module()
+class RetinaGFLHead(_RetinaFamily, _DenseHead):
+    """retina_gfl_head.py:50-330: the RetinaNet head with a
+    general-distribution box branch (``atss_cls`` / ``atss_reg`` predictor
+    names as in the reference, Integral * stride decoded about the cell
+    centre)."""
+    _predictors = ('atss_cls', 'atss_reg')
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4,
+                 conv_cfg=None, norm_cfg=None, reg_max=16, feat_channels=256,
+                 anchor_generator=dict(type='AnchorGenerator',
+                                       octave_base_scale=4,
+                                       scales_per_octave=3,
+                                       ratios=[0.5, 1.0, 2.0],
+                                       strides=[8, 16, 32, 64, 128]),
+                 bbox_coder=dict(type='DeltaXYWHBBoxCoder',
+                                 target_means=(.0, .0, .0, .0),
+                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
+                 reg_decoded_bbox=False,
+                 loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True,
+                               loss_weight=1.0),
+                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0,
+                                loss_weight=1.0),
+                 train_cfg=None, test_cfg=None):
+        super().__init__()
+        self.reg_max = reg_max
+        self._init_anchor_head(num_classes, in_channels, feat_channels,
+                               stacked_convs, conv_cfg, norm_cfg,
+                               anchor_generator, bbox_coder, reg_decoded_bbox,
+                               loss_cls, loss_bbox, train_cfg, test_cfg)
+        # after the layers, like the reference (state_dict key order)
+        self.integral = Integral(self.reg_max)
+
+    def _check_loss_cfg(self):
+        if not self.reg_decoded_bbox:
+            raise NotImplementedError(
+                'the fused RetinaGFL loss block evaluates its box loss on '
+                'decoded boxes (reg_decoded_bbox=True)')
+        self._check_focal_cfg('RetinaGFL', centerness=False)
+        self._check_train_cfg()
+        self._check_assigner()
+
+    def _hp(self, **over):
+        kw = dict(focal_alpha=self.loss_cls.alpha, flags=L.LD_LOSS_RETINA)
+        kw.update(over)
+        return super()._hp(**kw)
 
 
 @HEADS.register_module()

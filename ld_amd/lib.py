@@ -52,17 +52,27 @@ class LossHpT(C.Structure):
                 ('lw_ctr', C.c_float), ('focal_alpha', C.c_float)]
 
 
+class DeltaT(C.Structure):  # ld_delta_t
+    _fields_ = [('means', C.c_float * 4), ('stds', C.c_float * 4),
+                ('max_ratio', C.c_float), ('beta', C.c_float),
+                ('num_base', C.c_int32), ('box_term', C.c_int32)]
+
+
 LD_LOSS_PROB_CLS = 1
 LD_IM_CENTER_INSIDE = 2
 LD_LOSS_ATSS = 4
 LD_LOSS_FCOS = 8
 LD_LOSS_RETINA = 16
+LD_LOSS_DELTA = 32
+LD_DELTA_TERMS = {'decoded': 0, 'l1': 1, 'smooth_l1': 2}
+LD_LOSS_PART_CLS = 4
 LD_LOSS_BBOX_SHIFT = 8
 LD_LOSS_BBOX_MODES = {'giou': 0, 'iou': 1, 'iou_linear': 2, 'diou': 3,
                       'ciou': 4}
 LD_INFER_VOTING = 1
 LD_INFER_PROB = 2
 LD_INFER_POINTS = 4
+LD_INFER_DELTA = 16
 LD_AUG_RESCALE = 8
 LD_MAX_AUG_VIEWS = 16
 LD_FLIP = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
@@ -292,11 +302,12 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
 _AV = C.POINTER(AugViewT)
+_D = C.POINTER(DeltaT)
 
 # name -> (restype, argtypes); kept in one table so the CPU test-suite can
 # check that every symbol include/ld_hip.h declares is exported.
@@ -371,6 +382,16 @@ SIGNATURES = {
     'ld_loss_centerness': (C.c_int, [_G, _H, _M, _vp, _vp, _vp, _vp, _M, _vp,
                                      _sz, _vp]),
     'ld_loss_set_reg_variant': (C.c_int, [_i32]),
+    'ld_loss_delta_prepass': (C.c_int, [_G, _H, _D, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _sz, _vp]),
+    'ld_loss_delta_pos': (C.c_int, [_G, _H, _D, _vp, _M, _M, _vp, _vp, _vp,
+                                    _vp, _vp, _M, _vp, _sz, _vp]),
+    'ld_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    'ld_smooth_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
+                                    _vp]),
+    'ld_delta_encode_rows': (C.c_int, [_D, _vp, _vp, _i64, _vp, _vp]),
+    'ld_delta_decode_rows': (C.c_int, [_D, _vp, _vp, _i64,
+                                       C.POINTER(C.c_float), _vp, _vp]),
     'ld_probe_copy': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
     'ld_probe_planes': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     'ld_gconv_weight_image_floats': (_sz, [_i32, _i32, _i32, _i32]),
@@ -421,12 +442,12 @@ SIGNATURES = {
                                 _f32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ld_get_bboxes_num_selected': (C.c_int, [_G, _i32, _i32]),
     'ld_get_bboxes_pre_nms': (C.c_int, [_G, _M, _M, _M, _i32, _i32, _i32, _vp,
-                                        _vp, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
-                                        _vp]),
+                                        _vp, _i32, _i32, _D, _vp, _vp, _vp, _vp,
+                                        _vp, _sz, _vp]),
     'ld_get_bboxes_ex_workspace_bytes': (_sz, [_G, _i32, _i32, _i32]),
     'ld_get_bboxes_ex': (C.c_int, [_G, _M, _M, _M, _i32, _i32, _i32, _vp, _vp, _i32, _f32,
-                                   _f32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
-                                   _vp]),
+                                   _f32, _i32, _i32, _D, _vp, _vp, _vp, _vp, _vp,
+                                   _sz, _vp]),
     'ld_aug_merge_nms_workspace_bytes': (_sz, [_AV, _i32, _i32]),
     'ld_aug_merge_nms': (C.c_int, [_AV, _i32, _i32, _f32, _f32, _i32, _i32,
                                    _vp, _vp, _vp, _vp, _sz, _vp]),

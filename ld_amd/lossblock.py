@@ -544,10 +544,20 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     their gradient comes back as grads['ctr'] and the centerness loss in row 6.
     reduce_norm: optional callable(norm_tensor[2]) doing the cross-rank MEAN
     in place (core/utils/dist_utils.py:63-69) -- device side, no host sync.
+    hp.flags & LD_LOSS_DELTA (ATSSHead / RetinaHead): ``reg`` are 4-channel
+    DeltaXYWH maps and ``targets['delta']`` = (ld_delta_t, explicit anchors or
+    None); the block runs its delta prepass / positives launches and the class
+    part only, the teacher arguments are not read.
     Returns (losses (8, L) tensor, grads dict of lists, norm tensor).
     """
     lib = L.get_lib()
     geom = targets['geom']
+    delta = None
+    if hp.flags & L.LD_LOSS_DELTA:
+        delta = targets['delta']
+        if any(r.shape[1] != 4 for r in reg):
+            raise L.LdError('LD_LOSS_DELTA: the reg maps carry 4 channels per '
+                            'anchor')
     device = cls[0].device
     N, A = geom.num_imgs, geom.num_anchors
     m_cls, m_reg = L.make_maps(cls), L.make_maps(reg)
@@ -577,12 +587,19 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     need = lib.ld_loss_workspace_bytes(C.byref(geom))
     ws = workspace(device, need, 'loss')
     st = L.stream_ptr(device)
-    L.check(lib.ld_loss_prepass_ex(
-        C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
-        L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
-        L.ptr(targets['vlr']), L.ptr(targets['counts']), L.ptr(wt),
-        L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
-        'ld_loss_prepass')
+    if delta is not None:
+        L.check(lib.ld_loss_delta_prepass(
+            C.byref(geom), C.byref(hp), C.byref(delta[0]), L.ptr(delta[1]),
+            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
+            L.ptr(targets['counts']), L.ptr(wt), L.ptr(score), L.ptr(norm),
+            L.ptr(ws), ws.numel(), st), 'ld_loss_delta_prepass')
+    else:
+        L.check(lib.ld_loss_prepass_ex(
+            C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
+            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
+            L.ptr(targets['vlr']), L.ptr(targets['counts']), L.ptr(wt),
+            L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
+            'ld_loss_prepass')
     up = None
     if upstream is not None:
         up = L.require_device(upstream.contiguous(), torch.float32,
@@ -602,7 +619,7 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     def _main(norm, keep=keep):
         _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg,
                          m_x, m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x,
-                         m_kds, m_kdt, mg_kd, ctr, g_ctr, ws, losses, st)
+                         m_kds, m_kdt, mg_kd, ctr, g_ctr, ws, losses, st, delta)
 
     if deferred:
         # virtual ranks: the main part waits for the other ranks' prepasses
@@ -616,10 +633,20 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
 
 def _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg, m_x,
                      m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x, m_kds,
-                     m_kdt, mg_kd, ctr, g_ctr, ws, losses, st):
+                     m_kdt, mg_kd, ctr, g_ctr, ws, losses, st, delta=None):
     """main -> (centerness) -> finalise of ``loss_block_forward`` with the
     normalisers in ``norm``."""
     split = m_kds is not None
+    parts = 15
+    if delta is not None:
+        # the positives' box term on the 4 deltas, then the class part alone
+        L.check(lib.ld_loss_delta_pos(
+            C.byref(geom), C.byref(hp), C.byref(delta[0]), L.ptr(delta[1]),
+            C.byref(m_cls), C.byref(m_reg), L.ptr(targets['labels']),
+            L.ptr(targets['bbox_targets']), L.ptr(score), L.ptr(norm),
+            L.ptr(up), C.byref(mg_reg), L.ptr(ws), ws.numel(), st),
+            'ld_loss_delta_pos')
+        parts = L.LD_LOSS_PART_CLS
     L.check(lib.ld_loss_main_parts(
         C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
         C.byref(m_tcls), C.byref(m_treg), C.byref(m_x), C.byref(m_tx),
@@ -629,7 +656,7 @@ def _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg, m_x,
         L.ptr(score), L.ptr(norm), L.ptr(up), C.byref(mg_cls),
         C.byref(mg_reg), C.byref(mg_x),
         C.byref(m_kds) if split else None, C.byref(m_kdt) if split else None,
-        C.byref(mg_kd) if split else None, L.ptr(ws), ws.numel(), 15, st),
+        C.byref(mg_kd) if split else None, L.ptr(ws), ws.numel(), parts, st),
         'ld_loss_main')
     if g_ctr is not None:
         L.check(lib.ld_loss_centerness(
@@ -740,25 +767,38 @@ def kl_integral_dense(s_reg, t_reg, weight, T=10.0, scale=1.0, with_grad=True):
 def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
                nms_pre=1000, score_thr=0.05, iou_thr=0.6, max_per_img=100,
                num_classes=None, reg_max=16, voting=False, prob=False,
-               centernesses=None, points=False, num_base=1, with_nms=True):
+               centernesses=None, points=False, num_base=1, with_nms=True,
+               delta=None, anchor_scale=8):
     """GFLHead.get_bboxes on the device (ld_get_bboxes_ex; ``voting`` = the
     score-voting Cluster-DIoU-NMS variant, ``prob`` = the class maps hold
     probabilities: GFocalHead.get_bboxes; ``centernesses`` / ``points``: the
     ATSSGFLHead / FCOSGFLHead variants).  ``cls_scores`` /
     ``bbox_preds``: per-level NCHW maps; ``img_shapes``: per image (h, w[, c]);
     ``scale_factors``: per image 4 values (rescale=True) or None.
+    ``delta`` = (ld_delta_t, explicit anchors (cells * num_base, 4) or None):
+    the ATSSHead / RetinaHead variant (LD_INFER_DELTA), ``bbox_preds`` hold
+    num_base * 4 DeltaXYWH deltas; ``anchor_scale``: the implicit anchor's.
     -> list of (dets (k, 5), labels (k,)) device tensors, one pair per image."""
     lib = L.get_lib()
     dev = cls_scores[0].device
     N = cls_scores[0].shape[0]
     B_ = int(num_base)
     C_ = int(num_classes or cls_scores[0].shape[1] // B_)
+    R_ = 4 if delta is not None else 4 * (reg_max + 1)
     if cls_scores[0].shape[1] != B_ * C_ or \
-            bbox_preds[0].shape[1] != B_ * 4 * (reg_max + 1):
+            bbox_preds[0].shape[1] != B_ * R_:
         raise L.LdError('get_bboxes: channel counts do not match num_base x '
-                        '(num_classes, 4 * (reg_max + 1))')
+                        f'(num_classes, {R_})')
     sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
-    g = L.make_geom(sizes, strides, N)
+    g = L.make_geom(sizes, strides, N, anchor_scale)
+    dt = da = None
+    if delta is not None:
+        dt, da = C.byref(delta[0]), delta[1]
+        if da is not None:
+            da = L.require_device(da.contiguous(), torch.float32, 'anchors')
+            if da.shape != (g.num_anchors * B_, 4):
+                raise L.LdError(f'get_bboxes: {tuple(da.shape)} anchors for '
+                                f'{g.num_anchors} cells x {B_}')
     cm, rm = L.make_maps(cls_scores), L.make_maps(bbox_preds)
     hw = torch.tensor([[float(s[0]), float(s[1])] for s in img_shapes],
                       dtype=torch.float32).to(dev)
@@ -772,7 +812,8 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
         raise L.LdError('ld_get_bboxes: bad geometry')
     ws = workspace(dev, need, 'infer')
     pflags = (L.LD_INFER_PROB if prob else 0) | \
-        (L.LD_INFER_POINTS if points else 0)
+        (L.LD_INFER_POINTS if points else 0) | \
+        (L.LD_INFER_DELTA if delta is not None else 0)
     flags = pflags | (L.LD_INFER_VOTING if voting else 0)
     km = C.byref(L.make_maps(centernesses)) if centernesses is not None \
         else None
@@ -789,8 +830,8 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
             if centernesses is not None else None
         L.check(lib.ld_get_bboxes_pre_nms(
             C.byref(g), C.byref(cm), C.byref(rm), km, C_, B_, int(reg_max),
-            L.ptr(hw), L.ptr(sf), int(nms_pre), pflags, L.ptr(boxes),
-            L.ptr(raw), L.ptr(fac), L.ptr(ws), ws.numel(),
+            L.ptr(hw), L.ptr(sf), int(nms_pre), pflags, dt, L.ptr(da),
+            L.ptr(boxes), L.ptr(raw), L.ptr(fac), L.ptr(ws), ws.numel(),
             L.stream_ptr(dev)), 'ld_get_bboxes_pre_nms')
         scores[:, :, :C_] = raw
         if fac is not None:
@@ -803,7 +844,8 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
         C.byref(g), C.byref(cm), C.byref(rm), km, C_, B_, int(reg_max),
         L.ptr(hw),
         L.ptr(sf), int(nms_pre), float(score_thr), float(iou_thr),
-        int(max_per_img), flags, L.ptr(dets), L.ptr(labels), L.ptr(counts),
+        int(max_per_img), flags, dt, L.ptr(da), L.ptr(dets), L.ptr(labels),
+        L.ptr(counts),
         L.ptr(ws), ws.numel(), L.stream_ptr(dev)), 'ld_get_bboxes_ex')
     ks = counts.cpu().tolist()  # the one sync of the call
     return [(dets[n, :k], labels[n, :k]) for n, k in enumerate(ks)]

@@ -344,16 +344,72 @@ def bbox_loss_mode(module):
     return None
 
 
+def _launch_l1(pred, weight, loss, grad, target):
+    L.check(L.get_lib().ld_l1_rows(L.ptr(pred), L.ptr(target), L.ptr(weight),
+                                   pred.numel(), 1.0, L.ptr(loss), L.ptr(grad),
+                                   _st(pred)), 'ld_l1_rows')
+
+
+def _launch_smooth_l1(pred, weight, loss, grad, target, beta):
+    L.check(L.get_lib().ld_smooth_l1_rows(
+        L.ptr(pred), L.ptr(target), L.ptr(weight), pred.numel(), float(beta),
+        1.0, L.ptr(loss), L.ptr(grad), _st(pred)), 'ld_smooth_l1_rows')
+
+
+class _ElementLoss(nn.Module):
+    """L1Loss / SmoothL1Loss (smooth_l1_loss.py:59-139): element-wise losses
+    with an element-wise weight.  The tensors are handed to ``_RowLoss`` as
+    (numel,) "rows" of one element, so one launch yields the weighted loss and
+    d/dpred of every element."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def _launch(self):
+        raise NotImplementedError
+
+    def forward(self, pred, target, weight=None, avg_factor=None,
+                reduction_override=None, **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        assert pred.size() == target.size()
+        if target.numel() == 0:
+            return self.loss_weight * (pred.sum() * 0)
+        target = L.require_device(target.detach().contiguous().reshape(-1),
+                                  torch.float32, 'target')
+        if weight is not None:
+            weight = weight.float().expand_as(pred).reshape(-1)
+        rows = _RowLoss.apply(*self._launch(), pred.reshape(-1), weight, target,
+                              *self._consts())
+        return self.loss_weight * _reduce_weighted(rows.reshape(pred.shape),
+                                                   reduction, avg_factor)
+
+    def _consts(self):
+        return ()
+
+
 @LOSSES.register_module()
-class SmoothL1Loss(nn.Module):
-    """Only *registrable* (AnchorHead's constructor default, anchor_head.py:47-48,
-    inherited by RetinaGFLHead); every RetinaGFL config overrides it with
-    GIoULoss on decoded boxes."""
+class L1Loss(_ElementLoss):
+    """smooth_l1_loss.py:36-56,106-139."""
+
+    def _launch(self):
+        return (_launch_l1, )
+
+
+@LOSSES.register_module()
+class SmoothL1Loss(_ElementLoss):
+    """smooth_l1_loss.py:9-33,59-103.  AnchorHead's constructor default
+    (anchor_head.py:47-48); RetinaHead evaluates it inside the fused loss
+    block (LD_DELTA_SMOOTH_L1)."""
 
     def __init__(self, beta=1.0, reduction='mean', loss_weight=1.0):
-        super().__init__()
-        self.beta, self.reduction, self.loss_weight = (beta, reduction,
-                                                       loss_weight)
+        super().__init__(reduction, loss_weight)
+        assert beta > 0
+        self.beta = beta
 
-    def forward(self, *args, **kwargs):
-        raise NotImplementedError('SmoothL1Loss is not on the LD train path')
+    def _launch(self):
+        return (_launch_smooth_l1, )
+
+    def _consts(self):
+        return (self.beta, )

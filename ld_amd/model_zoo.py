@@ -276,6 +276,17 @@ def atss_gfl_detector(depth=101):
                 test_cfg=copy.deepcopy(_TEST_CFG))
 
 
+def atss_detector(depth=50):
+    """configs/atss/atss_r50_fpn_1x_coco.py:5-60: plain ATSS, the baseline the
+    ATSS-GFL / LD-ATSS rows are measured against (``depth`` 101 =
+    atss_r101_fpn_1x_coco.py)."""
+    return dict(type='ATSS', pretrained=None, backbone=_backbone(depth),
+                neck=_neck(depth),
+                bbox_head=dict(type='ATSSHead', **_atss_head_common()),
+                train_cfg=copy.deepcopy(_TRAIN_CFG),
+                test_cfg=copy.deepcopy(_TEST_CFG))
+
+
 def ld_atss_detector(student_depth=50, teacher_depth=101):
     """configs/ld/ld_r50_atss_r101_1x.py: LDATSSHead student <- ATSS-GFL
     teacher; output_feature is the detector's default (False): the head takes
@@ -470,6 +481,21 @@ def retina_gfl_detector(depth=101):
                 bbox_head=dict(type='RetinaGFLHead', **_retina_head_common()),
                 train_cfg=copy.deepcopy(_FCOS_TRAIN_CFG),
                 test_cfg=copy.deepcopy(_TEST_CFG))
+
+
+def retinanet_detector(depth=50):
+    """configs/retinanet/retinanet_r50_fpn_1x_coco.py over
+    configs/_base_/models/retinanet_r50_fpn.py:2-60: plain RetinaNet, L1Loss on
+    the deltas, NMS at IoU 0.5 (``depth`` 101 = retinanet_r101_fpn_1x_coco.py)."""
+    head = _retina_head_common()
+    head.update(loss_bbox=dict(type='L1Loss', loss_weight=1.0))
+    del head['reg_decoded_bbox']  # the deltas themselves are regressed
+    test_cfg = copy.deepcopy(_TEST_CFG)
+    test_cfg['nms'] = dict(type='nms', iou_threshold=0.5)
+    return dict(type='RetinaNet', pretrained=None,
+                backbone=_backbone(depth), neck=_retina_neck(depth),
+                bbox_head=dict(type='RetinaHead', **head),
+                train_cfg=copy.deepcopy(_FCOS_TRAIN_CFG), test_cfg=test_cfg)
 
 
 def ld_retina_detector(student_depth=50, teacher_depth=101):

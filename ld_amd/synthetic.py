@@ -841,3 +841,126 @@ def box_loss_rows(n, seed=31, img_h=160, img_w=224):
     size = (target[:, 2:] - target[:, :2]).repeat(1, 2)
     pred = target + (torch.rand(n, 4, generator=gen) - 0.5) * 0.8 * size
     return pred.contiguous(), target
+
+
+# ---------------------------------------------------------------------------
+# plain ATSSHead / RetinaHead (tests/golden/plain_heads.npz,
+# tools/gen_golden_plain_heads.py)
+# ---------------------------------------------------------------------------
+# Geometry of every plain-head case: 2 images padded to 128 x 128, the five
+# levels 16^2 .. 1^2 of strides 8 .. 128, 4 classes.
+PLAIN_PAD = (128, 128)
+PLAIN_CLASSES = 4
+PLAIN_FEAT = 8
+PLAIN_CODERS = dict(atss=((0., 0., 0., 0.), (0.1, 0.1, 0.2, 0.2)),
+                    retina=((0., 0., 0., 0.), (1., 1., 1., 1.)))
+# Hand-written GT boxes (x1, y1, x2, y2, label) per image.  'multi': the 64 px
+# box IS the ATSS anchor of level 0, cell (6, 6) (image 0) and the 32 px box the
+# RetinaNet anchor of ratio 1, scale 4 (base 3) of that cell (image 1) -- the two
+# positives whose predicted dw is set beyond the clamp (PLAIN_CLAMP); the larger
+# boxes, one of them reaching past the image, put positives on levels 1 to 3.
+PLAIN_CASES = OrderedDict(
+    multi=[[(16., 16., 80., 80., 1), (-62., -66., 190., 194., 3)],
+           [(32., 32., 64., 64., 0), (4., 8., 124., 120., 2),
+            (70.5, 3.25, 127., 41.5, 1)]],
+    empty_img=[[(16., 16., 80., 80., 1), (3., 60., 99., 126., 0)], []],
+    no_pos=[[], []])
+PLAIN_SEEDS = dict(multi=71, empty_img=72, no_pos=73)
+# (head, image, level, y, x, base anchor, delta value): reg channel base * 4 + 2
+PLAIN_CLAMP = dict(atss=(0, 0, 6, 6, 0, 30.0), retina=(1, 0, 6, 6, 3, 6.0))
+PLAIN_INFER = dict(seed=81, nms_pre=100,
+                   img_shapes=[(128, 128, 3), (120, 110, 3)],
+                   scale_factors=[[1.0, 1.0, 1.0, 1.0],
+                                  [1.25, 1.25, 1.25, 1.25]])
+
+
+def plain_batch(case, device='cpu'):
+    """gt_bboxes / gt_labels / img_metas of a PLAIN_CASES entry."""
+    gtb, gtl = [], []
+    for rows in PLAIN_CASES[case]:
+        a = torch.tensor([r[:4] for r in rows], dtype=torch.float32)
+        gtb.append(a.reshape(-1, 4).to(device))
+        gtl.append(torch.tensor([int(r[4]) for r in rows],
+                                dtype=torch.long).to(device))
+    h, w = PLAIN_PAD
+    metas = [dict(img_shape=(h, w, 3), pad_shape=(h, w, 3),
+                  ori_shape=(h, w, 3), scale_factor=1.0, flip=False)
+             for _ in gtb]
+    return dict(gt_bboxes=gtb, gt_labels=gtl, img_metas=metas)
+
+
+def plain_head_inputs(kind, seed, num_imgs=2, device='cpu', clamp=True):
+    """Head outputs of a plain head on the PLAIN_PAD pyramid: ``kind`` 'atss'
+    -> cls (N, 4, h, w), reg (N, 4, h, w) ~ 4 * randn (in units of the coder's
+    stds 0.1 / 0.2), ctr; 'retina' -> cls (N, 36, h, w), reg (N, 36, h, w) ~
+    0.5 * randn.  ``clamp``: the PLAIN_CLAMP positive's dw is set beyond
+    |log(wh_ratio_clip)|."""
+    gen = _gen(seed)
+    B = 1 if kind == 'atss' else 9
+    amp = 4.0 if kind == 'atss' else 0.5
+    out = dict(cls=[], reg=[])
+    for (h, w) in level_shapes(PLAIN_PAD):
+        out['cls'].append(
+            _normal((num_imgs, B * PLAIN_CLASSES, h, w), gen) * 1.2 - 3.0)
+        out['reg'].append(_normal((num_imgs, B * 4, h, w), gen) * amp)
+    if clamp:
+        n, l, y, x, b, v = PLAIN_CLAMP[kind]
+        out['reg'][l][n, b * 4 + 2, y, x] = v
+    if kind == 'atss':
+        out['ctr'] = synthetic_centerness(num_imgs, level_shapes(PLAIN_PAD),
+                                          seed=seed)
+    return {k: [t.to(device) for t in v] for k, v in out.items()}
+
+
+def plain_infer_inputs(kind, device='cpu'):
+    """get_bboxes inputs: class logits lifted so that a few hundred (anchor,
+    class) pairs pass score_thr, metas with a second image smaller than the
+    pad (the decode clips to img_shape) and a scale factor."""
+    cfg = PLAIN_INFER
+    hi = plain_head_inputs(kind, cfg['seed'], len(cfg['img_shapes']), device)
+    hi['cls'] = [c * 1.25 + 1.0 for c in hi['cls']]
+    metas = [dict(img_shape=s, pad_shape=PLAIN_PAD + (3, ), ori_shape=s,
+                  scale_factor=np.array(f, dtype=np.float32), flip=False)
+             for s, f in zip(cfg['img_shapes'], cfg['scale_factors'])]
+    return hi, metas
+
+
+DELTA_ROWS = 257  # two 128-thread blocks and one row
+# hand-written coder rows: (anchor, gt box, deltas to decode)
+DELTA_HAND = [
+    # a degenerate anchor, 1 pixel wide / 1 pixel high
+    ((10., 20., 11., 84.), (8., 18., 30., 90.), (0.5, -0.25, 1.0, 0.1)),
+    ((40., 7., 104., 8.), (38., 2., 110., 20.), (-0.3, 2.0, -0.2, 3.0)),
+    # dw / dh beyond the wh_ratio_clip clamp on both sides, for both std sets
+    ((16., 16., 80., 80.), (0., 0., 128., 128.), (0.0, 0.0, 30.0, -30.0)),
+    ((16., 16., 80., 80.), (20., 20., 60., 70.), (1.0, -1.0, -25.0, 22.0)),
+    ((32., 32., 64., 64.), (30., 30., 70., 60.), (0.1, 0.2, 4.5, -4.5)),
+    ((32., 32., 64., 64.), (33., 31., 63., 65.), (-0.1, 0.3, -4.2, 4.2)),
+    # exactly at the clamp of the unit-std coder: |log(16 / 1000)|
+    ((0., 0., 32., 32.), (1., 1., 31., 31.),
+     (0.0, 0.0, 4.135166556742356, -4.135166556742356)),
+    # decoded boxes that cross max_shape on every side
+    ((-20., -30., 44., 34.), (-10., -10., 50., 40.), (-1.0, -1.0, 0.5, 0.5)),
+    ((100., 90., 164., 154.), (90., 100., 170., 150.), (1.0, 1.0, 0.8, 0.9)),
+    ((60., 60., 68., 68.), (0., 0., 128., 128.), (0.0, 0.0, 3.5, 3.5)),
+]
+DELTA_MAX_SHAPE = (120, 110, 3)
+
+
+def delta_coder_rows(n=DELTA_ROWS, seed=91):
+    """(anchors, gts, deltas), each (n, 4): DELTA_HAND first, then seeded rows
+    -- anchors and GT boxes in and around a 128 px image, deltas ~ randn with
+    every ninth row's dw / dh scaled past the clamp."""
+    gen = _gen(seed)
+    m = n - len(DELTA_HAND)
+    anchors, _ = synthetic_boxes(m, 128, 128, gen, min_size=4.0, max_size=128.0)
+    gts, _ = synthetic_boxes(m, 128, 128, gen, min_size=2.0, max_size=128.0)
+    anchors = anchors + (torch.rand(m, 4, generator=gen) - 0.5) * 40.0
+    anchors[:, 2:] = torch.maximum(anchors[:, 2:], anchors[:, :2] + 1.0)
+    deltas = _normal((m, 4), gen)
+    deltas[::9, 2:] = deltas[::9, 2:] * 25.0
+    hand = [torch.tensor([r[i] for r in DELTA_HAND], dtype=torch.float32)
+            for i in range(3)]
+    return (torch.cat([hand[0], anchors]).contiguous(),
+            torch.cat([hand[1], gts]).contiguous(),
+            torch.cat([hand[2], deltas]).contiguous())
