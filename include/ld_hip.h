@@ -144,6 +144,20 @@ typedef struct {
  * launch, no teacher maps, the DFL, LD, VLR-LD, KD and IM rows of the table are
  * zero (set lw_kd = 0).  The coder travels beside hp in an ld_delta_t. */
 #define LD_LOSS_DELTA 32
+/* Plain FCOSHead (fcos_head.py:157-254): with LD_LOSS_ATSS | LD_LOSS_FCOS (which
+ * keep the FocalLoss, the centerness BCE, the point geometry and the (l, t, r, b)
+ * targets of ld_fcos_targets), never with LD_LOSS_DELTA, LD_LOSS_RETINA or
+ * LD_LOSS_PROB_CLS.  The reg maps carry 4 ACTIVATED distances per point
+ * (ld_scale_act_levels_forward: exp or relu of the scaled conv output).  The
+ * block runs as ld_loss_dist_prepass -> ld_loss_dist_pos -> ld_loss_main_parts(
+ * LD_LOSS_PART_CLS) -> ld_loss_centerness -> ld_loss_finalize; the DFL, LD,
+ * VLR-LD, KD and IM rows are zero.  loss_cls and loss_centerness are divided by
+ * max(num_pos, 1), loss_bbox by max(sum of the centerness targets, 1e-6).
+ * LD_LOSS_DIST_NORM (only with LD_LOSS_DIST) = norm_on_bbox: the targets are
+ * divided by the level's stride and compared with the prediction as it is, about
+ * the pixel points (fcos_head.py:233-236, 524-525). */
+#define LD_LOSS_DIST 64
+#define LD_LOSS_DIST_NORM 128
 
 /* DeltaXYWHBBoxCoder (delta_xywh_bbox_coder.py:26-237) and what the box term of
  * an LD_LOSS_DELTA block does with it. */
@@ -390,6 +404,29 @@ int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                       const float* score, const float* norm, const float* upstream,
                       const ld_maps_t* grad_reg, void* workspace,
                       size_t workspace_bytes, ld_stream_t stream);
+
+/* The two launches an LD_LOSS_DIST block has of its own.  reg / grad_reg:
+ * (N, 4, H_l, W_l) maps of activated distances; bbox_targets: ld_fcos_targets'
+ * (l, t, r, b) in pixels.
+ * prepass: score = the centerness target sqrt(min(l, r) / max(l, r) * min(t, b) /
+ * max(t, b)) of the positives, weight_targets = 0, norm as ld_loss_prepass
+ * leaves it (num_pos, sum of the centerness targets).
+ * pos: hp's LD_LOSS_BBOX_* loss on (px - d0, py - d1, px + d2, py + d3) against
+ * the same form of the targets, (px, py) = (x, y) * stride + stride / 2, weighted
+ * by the centerness target; d(loss)/d(d) = (-g.x1, -g.y1, +g.x2, +g.y2), written
+ * dense into grad_reg (zeros away from the positives), and the class-softmax
+ * statistics ld_loss_main_parts(CLS) reads.  Any other flag combination than the
+ * one LD_LOSS_DIST names: LD_EINVAL.  Same workspace as the other parts. */
+int ld_loss_dist_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                         const int64_t* labels, const float* bbox_targets,
+                         const int32_t* counts, float* weight_targets, float* score,
+                         float* norm, void* workspace, size_t workspace_bytes,
+                         ld_stream_t stream);
+int ld_loss_dist_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                     const ld_maps_t* cls, const ld_maps_t* reg, const int64_t* labels,
+                     const float* bbox_targets, const float* score, const float* norm,
+                     const float* upstream, const ld_maps_t* grad_reg, void* workspace,
+                     size_t workspace_bytes, ld_stream_t stream);
 
 /* The 'gibox' imitation region (LDHead.get_gi_region, ld_head.py:613-637;
  * LDv2Head: ld_gflv2.py:619-644 with hp->flags & LD_LOSS_PROB_CLS): per level,
@@ -1134,6 +1171,27 @@ int ld_scale_levels_backward(const ld_levels_t* lv, const float* dy, const float
                              const float* scales, int rows, float* dx,
                              float* dscales, int accumulate, void* workspace,
                              size_t workspace_bytes, ld_stream_t stream);
+/* Scale followed by the activation of FCOSHead's box branch
+ * (fcos_head.py:145-153), all levels in one launch: with u = x * scales[level],
+ *   LD_SCALE_ACT_EXP          y = exp(u)
+ *   LD_SCALE_ACT_RELU         y = max(u, 0)            (norm_on_bbox, training)
+ *   LD_SCALE_ACT_RELU_STRIDE  y = max(u, 0) * strides[level]   (eval mode)
+ * ``strides``: host array of lv->num_levels ints, read only by RELU_STRIDE.
+ * backward: dx = s * y' * dy and dscales[l] = sum over level l of x * y' * dy,
+ * y' = y (EXP) or [u > 0] (* stride), the partial sums in fp64 and in the fixed
+ * order of ld_scale_levels_backward (its workspace size; no float atomics).
+ * ``y``: the forward output (read by EXP only, may be NULL otherwise). */
+#define LD_SCALE_ACT_EXP 0
+#define LD_SCALE_ACT_RELU 1
+#define LD_SCALE_ACT_RELU_STRIDE 2
+int ld_scale_act_levels_forward(const ld_levels_t* lv, const float* x,
+                                const float* scales, const int32_t* strides, int mode,
+                                int rows, float* y, ld_stream_t stream);
+int ld_scale_act_levels_backward(const ld_levels_t* lv, const float* dy, const float* x,
+                                 const float* y, const float* scales,
+                                 const int32_t* strides, int mode, int rows, float* dx,
+                                 float* dscales, int accumulate, void* workspace,
+                                 size_t workspace_bytes, ld_stream_t stream);
 /* torch.optim.SGD(momentum, weight_decay) over a flat parameter arena
  * (apis/train.py:88): d = g*grad_scale + wd*p; buf = mu*buf + d; p -= lr*buf. */
 int ld_sgd_step(float* params, const float* grads, float* momentum_buf, size_t n,
@@ -1587,11 +1645,17 @@ int ld_get_bboxes_voting(const ld_geom_t* g, const ld_maps_t* cls, const ld_maps
  * (cells * num_base, 4) list in candidate-row order, or NULL with num_base = 1
  * for the square anchor of side anchor_scale * stride).  reg_max is ignored.
  * Everything around the decode -- keys, top-k, centerness factor, NMS, rescale
- * -- is unchanged.  Without the flag ``delta`` / ``anchors`` are not read. */
+ * -- is unchanged.  Without the flag ``delta`` / ``anchors`` are not read.
+ * LD_INFER_DIST (FCOSHead._get_bboxes, fcos_head.py:322-454; only with
+ * LD_INFER_POINTS and num_base = 1, not with LD_INFER_DELTA): the reg maps are
+ * (N, 4, H, W) distances in pixels; a candidate is distance2bbox(point, d,
+ * max_shape=img_shape).  reg_max, ``delta`` and ``anchors`` are ignored;
+ * everything around the decode is unchanged. */
 #define LD_INFER_VOTING 1
 #define LD_INFER_PROB 2
 #define LD_INFER_POINTS 4
 #define LD_INFER_DELTA 16 /* 8 is LD_AUG_RESCALE of ld_aug_merge_nms */
+#define LD_INFER_DIST 32
 size_t ld_get_bboxes_ex_workspace_bytes(const ld_geom_t* g, int num_classes,
                                        int num_base, int nms_pre);
 int ld_get_bboxes_ex(const ld_geom_t* g, const ld_maps_t* cls, const ld_maps_t* reg,

@@ -255,7 +255,10 @@ __global__ __launch_bounds__(kSortThreads) void infer_topk_sort_kernel(
 // is decoded about its anchor -- row (level's first cell * B + a) of `anchors`,
 // or the square of side anchor_scale * stride -- and clipped to the image
 // (delta2bbox with max_shape, atss_head.py:470-480, anchor_head.py:690-700).
-template <bool DELTA>
+// DIST (LD_INFER_DIST): the reg maps hold 4 distances in pixels, decoded about
+// the point (distance2bbox with max_shape, fcos_head.py:402).
+enum { kDecodeIntegral = 0, kDecodeDelta = 1, kDecodeDist = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void infer_decode_kernel(
     Plan p, ld_maps_t cls, ld_maps_t reg, ld_maps_t ctr,
     const unsigned long long* keys, const float* img_hw, const float* scale_factors,
@@ -282,11 +285,19 @@ __global__ __launch_bounds__(256) void infer_decode_kernel(
   const int half = p.points ? s / 2 : 0;
   const float cx = (float)(x * s + half), cy = (float)(y * s + half);
   const float* rbase = reg.ptr[l] + (size_t)n * reg.stride_n[l] +
-                       (size_t)b * (DELTA ? 4 : 68) * reg.stride_c[l] + cell;
+                       (size_t)b * (MODE == kDecodeIntegral ? 68 : 4) * reg.stride_c[l] +
+                       cell;
   float d[4];
   const float Hi = img_hw[n * 2 + 0], Wi = img_hw[n * 2 + 1];
   float bx[4];
-  if (DELTA) {
+  if (MODE == kDecodeDist) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = rbase[(size_t)k * reg.stride_c[l]];
+    bx[0] = cx - d[0];
+    bx[1] = cy - d[1];
+    bx[2] = cx + d[2];
+    bx[3] = cy + d[3];
+  } else if (MODE == kDecodeDelta) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) d[k] = rbase[(size_t)k * reg.stride_c[l]];
     ld::Box an;
@@ -711,7 +722,7 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
                            int num_base = 1, float* pre_boxes = nullptr,
                            float* pre_scores = nullptr, float* pre_factors = nullptr,
                            const ld_delta_t* delta = nullptr,
-                           const float* anchors = nullptr) {
+                           const float* anchors = nullptr, bool dist = false) {
   Plan p;
   if (int e = make_plan(g, num_classes, nms_pre, &p, num_base)) return e;
   p.prob = prob ? 1 : 0;
@@ -723,7 +734,8 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
   if (!cls || !reg || !img_hw) return LD_EINVAL;
   if (pre_only ? !pre_scores : (!dets || !labels || !counts)) return LD_EINVAL;
   if (pre_only) max_per_img = 1;  // unused
-  if (!delta && reg_max != 16) return LD_EUNSUPPORTED;  // 17-bin Integral only
+  if (dist && (delta || !points || num_base != 1)) return LD_EINVAL;
+  if (!delta && !dist && reg_max != 16) return LD_EUNSUPPORTED;  // 17-bin Integral only
   if (delta) {
     if (points || !(delta->max_ratio >= 0.0f)) return LD_EINVAL;
     // an explicit list gives every (cell, base) row its anchor; the implicit
@@ -771,13 +783,18 @@ static int get_bboxes_impl(const ld_geom_t* g, const ld_maps_t* cls,
       LD_LAUNCH(infer_topk_sort_kernel, dim3(nsorted, p.N),
                          dim3(kSortThreads), 0, stream, p, keys);
   }
-  if (delta)
-    LD_LAUNCH(infer_decode_kernel<true>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
+  if (dist)
+    LD_LAUNCH(infer_decode_kernel<kDecodeDist>, dim3((p.Ktot + 255) / 256, p.N), dim3(256),
+                       0, stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors,
+                       score_thr, boxes, scores, cand, count, maxc, pre_factors,
+                       ld_delta_t{}, (const float*)nullptr, 0);
+  else if (delta)
+    LD_LAUNCH(infer_decode_kernel<kDecodeDelta>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
                        stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors,
                        score_thr, boxes, scores, cand, count, maxc, pre_factors, *delta,
                        anchors, g->anchor_scale);
   else
-    LD_LAUNCH(infer_decode_kernel<false>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
+    LD_LAUNCH(infer_decode_kernel<kDecodeIntegral>, dim3((p.Ktot + 255) / 256, p.N), dim3(256), 0,
                        stream, p, *cls, *reg, ctr_maps, keys, img_hw, scale_factors,
                        score_thr, boxes, scores, cand, count, maxc, pre_factors,
                        ld_delta_t{}, (const float*)nullptr, 0);
@@ -832,16 +849,18 @@ extern "C" int ld_get_bboxes_ex(const ld_geom_t* g, const ld_maps_t* cls,
                                 const float* anchors, float* dets, int64_t* labels,
                                 int32_t* counts, void* workspace,
                                 size_t workspace_bytes, ld_stream_t stream) {
-  if (flags & ~(LD_INFER_VOTING | LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA))
+  if (flags & ~(LD_INFER_VOTING | LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA |
+                LD_INFER_DIST))
     return LD_EINVAL;
   const bool dl = (flags & LD_INFER_DELTA) != 0;
-  if (dl && !delta) return LD_EINVAL;
+  if (dl && (!delta || (flags & LD_INFER_DIST))) return LD_EINVAL;
   return get_bboxes_impl(g, cls, reg, num_classes, reg_max, img_hw, scale_factors,
                          nms_pre, score_thr, iou_thr, max_per_img, dets, labels,
                          counts, workspace, workspace_bytes, stream,
                          (flags & LD_INFER_VOTING) != 0, (flags & LD_INFER_PROB) != 0,
                          ctr, (flags & LD_INFER_POINTS) != 0, num_base, nullptr, nullptr,
-                         nullptr, dl ? delta : nullptr, dl ? anchors : nullptr);
+                         nullptr, dl ? delta : nullptr, dl ? anchors : nullptr,
+                         (flags & LD_INFER_DIST) != 0);
 }
 
 extern "C" int ld_get_bboxes_num_selected(const ld_geom_t* g, int num_base, int nms_pre) {
@@ -858,15 +877,17 @@ extern "C" int ld_get_bboxes_pre_nms(const ld_geom_t* g, const ld_maps_t* cls,
                                      const float* anchors, float* boxes, float* scores,
                                      float* factors, void* workspace,
                                      size_t workspace_bytes, ld_stream_t stream) {
-  if (flags & ~(LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA)) return LD_EINVAL;
+  if (flags & ~(LD_INFER_PROB | LD_INFER_POINTS | LD_INFER_DELTA | LD_INFER_DIST))
+    return LD_EINVAL;
   if (!boxes || !scores || (factors && !ctr)) return LD_EINVAL;
   const bool dl = (flags & LD_INFER_DELTA) != 0;
-  if (dl && !delta) return LD_EINVAL;
+  if (dl && (!delta || (flags & LD_INFER_DIST))) return LD_EINVAL;
   return get_bboxes_impl(g, cls, reg, num_classes, reg_max, img_hw, scale_factors,
                          nms_pre, 0.0f, 0.5f, 1, nullptr, nullptr, nullptr, workspace,
                          workspace_bytes, stream, false, (flags & LD_INFER_PROB) != 0, ctr,
                          (flags & LD_INFER_POINTS) != 0, num_base, boxes, scores, factors,
-                         dl ? delta : nullptr, dl ? anchors : nullptr);
+                         dl ? delta : nullptr, dl ? anchors : nullptr,
+                         (flags & LD_INFER_DIST) != 0);
 }
 
 // ---- test-time augmentation: merge the views, then multiclass_nms ----------------

@@ -84,6 +84,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 // (ld_head.py:362-365); LDATSSHead sum(centerness targets), 1 if < EPS
 // (ld_atss.py:245-249)
 __device__ __forceinline__ float avg_divisor(const ld_loss_hp_t& hp, const float* norm) {
+  // FCOSHead: max(sum(centerness targets), 1e-6) (fcos_head.py:238-239)
+  if (hp.flags & LD_LOSS_DIST) return fmaxf(norm[1], 1e-6f);
   if (hp.flags & LD_LOSS_ATSS) return norm[1] < 1e-12f ? 1.0f : norm[1];
   // LDRetinaHead: loss_bbox(avg_factor = num_total_samples), ld_retina.py:104-108
   if (hp.flags & LD_LOSS_RETINA) return fmaxf(norm[0], 1.0f);
@@ -266,6 +268,24 @@ __device__ __forceinline__ size_t part_idx(int slot, int z, const BlockMap& bm, 
   return ((size_t)slot * kZMax + z) * nb + (size_t)n * bm.blocks_per_img + blockIdx.x;
 }
 
+// the box loss of a launch (LD_LOSS_BBOX_* in hp.flags; 0 = GIoU) on one pair
+// of boxes: the loss, bbox_overlaps' IoU and d(loss)/d(pred box)
+__device__ __forceinline__ float bbox_loss_grad(const ld_loss_hp_t& hp, const Box& box,
+                                                const Box& tgt, float* iou, float g[4]) {
+  switch ((hp.flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) {
+    case LD_LOSS_BBOX_IOU:
+      return ld::iou_loss_grad(box, tgt, hp.giou_eps, false, iou, g);
+    case LD_LOSS_BBOX_IOU_LINEAR:
+      return ld::iou_loss_grad(box, tgt, hp.giou_eps, true, iou, g);
+    case LD_LOSS_BBOX_DIOU:
+      return ld::diou_loss_grad(box, tgt, hp.giou_eps, iou, g);
+    case LD_LOSS_BBOX_CIOU:
+      return ld::ciou_loss_grad(box, tgt, hp.giou_eps, iou, g);
+    default:
+      return ld::giou_loss_grad(box, tgt, hp.giou_eps, iou, g);
+  }
+}
+
 // ------------------------------------------ positives: box loss + KD stats
 __global__ __launch_bounds__(kBlk) void loss_pos_kernel(
     ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t t_cls,
@@ -306,24 +326,7 @@ __global__ __launch_bounds__(kBlk) void loss_pos_kernel(
       const float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
       const Box tgt = target_box(fcos, cx, cy, t, stride);
       float iou, g[4];
-      // the box loss of the launch (LD_LOSS_BBOX_* in hp.flags; 0 = GIoU)
-      float gl;
-      switch ((hp.flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) {
-        case LD_LOSS_BBOX_IOU:
-          gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, false, &iou, g);
-          break;
-        case LD_LOSS_BBOX_IOU_LINEAR:
-          gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, true, &iou, g);
-          break;
-        case LD_LOSS_BBOX_DIOU:
-          gl = ld::diou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-          break;
-        case LD_LOSS_BBOX_CIOU:
-          gl = ld::ciou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-          break;
-        default:
-          gl = ld::giou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-      }
+      const float gl = bbox_loss_grad(hp, box, tgt, &iou, g);
       s_bbox = wt * gl;
       // softmax statistics of the class logits at temperature T_kd
       const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
@@ -1083,6 +1086,22 @@ __device__ __forceinline__ Box delta_target(const ld_loss_hp_t& hp, const ld_del
   return ld::delta2bbox(anchor, td, dc.means, dc.stds, dc.max_ratio, nullptr);
 }
 
+// The positives record of a plain (teacher-less) block: the softmax statistics
+// of the class logits the CLS part reads (its KD term has weight zero here;
+// student == teacher).
+__device__ __forceinline__ void plain_cls_stats(const ld_loss_hp_t& hp, const ld_maps_t& cls,
+                                                const Cell& c, float* __restrict__ posrec) {
+  const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
+  const float invT = 1.0f / hp.T_kd;
+  float ms = *chan_ptr(cls, c, 0);
+  for (int ch = 1; ch < C; ++ch) ms = fmaxf(ms, *chan_ptr(cls, c, ch));
+  float zs = 0.0f;
+  for (int ch = 0; ch < C; ++ch) zs += expf((*chan_ptr(cls, c, ch) - ms) * invT);
+  float4* rec = reinterpret_cast<float4*>(posrec + c.o * kPosRec);
+  rec[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  rec[1] = make_float4(ms, zs, ms, zs);
+}
+
 __global__ __launch_bounds__(kWave) void loss_delta_prepass_kernel(
     ld_geom_t geom, ld_loss_hp_t hp, ld_delta_t dc, BlockMap bm,
     const float* __restrict__ anchors, const int64_t* __restrict__ labels,
@@ -1135,25 +1154,10 @@ __global__ __launch_bounds__(kBlk) void loss_delta_pos_kernel(
         // centerness target (ATSS) / bbox_weights = 1 (Retina)
         const float wt = (hp.flags & LD_LOSS_ATSS) ? score[c.o] : 1.0f;
         const float c_bbox = up_bbox * hp.lw_bbox * wt * inv_avg;
-        float jac[4], iou, g[4], gl;
+        float jac[4], iou, g[4];
         const Box box = ld::delta2bbox(an, d, dc.means, dc.stds, dc.max_ratio, jac);
         const Box tgt = delta_target(hp, dc, an, t);
-        switch ((hp.flags >> LD_LOSS_BBOX_SHIFT) & LD_LOSS_BBOX_MASK) {
-          case LD_LOSS_BBOX_IOU:
-            gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, false, &iou, g);
-            break;
-          case LD_LOSS_BBOX_IOU_LINEAR:
-            gl = ld::iou_loss_grad(box, tgt, hp.giou_eps, true, &iou, g);
-            break;
-          case LD_LOSS_BBOX_DIOU:
-            gl = ld::diou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-            break;
-          case LD_LOSS_BBOX_CIOU:
-            gl = ld::ciou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-            break;
-          default:
-            gl = ld::giou_loss_grad(box, tgt, hp.giou_eps, &iou, g);
-        }
+        const float gl = bbox_loss_grad(hp, box, tgt, &iou, g);
         s_bbox = wt * gl;
         ld::delta2bbox_grad(g, jac, gd);
 #pragma unroll
@@ -1172,17 +1176,87 @@ __global__ __launch_bounds__(kBlk) void loss_delta_pos_kernel(
           gd[k] = c_bbox * dl;
         }
       }
-      // softmax statistics of the class logits for the CLS part (its KD term
-      // has weight zero here; student == teacher)
-      const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
-      const float invT = 1.0f / hp.T_kd;
-      float ms = *chan_ptr(cls, c, 0);
-      for (int ch = 1; ch < C; ++ch) ms = fmaxf(ms, *chan_ptr(cls, c, ch));
-      float zs = 0.0f;
-      for (int ch = 0; ch < C; ++ch) zs += expf((*chan_ptr(cls, c, ch) - ms) * invT);
-      float4* rec = reinterpret_cast<float4*>(posrec + c.o * kPosRec);
-      rec[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-      rec[1] = make_float4(ms, zs, ms, zs);
+      plain_cls_stats(hp, cls, c, posrec);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) *chan_ptr_w(grad_reg, c, k) = gd[k];
+  }
+  s_bbox = block_sum(s_bbox, lds4);
+  if (threadIdx.x == 0) partial[part_idx(S_BBOX, 0, bm, c.n)] = s_bbox;
+}
+
+// --------------------- plain FCOS: 4 activated distances (LD_LOSS_DIST) -------
+// FCOSHead.loss (fcos_head.py:157-254) on (N, 4, H, W) maps of exp / relu
+// activated (l, t, r, b) distances.  bbox_targets hold ld_fcos_targets' pixel
+// distances; with LD_LOSS_DIST_NORM (norm_on_bbox) they are divided by the
+// level's stride first (fcos_head.py:524-525) and the prediction is in stride
+// units already, while the points stay in pixels (:233-236).
+__device__ __forceinline__ float4 dist_target(const ld_geom_t& g, const ld_loss_hp_t& hp,
+                                              const float* __restrict__ bbox_targets,
+                                              const Cell& c) {
+  float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
+  if (hp.flags & LD_LOSS_DIST_NORM) {
+    const float s = (float)g.lv[c.l].stride;
+    t = make_float4(t.x / s, t.y / s, t.z / s, t.w / s);
+  }
+  return t;
+}
+
+__global__ __launch_bounds__(kWave) void loss_dist_prepass_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, const int64_t* __restrict__ labels,
+    const float* __restrict__ bbox_targets, float* __restrict__ weight_targets,
+    float* __restrict__ score, float* __restrict__ partial) {
+  const Cell c = locate(geom, bm);
+  float sc = 0.0f;
+  if (c.active) {
+    const int64_t lab = labels[c.o];
+    if (lab >= 0 && lab < hp.num_classes) {
+      // centerness_target, fcos_head.py:590-608
+      const float4 t = dist_target(geom, hp, bbox_targets, c);
+      sc = sqrtf((fminf(t.x, t.z) / fmaxf(t.x, t.z)) *
+                 (fminf(t.y, t.w) / fmaxf(t.y, t.w)));
+    }
+    weight_targets[c.o] = 0.0f;
+    score[c.o] = sc;
+  }
+  const float s = wave_sum(sc);
+  if (threadIdx.x == 0)
+    partial[(size_t)S_WSUM * gridDim.y * bm.blocks_per_img +
+            (size_t)c.n * bm.blocks_per_img + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kBlk) void loss_dist_pos_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t reg,
+    const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
+    const float* __restrict__ score, const float* __restrict__ norm,
+    const float* __restrict__ upstream, ld_maps_t grad_reg, float* __restrict__ posrec,
+    float* __restrict__ partial) {
+  __shared__ float lds4[4];
+  const Cell c = locate256(geom, bm);
+  float s_bbox = 0.0f;
+  if (c.active) {
+    const int64_t lab = labels[c.o];
+    float gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (lab >= 0 && lab < hp.num_classes) {
+      const float up_bbox = upstream ? upstream[1 * geom.num_levels + c.l] : 1.0f;
+      const float wt = score[c.o];  // the centerness target
+      const float c_bbox = up_bbox * hp.lw_bbox * wt / avg_divisor(hp, norm);
+      // the point (x, y) * stride + stride // 2, in pixels
+      const int stride = geom.lv[c.l].stride;
+      const float px = (float)(c.x * stride + stride / 2);
+      const float py = (float)(c.y * stride + stride / 2);
+      const float4 t = dist_target(geom, hp, bbox_targets, c);
+      // distance2bbox of prediction and target about the same point
+      const Box box{px - *chan_ptr(reg, c, 0), py - *chan_ptr(reg, c, 1),
+                    px + *chan_ptr(reg, c, 2), py + *chan_ptr(reg, c, 3)};
+      const Box tgt{px - t.x, py - t.y, px + t.z, py + t.w};
+      float iou, g[4];
+      s_bbox = wt * bbox_loss_grad(hp, box, tgt, &iou, g);
+      gd[0] = -c_bbox * g[0];
+      gd[1] = -c_bbox * g[1];
+      gd[2] = c_bbox * g[2];
+      gd[3] = c_bbox * g[3];
+      plain_cls_stats(hp, cls, c, posrec);
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) *chan_ptr_w(grad_reg, c, k) = gd[k];
@@ -1210,8 +1284,8 @@ __global__ __launch_bounds__(kWave) void loss_finalize_kernel(
                   : (k == S_CLS || k == S_KD)  ? zcls
                   : k == S_IM                  ? zim
                                                : 4;
-    // LD_LOSS_DELTA: no REG / IM launch has written these slots
-    const bool unwritten = (hp.flags & LD_LOSS_DELTA) &&
+    // LD_LOSS_DELTA / LD_LOSS_DIST: no REG / IM launch has written these slots
+    const bool unwritten = (hp.flags & (LD_LOSS_DELTA | LD_LOSS_DIST)) &&
                            (k == S_DFL || k == S_LD || k == S_VLR || k == S_IM);
     if ((k == S_WSUM && !(hp.flags & LD_LOSS_ATSS)) || unwritten) {
       acc[k] = 0.0f;
@@ -1333,6 +1407,16 @@ int check_geom(const ld_geom_t* g) {
   return 0;
 }
 
+// LD_LOSS_DIST: FCOS points, FocalLoss + centerness, and nothing of the other
+// box branches; LD_LOSS_DIST_NORM is its modifier
+int check_dist(const ld_loss_hp_t* hp) {
+  const int need = LD_LOSS_DIST | LD_LOSS_ATSS | LD_LOSS_FCOS;
+  if ((hp->flags & need) != need ||
+      (hp->flags & (LD_LOSS_DELTA | LD_LOSS_RETINA | LD_LOSS_PROB_CLS)))
+    return LD_EINVAL;
+  return 0;
+}
+
 int check_hp(const ld_loss_hp_t* hp) {
   if (!hp) return LD_EINVAL;
   if (hp->reg_max != 16 || hp->qfl_beta != 2.0f) return LD_EUNSUPPORTED;
@@ -1341,6 +1425,7 @@ int check_hp(const ld_loss_hp_t* hp) {
     return LD_EINVAL;
   if (hp->T_ld < 1.0f || hp->T_ld_vlr < 1.0f || hp->T_kd < 1.0f)
     return LD_EINVAL;  // kd_loss.py:51 assert T >= 1
+  if (hp->flags & (LD_LOSS_DIST | LD_LOSS_DIST_NORM)) return check_dist(hp);
   return 0;
 }
 
@@ -1497,6 +1582,8 @@ extern "C" int ld_loss_prepass_ex(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   if (int e = check_hp(hp)) return e;
   if ((hp->flags & LD_LOSS_FCOS) && (!vlr || !(hp->flags & LD_LOSS_ATSS)))
     return LD_EINVAL;
+  // 4 distance channels are not what this prepass reads: ld_loss_dist_prepass
+  if (hp->flags & LD_LOSS_DIST) return LD_EINVAL;
   if (!cls || !reg || !labels || !bbox_targets || !counts || !weight_targets ||
       !score || !norm)
     return LD_EINVAL;
@@ -1546,7 +1633,8 @@ extern "C" int ld_loss_main_parts(
        hp->T_ld != hp->T_ld_vlr))
     return LD_EINVAL;
   // the 4-channel reg maps of a delta block are not what POS / REG read
-  if ((hp->flags & LD_LOSS_DELTA) && (parts & ~LD_LOSS_PART_CLS)) return LD_EINVAL;
+  if ((hp->flags & (LD_LOSS_DELTA | LD_LOSS_DIST)) && (parts & ~LD_LOSS_PART_CLS))
+    return LD_EINVAL;
   hipStream_t stream = (hipStream_t)stream_;
   const LossWs w = loss_ws(*geom);
   const BlockMap& bm = w.bm256;
@@ -1703,6 +1791,55 @@ extern "C" int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   return (int)hipGetLastError();
 }
 
+extern "C" int ld_loss_dist_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                                    const int64_t* labels, const float* bbox_targets,
+                                    const int32_t* counts, float* weight_targets,
+                                    float* score, float* norm, void* workspace,
+                                    size_t workspace_bytes, ld_stream_t stream_) {
+  if (int e = check_geom(geom)) return e;
+  if (int e = check_hp(hp)) return e;
+  if (int e = check_dist(hp)) return e;
+  if (!labels || !bbox_targets || !counts || !weight_targets || !score || !norm)
+    return LD_EINVAL;
+  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
+    return LD_ENOSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const BlockMap bm = make_block_map(*geom, kWave);
+  float* partial = (float*)workspace;
+  LD_LAUNCH(loss_dist_prepass_kernel, dim3(bm.blocks_per_img, geom->num_imgs),
+                     dim3(kWave), 0, stream, *geom, *hp, bm, labels, bbox_targets,
+                     weight_targets, score, partial);
+  const int nparts = geom->num_imgs * bm.blocks_per_img;
+  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
+                     partial + (size_t)S_WSUM * nparts, counts,
+                     geom->num_imgs + 2 * geom->num_levels, norm);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_loss_dist_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+                                const ld_maps_t* cls, const ld_maps_t* reg,
+                                const int64_t* labels, const float* bbox_targets,
+                                const float* score, const float* norm,
+                                const float* upstream, const ld_maps_t* grad_reg,
+                                void* workspace, size_t workspace_bytes,
+                                ld_stream_t stream_) {
+  if (int e = check_geom(geom)) return e;
+  if (int e = check_hp(hp)) return e;
+  if (int e = check_dist(hp)) return e;
+  if (!cls || !reg || !labels || !bbox_targets || !score || !norm || !grad_reg)
+    return LD_EINVAL;
+  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
+    return LD_ENOSPACE;
+  const LossWs w = loss_ws(*geom);
+  float* partial = (float*)workspace + w.pre_floats;
+  float* posrec = partial + w.main_floats;
+  LD_LAUNCH(loss_dist_pos_kernel, dim3(w.bm256.blocks_per_img, geom->num_imgs),
+                     dim3(kBlk), 0, (hipStream_t)stream_, *geom, *hp, w.bm256, *cls, *reg,
+                     labels, bbox_targets, score, norm, upstream, *grad_reg, posrec,
+                     partial);
+  return (int)hipGetLastError();
+}
+
 extern "C" int ld_loss_main(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                             const ld_maps_t* cls, const ld_maps_t* reg,
                             const ld_maps_t* t_cls, const ld_maps_t* t_reg,
@@ -1754,7 +1891,7 @@ extern "C" int ld_gi_region(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   if (int e = check_geom(geom)) return e;
   if (int e = check_hp(hp)) return e;
   if (!cls || !reg || !t_cls || !t_reg || !im || !counts || topn < 1 ||
-      !(iou_thr >= 0.0f))
+      !(iou_thr >= 0.0f) || (hp->flags & LD_LOSS_DIST))
     return LD_EINVAL;
   if (!workspace || workspace_bytes < ld_gi_region_workspace_bytes(geom))
     return LD_ENOSPACE;

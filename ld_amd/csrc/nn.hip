@@ -1744,6 +1744,82 @@ __global__ void scale_levels_bwd_final_kernel(const double* __restrict__ partial
   dscale[l] = accumulate ? dscale[l] + (float)s : (float)s;
 }
 
+// ------------------------------- Scale + activation (FCOSHead's box branch) --
+// u = x * scale[level(p)]; y = exp(u) | relu(u) | relu(u) * stride[level(p)]
+// (fcos_head.py:145-153).  expf is OCML's (documented at 1 ulp); torch.exp on
+// the device calls the same function, so y equals torch's (scale(x)).exp() bit
+// for bit there, and is within 1 ulp (1.2e-7 relative) of a correctly rounded
+// exp.  relu keeps a NaN, as torch's does.
+struct LevelMul {
+  float m[LD_MAX_LEVELS];
+};
+
+// d y / d u at one element
+template <int MODE>
+__device__ __forceinline__ float scale_act_slope(float u, float y, float mul) {
+  if (MODE == LD_SCALE_ACT_EXP) return y;
+  const float on = u > 0.0f ? 1.0f : 0.0f;
+  return MODE == LD_SCALE_ACT_RELU ? on : on * mul;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void scale_act_levels_kernel(
+    const float* __restrict__ x, Levels lv, const float* __restrict__ scales, LevelMul mul,
+    float* __restrict__ y) {
+  const int row = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= lv.P) return;
+  const int l = level_of_pos(lv, p);
+  const size_t idx = (size_t)row * lv.P + p;
+  const float u = x[idx] * scales[l];
+  if (MODE == LD_SCALE_ACT_EXP) {
+    y[idx] = expf(u);
+  } else {
+    const float r = (u > 0.0f || u != u) ? u : 0.0f;
+    y[idx] = MODE == LD_SCALE_ACT_RELU ? r : r * mul.m[l];
+  }
+}
+
+// dx = scale * y' * dy
+template <int MODE>
+__global__ __launch_bounds__(256) void scale_act_levels_bwd_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
+    Levels lv, const float* __restrict__ scales, LevelMul mul, float* __restrict__ dx) {
+  const int row = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= lv.P) return;
+  const int l = level_of_pos(lv, p);
+  const size_t idx = (size_t)row * lv.P + p;
+  const float sc = scales[l];
+  const float yv = MODE == LD_SCALE_ACT_EXP ? y[idx] : 0.0f;
+  dx[idx] = sc * (scale_act_slope<MODE>(x[idx] * sc, yv, mul.m[l]) * dy[idx]);
+}
+
+// dscale[l] = sum x * y' * dy over level l: the split and the order of
+// scale_levels_bwd_partial_kernel; scale_levels_bwd_final_kernel adds them
+template <int MODE>
+__global__ __launch_bounds__(256) void scale_act_levels_bwd_partial_kernel(
+    const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ y,
+    Levels lv, const float* __restrict__ scales, LevelMul mul, int rows,
+    double* __restrict__ partial) {
+  const int l = blockIdx.x / kScaleSplit, sp = blockIdx.x % kScaleSplit;
+  const int A = lv.off[l + 1] - lv.off[l];
+  const long long total = (long long)rows * A;
+  const long long per = (total + kScaleSplit - 1) / kScaleSplit;
+  const long long beg = sp * per, end = min(total, beg + per);
+  const float sc = scales[l];
+  double s = 0.0, z = 0.0;
+  for (long long e = beg + threadIdx.x; e < end; e += 256) {
+    const int r = (int)(e / A), p = (int)(e - (long long)r * A);
+    const size_t idx = (size_t)r * lv.P + lv.off[l] + p;
+    const float yv = MODE == LD_SCALE_ACT_EXP ? y[idx] : 0.0f;
+    s += (double)x[idx] *
+         (double)(scale_act_slope<MODE>(x[idx] * sc, yv, mul.m[l]) * dy[idx]);
+  }
+  block_sum2(s, z);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
 // --------------------------------------------------------------------- SGD --
 // torch.optim.SGD: d = g + wd*p; buf = mu*buf + d; p -= lr*buf
 __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p,
@@ -2526,6 +2602,77 @@ extern "C" int ld_scale_levels_backward(const ld_levels_t* lv, const float* dy,
   }
   return (int)hipGetLastError();
 }
+
+namespace {
+int scale_act_args(const ld_levels_t* lv, const int32_t* strides, int mode, LevelMul* mul) {
+  if (int e = check_levels(lv)) return e;
+  if (mode < LD_SCALE_ACT_EXP || mode > LD_SCALE_ACT_RELU_STRIDE) return LD_EINVAL;
+  if (mode == LD_SCALE_ACT_RELU_STRIDE && !strides) return LD_EINVAL;
+  for (int l = 0; l < LD_MAX_LEVELS; ++l) {
+    mul->m[l] = 1.0f;
+    if (mode == LD_SCALE_ACT_RELU_STRIDE && l < lv->num_levels) {
+      if (strides[l] < 1) return LD_EINVAL;
+      mul->m[l] = (float)strides[l];
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+#define LD_SCALE_ACT_MODE(mode, GO)                      \
+  do {                                                   \
+    if ((mode) == LD_SCALE_ACT_EXP) GO(LD_SCALE_ACT_EXP); \
+    else if ((mode) == LD_SCALE_ACT_RELU) GO(LD_SCALE_ACT_RELU); \
+    else GO(LD_SCALE_ACT_RELU_STRIDE);                   \
+  } while (0)
+
+extern "C" int ld_scale_act_levels_forward(const ld_levels_t* lv, const float* x,
+                                           const float* scales, const int32_t* strides,
+                                           int mode, int rows, float* y,
+                                           ld_stream_t stream) {
+  LevelMul mul;
+  if (int e = scale_act_args(lv, strides, mode, &mul)) return e;
+  if (!x || !scales || !y || rows < 1) return LD_EINVAL;
+  const Levels k = make_levels(lv);
+#define LD_GO(M)                                                                       \
+  LD_LAUNCH(scale_act_levels_kernel<M>, dim3((k.P + 255) / 256, rows), dim3(256), 0, \
+            LD_STREAM, x, k, scales, mul, y)
+  LD_SCALE_ACT_MODE(mode, LD_GO);
+#undef LD_GO
+  return (int)hipGetLastError();
+}
+
+extern "C" int ld_scale_act_levels_backward(const ld_levels_t* lv, const float* dy,
+                                            const float* x, const float* y,
+                                            const float* scales, const int32_t* strides,
+                                            int mode, int rows, float* dx, float* dscales,
+                                            int accumulate, void* workspace,
+                                            size_t workspace_bytes, ld_stream_t stream) {
+  LevelMul mul;
+  if (int e = scale_act_args(lv, strides, mode, &mul)) return e;
+  if (!dy || !x || !scales || !dx || rows < 1) return LD_EINVAL;
+  if (mode == LD_SCALE_ACT_EXP && !y) return LD_EINVAL;
+  if (dscales && (!workspace ||
+                  workspace_bytes < ld_scale_levels_backward_workspace_bytes(lv)))
+    return LD_ENOSPACE;
+  const Levels k = make_levels(lv);
+#define LD_GO(M)                                                                     \
+  LD_LAUNCH(scale_act_levels_bwd_kernel<M>, dim3((k.P + 255) / 256, rows), dim3(256), \
+            0, LD_STREAM, dy, x, y, k, scales, mul, dx)
+  LD_SCALE_ACT_MODE(mode, LD_GO);
+#undef LD_GO
+  if (dscales) {
+#define LD_GO(M)                                                                   \
+  LD_LAUNCH(scale_act_levels_bwd_partial_kernel<M>, dim3(k.num_levels * kScaleSplit), \
+            dim3(256), 0, LD_STREAM, dy, x, y, k, scales, mul, rows, (double*)workspace)
+    LD_SCALE_ACT_MODE(mode, LD_GO);
+#undef LD_GO
+    LD_LAUNCH(scale_levels_bwd_final_kernel, dim3(1), dim3(64), 0, LD_STREAM,
+              (const double*)workspace, k.num_levels, dscales, accumulate);
+  }
+  return (int)hipGetLastError();
+}
+#undef LD_SCALE_ACT_MODE
 
 extern "C" int ld_sgd_step_dev(float* params, const float* grads, float* momentum_buf,
                                size_t n, const float* hyper, ld_stream_t stream) {

@@ -325,9 +325,10 @@ class _DenseHead(BBoxTestMixin, nn.Module):
         self.unit_upstream = False
         self._init_layers()
 
-    def _build_towers(self):
+    def _build_towers(self, bias='auto'):
         """The cls / reg conv stacks (gfl_head.py:102-121 and the same loop of
-        atss_gfl_head.py, fcos_gfl_head.py and retina_gfl_head.py)."""
+        atss_gfl_head.py, fcos_gfl_head.py and retina_gfl_head.py; ``bias``:
+        anchor_free_head.py:93-127 hands its conv_bias to every layer)."""
         self.relu = nn.ReLU(inplace=True)
         self.cls_convs = nn.ModuleList()
         self.reg_convs = nn.ModuleList()
@@ -335,10 +336,12 @@ class _DenseHead(BBoxTestMixin, nn.Module):
             chn = self.in_channels if i == 0 else self.feat_channels
             self.cls_convs.append(
                 ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
+                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg,
+                           bias=bias))
             self.reg_convs.append(
                 ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg))
+                           conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg,
+                           bias=bias))
 
     def _build_scales(self, strides):
         self.scales = nn.ModuleList([Scale(1.0) for _ in strides])
@@ -599,7 +602,7 @@ class _DenseHead(BBoxTestMixin, nn.Module):
     # ---------------------------------------------------------- inference --
     def _get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg, rescale,
                     with_nms, prob, centernesses=None, points=False,
-                    strides=None, num_base=1, delta=None):
+                    strides=None, num_base=1, delta=None, dist=False):
         cfg = self.test_cfg if cfg is None else cfg
         if cfg is None:
             raise ValueError('get_bboxes needs a test_cfg')
@@ -631,7 +634,7 @@ class _DenseHead(BBoxTestMixin, nn.Module):
             voting=nms_type == 'voting_cluster_diounms',
             prob=prob, centernesses=None if centernesses is None else
             [c.detach() for c in centernesses], points=points,
-            num_base=num_base, with_nms=with_nms,
+            num_base=num_base, with_nms=with_nms, dist=dist,
             delta=delta and delta(cls_scores), **(
                 dict(anchor_scale=self.anchor_generator.anchor_scale or 8)
                 if delta else {}))
@@ -949,16 +952,126 @@ class LDATSSHead(_SideLD, ATSSGFLHead):
 INF = 1e8
 
 
-@HEADS.register_module()
-class FCOSGFLHead(_DenseHead):
-    """fcos_gfl_head.py:52-346 over anchor_free_head.py:15-130: the anchor-free
-    FCOS head with a general-distribution box branch.  Parameters
-    ``cls_convs / reg_convs / conv_cls / conv_reg / conv_centerness / scales``
-    as in the reference; forward returns (cls_scores, bbox_preds,
-    centernesses); points are (x, y) * stride + stride // 2."""
+class _FCOSFamily:
+    """What FCOSGFLHead and the plain FCOSHead share (fcos_gfl_head.py:52-346,
+    fcos_head.py:15-154 over anchor_free_head.py:15-130): the anchor-free
+    constructor, parameters ``cls_convs / reg_convs / conv_cls / conv_reg /
+    conv_centerness / scales`` as in the reference, points (x, y) * stride +
+    stride // 2 with the batched point targets, FocalLoss + centerness-weighted
+    box loss + centerness BCE.  forward returns (cls_scores, bbox_preds,
+    centernesses); the box branch has ``_reg_out`` channels."""
     _predictors = ('conv_cls', 'conv_reg', 'conv_centerness')
     _loss_keys, _loss_rows = ATSS_LOSS_KEYS, _ATSS_ROWS
     _plain_keys = ('loss_cls', 'loss_bbox', 'loss_centerness')
+    # the targets of a captured step come from its StaticTargets
+    _static_gt = False
+    # ConvModule's bias argument of the tower layers
+    _tower_bias = 'auto'
+
+    def _init_fcos_head(self, num_classes, in_channels, feat_channels,
+                        stacked_convs, strides, dcn_on_last_conv, conv_bias,
+                        regress_ranges, center_sampling, center_sample_radius,
+                        norm_on_bbox, centerness_on_reg, loss_cls, loss_bbox,
+                        loss_centerness, conv_cfg, norm_cfg, train_cfg,
+                        test_cfg):
+        """AnchorFreeHead.__init__ (anchor_free_head.py:46-91) + the FCOS
+        arguments; the caller runs ``_init_layers()``."""
+        self.num_classes = self.cls_out_channels = num_classes
+        self.in_channels, self.feat_channels = in_channels, feat_channels
+        self.stacked_convs, self.strides = stacked_convs, list(strides)
+        self.dcn_on_last_conv, self.conv_bias = dcn_on_last_conv, conv_bias
+        self.regress_ranges = regress_ranges
+        self.center_sampling = center_sampling
+        self.center_sample_radius = center_sample_radius
+        self.norm_on_bbox, self.centerness_on_reg = (norm_on_bbox,
+                                                     centerness_on_reg)
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_bbox = build_loss(loss_bbox)
+        self.loss_centerness = build_loss(loss_centerness)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.fp16_enabled = False
+        self.unit_upstream = False
+
+    def _init_layers(self):
+        """fcos_gfl_head.py:134-165, fcos_head.py:93-97."""
+        self._build_towers(self._tower_bias)
+        self.conv_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3,
+                               padding=1)
+        self.conv_reg = Conv2d(self.feat_channels, self._reg_out, 3,
+                               padding=1)
+        self.conv_centerness = Conv2d(self.feat_channels, 1, 3, padding=1)
+        self._build_scales(self.strides)
+
+    def forward(self, feats):
+        """fcos_gfl_head.py:178-224, fcos_head.py:104-154."""
+        return self._predict(*self._trunk(feats))
+
+    def _ctr_feat(self, cls_feat, reg_feat):
+        """The tower conv_centerness reads."""
+        return reg_feat
+
+    def _predict(self, cls_feat, reg_feat, levels):
+        cls3, _ = self.conv_cls.forward3(cls_feat, levels)
+        reg3, _ = self.conv_reg.forward3(reg_feat, levels)
+        ctr3, _ = self.conv_centerness.forward3(
+            self._ctr_feat(cls_feat, reg_feat), levels)
+        reg3 = self._scale(reg3, levels)
+        return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
+                Y.split_levels(ctr3, levels))
+
+    # ---------------------------------------------------------------- loss --
+    def _check_loss_cfg(self):
+        self._check_focal_cfg('FCOS', centerness=True)
+
+    def _fcos_hp(self):
+        return dict(lw_ctr=self.loss_centerness.loss_weight,
+                    focal_alpha=self.loss_cls.alpha,
+                    flags=L.LD_LOSS_ATSS | L.LD_LOSS_FCOS)
+
+    def _hp(self, **over):
+        kw = self._fcos_hp()
+        kw.update(over)
+        return super()._hp(**kw)
+
+    def get_targets_batched(self, featmap_sizes, gt_bboxes, gt_labels, device,
+                            img_metas=None):
+        """get_points + get_targets (ld_fcos_head.py:261-414, fcos_head.py:
+        468-588) for the whole batch in one launch."""
+        return LB.fcos_targets(featmap_sizes, self.strides, gt_bboxes,
+                               gt_labels, self.num_classes,
+                               self.regress_ranges, self.center_sampling,
+                               self.center_sample_radius, device,
+                               img_metas=img_metas)
+
+    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
+        sizes = self._level_sizes(cls_scores, len(self.strides))
+        return self.get_targets_batched(
+            sizes, gt_bboxes, gt_labels, cls_scores[0].device,
+            img_metas=img_metas if self._static_gt else None)
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
+             img_metas, gt_bboxes_ignore=None):
+        """fcos_gfl_head.py:276-345, fcos_head.py:157-254: loss_cls, loss_bbox,
+        loss_centerness."""
+        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
+                          img_metas, extra=centernesses)
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
+                   cfg=None, rescale=False, with_nms=True):
+        """fcos_gfl_head.py:347-546, fcos_head.py:257-454: as
+        ATSSGFLHead.get_bboxes, decoded about the FCOS points (x, y) * stride +
+        stride // 2."""
+        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
+                                rescale, with_nms, prob=False,
+                                centernesses=centernesses, points=True,
+                                strides=self.strides)
+
+
+@HEADS.register_module()
+class FCOSGFLHead(_FCOSFamily, _DenseHead):
+    """fcos_gfl_head.py:52-346 over anchor_free_head.py:15-130: the anchor-free
+    FCOS head with a general-distribution box branch."""
 
     def __init__(self, num_classes, in_channels, feat_channels=256,
                  stacked_convs=4, strides=(4, 8, 16, 32, 64),
@@ -980,87 +1093,17 @@ class FCOSGFLHead(_DenseHead):
             raise NotImplementedError('dcn_on_last_conv')
         if norm_on_bbox:
             raise NotImplementedError('norm_on_bbox=True')
-        self.num_classes = self.cls_out_channels = num_classes
-        self.in_channels, self.feat_channels = in_channels, feat_channels
-        self.stacked_convs, self.strides = stacked_convs, list(strides)
-        self.dcn_on_last_conv, self.conv_bias = dcn_on_last_conv, conv_bias
-        self.regress_ranges = regress_ranges
-        self.center_sampling = center_sampling
-        self.center_sample_radius = center_sample_radius
-        self.norm_on_bbox, self.centerness_on_reg = (norm_on_bbox,
-                                                     centerness_on_reg)
         self.reg_max = reg_max
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_bbox = build_loss(loss_bbox)
-        self.loss_centerness = build_loss(loss_centerness)
-        self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
-        self.fp16_enabled = False
-        self.unit_upstream = False
+        self._init_fcos_head(num_classes, in_channels, feat_channels,
+                             stacked_convs, strides, dcn_on_last_conv,
+                             conv_bias, regress_ranges, center_sampling,
+                             center_sample_radius, norm_on_bbox,
+                             centerness_on_reg, loss_cls, loss_bbox,
+                             loss_centerness, conv_cfg, norm_cfg, train_cfg,
+                             test_cfg)
         self._init_layers()
         # after the layers, like the reference (state_dict key order)
         self.integral = Integral(reg_max)
-
-    def _init_layers(self):
-        """fcos_gfl_head.py:134-165."""
-        self._build_towers()
-        self.conv_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3,
-                               padding=1)
-        self.conv_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3,
-                               padding=1)
-        self.conv_centerness = Conv2d(self.feat_channels, 1, 3, padding=1)
-        self._build_scales(self.strides)
-
-    def forward(self, feats):
-        """fcos_gfl_head.py:178-224."""
-        return self._predict(*self._trunk(feats))
-
-    def _predict(self, cls_feat, reg_feat, levels):
-        cls3, _ = self.conv_cls.forward3(cls_feat, levels)
-        reg3, _ = self.conv_reg.forward3(reg_feat, levels)
-        ctr3, _ = self.conv_centerness.forward3(reg_feat, levels)
-        reg3 = self._scale(reg3, levels)
-        return (Y.split_levels(cls3, levels), Y.split_levels(reg3, levels),
-                Y.split_levels(ctr3, levels))
-
-    # ---------------------------------------------------------------- loss --
-    def _check_loss_cfg(self):
-        self._check_focal_cfg('FCOS', centerness=True)
-
-    def _hp(self, **over):
-        kw = dict(lw_ctr=self.loss_centerness.loss_weight,
-                  focal_alpha=self.loss_cls.alpha,
-                  flags=L.LD_LOSS_ATSS | L.LD_LOSS_FCOS)
-        kw.update(over)
-        return super()._hp(**kw)
-
-    def get_targets_batched(self, featmap_sizes, gt_bboxes, gt_labels, device):
-        """get_points + get_targets (ld_fcos_head.py:261-414) for the whole
-        batch in one launch."""
-        return LB.fcos_targets(featmap_sizes, self.strides, gt_bboxes,
-                               gt_labels, self.num_classes,
-                               self.regress_ranges, self.center_sampling,
-                               self.center_sample_radius, device)
-
-    def _targets(self, hp, cls_scores, img_metas, gt_bboxes, gt_labels):
-        sizes = self._level_sizes(cls_scores, len(self.strides))
-        return self.get_targets_batched(sizes, gt_bboxes, gt_labels,
-                                        cls_scores[0].device)
-
-    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels,
-             img_metas, gt_bboxes_ignore=None):
-        """fcos_gfl_head.py:276-345: loss_cls, loss_bbox, loss_centerness."""
-        return self._loss((cls_scores, bbox_preds), gt_bboxes, gt_labels,
-                          img_metas, extra=centernesses)
-
-    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas,
-                   cfg=None, rescale=False, with_nms=True):
-        """fcos_gfl_head.py:347-546: as ATSSGFLHead.get_bboxes, decoded about
-        the FCOS points (x, y) * stride + stride // 2."""
-        return self._get_bboxes(cls_scores, bbox_preds, img_metas, cfg,
-                                rescale, with_nms, prob=False,
-                                centernesses=centernesses, points=True,
-                                strides=self.strides)
 
 
 @HEADS.register_module()

@@ -2676,6 +2676,61 @@ def scale_levels(x3, scales, levels):
     return ScaleLevelsFn.apply(x3, scales, levels)
 
 
+class ScaleActLevelsFn(torch.autograd.Function):
+    """y[:, :, level l] = act(x * scales[l]): the Scale and the activation of
+    FCOSHead's box branch (fcos_head.py:145-153) in one launch for all levels.
+    ``mode``: 'exp' | 'relu' | 'relu_stride' (relu, times ``strides[l]``: the
+    eval-mode output of norm_on_bbox)."""
+
+    @staticmethod
+    def forward(ctx, x3, scales, levels, mode, strides):
+        _dev_f32(x3, 'scale_act_levels input')
+        lib = L.get_lib()
+        N, c, P = x3.shape
+        lv = levels_desc(levels)
+        if len(strides) != len(levels):
+            raise L.LdError(f'scale_act_levels: {len(strides)} strides for '
+                            f'{len(levels)} levels')
+        st = (C.c_int32 * len(strides))(*[int(s) for s in strides])
+        y = torch.empty_like(x3)
+        L.check(lib.ld_scale_act_levels_forward(
+            C.byref(lv), L.ptr(x3), L.ptr(scales), st,
+            L.LD_SCALE_ACT_MODES[mode], N * c, L.ptr(y),
+            L.stream_ptr(x3.device)), 'ld_scale_act_levels_forward')
+        ctx.save_for_backward(x3, scales, y)
+        ctx.levels, ctx.mode, ctx.strides = levels, mode, st
+        ctx.params = (scales, )
+        _note_use(scales)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = L.get_lib()
+        x3, scales, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, c, P = x3.shape
+        lv = levels_desc(ctx.levels)
+        dx = torch.empty_like(x3)
+        (ds, ), direct = _grad_outs(ctx.params, ctx.needs_input_grad[1:2],
+                                    lambda p: torch.empty_like(scales))
+        need = lib.ld_scale_levels_backward_workspace_bytes(C.byref(lv))
+        ws = workspace(x3.device, need, 'scale_bwd')
+        L.check(lib.ld_scale_act_levels_backward(
+            C.byref(lv), L.ptr(dy), L.ptr(x3), L.ptr(y), L.ptr(scales),
+            ctx.strides, L.LD_SCALE_ACT_MODES[ctx.mode], N * c, L.ptr(dx),
+            L.ptr(ds), 1 if direct else 0, L.ptr(ws), ws.numel(),
+            L.stream_ptr(x3.device)), 'ld_scale_act_levels_backward')
+        return (dx, _grad_done(ctx.params, (ds, ), direct)[0], None, None,
+                None)
+
+
+def scale_act_levels(x3, scales, levels, mode, strides):
+    if mode not in L.LD_SCALE_ACT_MODES:
+        raise ValueError(f'scale_act_levels: mode {mode!r}, one of '
+                         f'{sorted(L.LD_SCALE_ACT_MODES)}')
+    return ScaleActLevelsFn.apply(x3, scales, levels, mode, tuple(strides))
+
+
 def deform_im2col(x3, off3, h, w, k, stride, pad, dilation):
     """(N, Cin, H*W) + offsets (N, 2*k*k, Hout*Wout) -> column tensor
     (N, Cin*k*k, Hout*Wout), no autograd (ld_deform_im2col; the differentiable

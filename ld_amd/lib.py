@@ -64,6 +64,8 @@ LD_LOSS_ATSS = 4
 LD_LOSS_FCOS = 8
 LD_LOSS_RETINA = 16
 LD_LOSS_DELTA = 32
+LD_LOSS_DIST = 64
+LD_LOSS_DIST_NORM = 128
 LD_DELTA_TERMS = {'decoded': 0, 'l1': 1, 'smooth_l1': 2}
 LD_LOSS_PART_CLS = 4
 LD_LOSS_BBOX_SHIFT = 8
@@ -73,6 +75,8 @@ LD_INFER_VOTING = 1
 LD_INFER_PROB = 2
 LD_INFER_POINTS = 4
 LD_INFER_DELTA = 16
+LD_INFER_DIST = 32
+LD_SCALE_ACT_MODES = {'exp': 0, 'relu': 1, 'relu_stride': 2}
 LD_AUG_RESCALE = 8
 LD_MAX_AUG_VIEWS = 16
 LD_FLIP = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
@@ -302,7 +306,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -386,6 +390,10 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _sz, _vp]),
     'ld_loss_delta_pos': (C.c_int, [_G, _H, _D, _vp, _M, _M, _vp, _vp, _vp,
                                     _vp, _vp, _M, _vp, _sz, _vp]),
+    'ld_loss_dist_prepass': (C.c_int, [_G, _H, _vp, _vp, _vp, _vp, _vp, _vp,
+                                       _vp, _sz, _vp]),
+    'ld_loss_dist_pos': (C.c_int, [_G, _H, _M, _M, _vp, _vp, _vp, _vp, _vp, _M,
+                                   _vp, _sz, _vp]),
     'ld_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
     'ld_smooth_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
                                     _vp]),
@@ -628,6 +636,13 @@ SIGNATURES = {
     'ld_scale_levels_backward_workspace_bytes': (_sz, [_LV]),
     'ld_scale_levels_backward': (C.c_int, [_LV, _vp, _vp, _vp, _i32, _vp, _vp,
                                            _i32, _vp, _sz, _vp]),
+    'ld_scale_act_levels_forward': (C.c_int, [_LV, _vp, _vp,
+                                              C.POINTER(C.c_int32), _i32, _i32,
+                                              _vp, _vp]),
+    'ld_scale_act_levels_backward': (C.c_int, [_LV, _vp, _vp, _vp, _vp,
+                                               C.POINTER(C.c_int32), _i32,
+                                               _i32, _vp, _vp, _i32, _vp, _sz,
+                                               _vp]),
     'ld_sgd_step': (C.c_int, [_vp, _vp, _vp, _sz, _f32, _f32, _f32, _f32,
                               _vp]),
     'ld_sgd_step_dev': (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),

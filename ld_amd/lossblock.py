@@ -295,25 +295,33 @@ def atss_targets(featmap_sizes, strides, img_metas, gt_bboxes, gt_labels, hp,
 
 def fcos_targets(featmap_sizes, strides, gt_bboxes, gt_labels, num_classes,
                  regress_ranges, center_sampling, center_sample_radius,
-                 device):
+                 device, img_metas=None):
     """Dense FCOS point targets for a batch (ld_fcos_targets): the same dict as
     :func:`atss_targets` (bbox_targets = (l, t, r, b) distances, vlr = the
-    head's "remain" points)."""
+    head's "remain" points).  ``img_metas`` (optional): a captured step's
+    ``StaticTargets`` travel in them, as for :func:`atss_targets`."""
     lib = L.get_lib()
     N = len(gt_bboxes)
     geom = L.make_geom(featmap_sizes, strides, N, 8)
     A, nl = geom.num_anchors, geom.num_levels
-    num_gt = [int(b.shape[0]) for b in gt_bboxes]
-    max_gt = max(num_gt) if num_gt else 0
-    gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
-                      device=device)
-    gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64, device=device)
-    for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
-        if num_gt[i]:
-            L.require_device(b, torch.float32, 'gt_bboxes')
-            gtb[i, :num_gt[i]] = b
-            gtl[i, :num_gt[i]] = l
-    ng = _small_int_tensor(tuple(num_gt), device)
+    st = _static_targets(img_metas)
+    if st is not None:
+        # captured step: padded boxes + device-side counts at fixed addresses
+        gtb, gtl, ng, max_gt = st.gtb, st.gtl, st.ng, st.max_gt
+        num_gt = list(st.num_gt)
+    else:
+        num_gt = [int(b.shape[0]) for b in gt_bboxes]
+        max_gt = max(num_gt) if num_gt else 0
+        gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
+                          device=device)
+        gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64,
+                          device=device)
+        for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
+            if num_gt[i]:
+                L.require_device(b, torch.float32, 'gt_bboxes')
+                gtb[i, :num_gt[i]] = b
+                gtl[i, :num_gt[i]] = l
+        ng = _small_int_tensor(tuple(num_gt), device)
     out = dict(
         labels=torch.empty((N, A), dtype=torch.int64, device=device),
         label_weights=torch.empty((N, A), dtype=torch.float32, device=device),
@@ -548,6 +556,10 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     DeltaXYWH maps and ``targets['delta']`` = (ld_delta_t, explicit anchors or
     None); the block runs its delta prepass / positives launches and the class
     part only, the teacher arguments are not read.
+    hp.flags & LD_LOSS_DIST (FCOSHead): ``reg`` are 4-channel maps of activated
+    distances (layers.scale_act_levels) and ``targets`` those of
+    :func:`fcos_targets`; the block runs its dist prepass / positives launches,
+    the class part and the centerness term.
     Returns (losses (8, L) tensor, grads dict of lists, norm tensor).
     """
     lib = L.get_lib()
@@ -558,6 +570,10 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
         if any(r.shape[1] != 4 for r in reg):
             raise L.LdError('LD_LOSS_DELTA: the reg maps carry 4 channels per '
                             'anchor')
+    dist = bool(hp.flags & L.LD_LOSS_DIST)
+    if dist and any(r.shape[1] != 4 for r in reg):
+        raise L.LdError('LD_LOSS_DIST: the reg maps carry 4 distances per '
+                        'point')
     device = cls[0].device
     N, A = geom.num_imgs, geom.num_anchors
     m_cls, m_reg = L.make_maps(cls), L.make_maps(reg)
@@ -593,6 +609,12 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
             L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
             L.ptr(targets['counts']), L.ptr(wt), L.ptr(score), L.ptr(norm),
             L.ptr(ws), ws.numel(), st), 'ld_loss_delta_prepass')
+    elif dist:
+        L.check(lib.ld_loss_dist_prepass(
+            C.byref(geom), C.byref(hp), L.ptr(targets['labels']),
+            L.ptr(targets['bbox_targets']), L.ptr(targets['counts']),
+            L.ptr(wt), L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
+            'ld_loss_dist_prepass')
     else:
         L.check(lib.ld_loss_prepass_ex(
             C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
@@ -646,6 +668,14 @@ def _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg, m_x,
             L.ptr(targets['bbox_targets']), L.ptr(score), L.ptr(norm),
             L.ptr(up), C.byref(mg_reg), L.ptr(ws), ws.numel(), st),
             'ld_loss_delta_pos')
+        parts = L.LD_LOSS_PART_CLS
+    elif hp.flags & L.LD_LOSS_DIST:
+        # the positives' box term on the 4 distances, then the class part
+        L.check(lib.ld_loss_dist_pos(
+            C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
+            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
+            L.ptr(score), L.ptr(norm), L.ptr(up), C.byref(mg_reg), L.ptr(ws),
+            ws.numel(), st), 'ld_loss_dist_pos')
         parts = L.LD_LOSS_PART_CLS
     L.check(lib.ld_loss_main_parts(
         C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
@@ -768,7 +798,7 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
                nms_pre=1000, score_thr=0.05, iou_thr=0.6, max_per_img=100,
                num_classes=None, reg_max=16, voting=False, prob=False,
                centernesses=None, points=False, num_base=1, with_nms=True,
-               delta=None, anchor_scale=8):
+               delta=None, anchor_scale=8, dist=False):
     """GFLHead.get_bboxes on the device (ld_get_bboxes_ex; ``voting`` = the
     score-voting Cluster-DIoU-NMS variant, ``prob`` = the class maps hold
     probabilities: GFocalHead.get_bboxes; ``centernesses`` / ``points``: the
@@ -778,13 +808,15 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
     ``delta`` = (ld_delta_t, explicit anchors (cells * num_base, 4) or None):
     the ATSSHead / RetinaHead variant (LD_INFER_DELTA), ``bbox_preds`` hold
     num_base * 4 DeltaXYWH deltas; ``anchor_scale``: the implicit anchor's.
+    ``dist``: the FCOSHead variant (LD_INFER_DIST, with ``points``),
+    ``bbox_preds`` hold 4 distances in pixels.
     -> list of (dets (k, 5), labels (k,)) device tensors, one pair per image."""
     lib = L.get_lib()
     dev = cls_scores[0].device
     N = cls_scores[0].shape[0]
     B_ = int(num_base)
     C_ = int(num_classes or cls_scores[0].shape[1] // B_)
-    R_ = 4 if delta is not None else 4 * (reg_max + 1)
+    R_ = 4 if delta is not None or dist else 4 * (reg_max + 1)
     if cls_scores[0].shape[1] != B_ * C_ or \
             bbox_preds[0].shape[1] != B_ * R_:
         raise L.LdError('get_bboxes: channel counts do not match num_base x '
@@ -813,7 +845,8 @@ def get_bboxes(cls_scores, bbox_preds, strides, img_shapes, scale_factors=None,
     ws = workspace(dev, need, 'infer')
     pflags = (L.LD_INFER_PROB if prob else 0) | \
         (L.LD_INFER_POINTS if points else 0) | \
-        (L.LD_INFER_DELTA if delta is not None else 0)
+        (L.LD_INFER_DELTA if delta is not None else 0) | \
+        (L.LD_INFER_DIST if dist else 0)
     flags = pflags | (L.LD_INFER_VOTING if voting else 0)
     km = C.byref(L.make_maps(centernesses)) if centernesses is not None \
         else None

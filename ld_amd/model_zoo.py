@@ -350,6 +350,50 @@ def fcos_gfl_detector(depth=101):
                 test_cfg=copy.deepcopy(_TEST_CFG))
 
 
+def fcos_detector(depth=50, tricks=False):
+    """Plain FCOS, the baseline the FCOS-GFL / LD-FCOS rows are measured
+    against.  ``tricks=False``: configs/fcos/fcos_r50_caffe_fpn_gn-head_1x_
+    coco.py:5-62 (``depth`` 101 = fcos_r101_caffe_fpn_gn-head_1x_coco.py);
+    ``tricks=True``: fcos_center-normbbox-centeronreg-giou_r50_caffe_fpn_
+    gn-head_1x_coco.py:3-14 on top of it."""
+    head = dict(
+        type='FCOSHead', num_classes=80, in_channels=256, stacked_convs=4,
+        feat_channels=256, strides=[8, 16, 32, 64, 128],
+        loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0,
+                      alpha=0.25, loss_weight=1.0),
+        loss_bbox=dict(type='IoULoss', loss_weight=1.0),
+        loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True,
+                             loss_weight=1.0))
+    test_cfg = copy.deepcopy(_TEST_CFG)
+    test_cfg['nms']['iou_threshold'] = 0.5
+    if tricks:
+        head.update(norm_on_bbox=True, centerness_on_reg=True,
+                    dcn_on_last_conv=False, center_sampling=True,
+                    conv_bias=True,
+                    loss_bbox=dict(type='GIoULoss', loss_weight=1.0))
+        test_cfg['nms']['iou_threshold'] = 0.6
+    return dict(type='FCOS', pretrained=None, backbone=_fcos_backbone(depth),
+                neck=_fcos_neck(depth), bbox_head=head,
+                train_cfg=copy.deepcopy(_FCOS_TRAIN_CFG), test_cfg=test_cfg)
+
+
+def fcos_schedule(tricks=False):
+    """The optimizer keys of the two plain FCOS configs over
+    configs/_base_/schedules/schedule_1x.py: biases learn at twice the rate
+    without weight decay; the base file clips gradients at norm 35 and warms up
+    at a constant third of the rate, the ``tricks`` file does not clip and
+    warms up linearly."""
+    return dict(
+        optimizer=dict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001,
+                       paramwise_cfg=dict(bias_lr_mult=2.,
+                                          bias_decay_mult=0.)),
+        optimizer_config=dict(grad_clip=None) if tricks else
+        dict(grad_clip=dict(max_norm=35, norm_type=2)),
+        lr_config=dict(policy='step',
+                       warmup='linear' if tricks else 'constant',
+                       warmup_iters=500, warmup_ratio=1.0 / 3, step=[8, 11]))
+
+
 def ld_fcos_detector(student_depth=50, teacher_depth=101):
     """configs/ld/ld_r50_fcos_r101_1x.py: LDFCOSHead student <- FCOS-GFL
     teacher (output_feature=False)."""

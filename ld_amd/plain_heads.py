@@ -1,7 +1,8 @@
-"""The plain ATSS and RetinaNet heads with mmdet's constructor arguments,
-state_dict keys and method signatures (reference:
+"""The plain ATSS, RetinaNet and FCOS heads with mmdet's constructor
+arguments, state_dict keys and method signatures (reference:
 mmdet/models/dense_heads/atss_head.py:15-508, retina_head.py:8-114,
-anchor_head.py:14-727): the baselines the general-distribution and LD heads
+anchor_head.py:14-727, fcos_head.py:15-608 over anchor_free_head.py): the
+baselines the general-distribution and LD heads
 of ``heads.py`` are measured against.
 
 They are ``heads._DenseHead`` heads -- towers, packed forward trunk, the ONE
@@ -9,9 +10,15 @@ loss-block call, loss dict, forward_train, get_bboxes, aug_test -- and share
 ``_ATSSFamily`` / ``_RetinaFamily`` with ATSSGFLHead / RetinaGFLHead; what
 differs is the box branch, stated once in ``_DeltaBox``: 4 DeltaXYWH deltas per
 anchor, taken by the fused loss block with LD_LOSS_DELTA and by get_bboxes with
-LD_INFER_DELTA (csrc/loss.hip, csrc/infer.hip)."""
+LD_INFER_DELTA (csrc/loss.hip, csrc/infer.hip).  FCOSHead shares
+``_FCOSFamily`` with FCOSGFLHead; its box branch is ``_DistBox``: 4 activated
+distances per point, LD_LOSS_DIST / LD_INFER_DIST."""
+import torch
+
+from . import layers as Y
 from . import lib as L
-from .heads import _BOX_LOSSES, _ATSSFamily, _DenseHead, _RetinaFamily
+from .heads import (INF, _BOX_LOSSES, _ATSSFamily, _DenseHead, _FCOSFamily,
+                    _RetinaFamily)
 from .losses import bbox_loss_mode
 from .registry import HEADS, build_loss
 
@@ -167,3 +174,81 @@ class RetinaHead(_DeltaBox, _RetinaFamily, _DenseHead):
                   flags=L.LD_LOSS_RETINA | L.LD_LOSS_DELTA)
         kw.update(over)
         return super()._hp(**kw)
+
+
+class _DistBox:
+    """The box branch of the plain FCOS head: 4 distances (l, t, r, b) per
+    point, ``exp(scale_l * x)`` or, with ``norm_on_bbox``, ``relu(scale_l *
+    x)`` in stride units while training and times the stride in eval mode
+    (fcos_head.py:145-153) -- Scale and activation in one launch
+    (layers.scale_act_levels), so ``forward`` returns the activated maps.  The
+    fused loss block takes them with LD_LOSS_DIST, get_bboxes with
+    LD_INFER_DIST.  No Integral, no teacher terms."""
+    _reg_out = 4
+
+    def _scale(self, reg3, levels):
+        mode = 'exp' if not self.norm_on_bbox else \
+            'relu' if self.training else 'relu_stride'
+        return Y.scale_act_levels(
+            reg3, torch.stack([s.scale for s in self.scales]), levels, mode,
+            self.strides)
+
+    def _get_bboxes(self, *args, **kwargs):
+        return super()._get_bboxes(*args, dist=True, **kwargs)
+
+
+@HEADS.register_module()
+class FCOSHead(_DistBox, _FCOSFamily, _DenseHead):
+    """fcos_head.py:15-154 over anchor_free_head.py:15-130: the plain FCOS
+    head.  Loss (fcos_head.py:157-254): FocalLoss / max(num_pos, 1), the box
+    loss on distance2bbox(point, pred) against distance2bbox(point, target)
+    weighted by the centerness target / max(sum of the targets, 1e-6),
+    centerness BCE / max(num_pos, 1).  ``conv_centerness`` reads the class
+    tower unless ``centerness_on_reg``."""
+    _static_gt = True
+
+    def __init__(self, num_classes, in_channels, feat_channels=256,
+                 stacked_convs=4, strides=(4, 8, 16, 32, 64),
+                 dcn_on_last_conv=False, conv_bias='auto',
+                 regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512),
+                                 (512, INF)),
+                 center_sampling=False, center_sample_radius=1.5,
+                 norm_on_bbox=False, centerness_on_reg=False,
+                 loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0,
+                               alpha=0.25, loss_weight=1.0),
+                 loss_bbox=dict(type='IoULoss', loss_weight=1.0),
+                 loss_centerness=dict(type='CrossEntropyLoss',
+                                      use_sigmoid=True, loss_weight=1.0),
+                 conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 train_cfg=None, test_cfg=None):
+        super().__init__()
+        if dcn_on_last_conv:
+            raise NotImplementedError('FCOSHead: dcn_on_last_conv')
+        if loss_cls.get('type') != 'FocalLoss' or \
+                loss_cls.get('gamma', 2.0) != 2.0:
+            raise NotImplementedError(
+                f'FCOSHead: loss_cls {loss_cls.get("type")} (gamma '
+                f'{loss_cls.get("gamma", 2.0)}); the fused loss block '
+                'implements FocalLoss with gamma 2')
+        self._init_fcos_head(num_classes, in_channels, feat_channels,
+                             stacked_convs, strides, dcn_on_last_conv,
+                             conv_bias, regress_ranges, center_sampling,
+                             center_sample_radius, norm_on_bbox,
+                             centerness_on_reg, loss_cls, loss_bbox,
+                             loss_centerness, conv_cfg, norm_cfg, train_cfg,
+                             test_cfg)
+        self._init_layers()
+
+    @property
+    def _tower_bias(self):
+        return self.conv_bias
+
+    def _ctr_feat(self, cls_feat, reg_feat):
+        return reg_feat if self.centerness_on_reg else cls_feat
+
+    def _fcos_hp(self):
+        kw = super()._fcos_hp()
+        kw['flags'] |= L.LD_LOSS_DIST | \
+            (L.LD_LOSS_DIST_NORM if self.norm_on_bbox else 0)
+        return kw

@@ -925,6 +925,98 @@ def plain_infer_inputs(kind, device='cpu'):
     return hi, metas
 
 
+# ---------------------------------------------------------------------------
+# plain FCOSHead (tests/golden/fcos_head.npz, tools/gen_golden_fcos_head.py):
+# the PLAIN_* geometry, cases and seeds with the default regress_ranges
+# ---------------------------------------------------------------------------
+FCOS_STRIDES = (8, 16, 32, 64, 128)
+# the per-level Scale parameters the loss cases run with (the reference starts
+# them at 1.0; distinct values make the per-level scale gradient tell levels
+# apart)
+FCOS_SCALES = (1.0, 0.75, 1.25, 0.5, 1.5)
+# head variants: constructor arguments on top of the reference's defaults
+FCOS_VARIANTS = OrderedDict(
+    plain={},
+    center=dict(center_sampling=True),
+    tricks=dict(center_sampling=True, norm_on_bbox=True,
+                centerness_on_reg=True,
+                loss_bbox=dict(type='GIoULoss', loss_weight=1.0)),
+    # not a config of the reference: relu distances under the default IoULoss,
+    # where a zero-area box costs -log(eps)
+    norm_iou=dict(norm_on_bbox=True))
+# ReLU variants, case 'multi': two positives of the 64 px box of image 0 (with
+# and without center_sampling), (image, level, y, x): ``all`` has four negative
+# pre-activations -- a zero-area box with a zero gradient --, ``one`` exactly one
+# (channel FCOS_NEG_CH)
+FCOS_NEG = dict(all=(0, 0, 5, 5), one=(0, 0, 6, 6))
+FCOS_NEG_CH = 2
+
+
+def fcos_head_inputs(seed, num_imgs=2, device='cpu', relu=False):
+    """Outputs of the plain FCOS head's convs on the PLAIN_PAD pyramid: cls
+    (N, 4, h, w) and ctr as for plain_head_inputs('atss'), ``raw`` (N, 4, h, w)
+    ~ 0.5 * randn -- the box maps BEFORE Scale and exp / relu, so exp stays in
+    range.  ``relu`` (the norm_on_bbox variants): every pre-activation is moved
+    0.125 away from zero and the FCOS_NEG cells get their negative ones.  The
+    reference adds stride-unit distances to PIXEL points (fcos_head.py:233-236):
+    a distance of 1e-3 next to a coordinate of 80 keeps 7 bits in fp32, and
+    seed 71 draws such a positive (0.0006 on level 2), whose IoU gradient the
+    reference's own fp32 then gets 0.4 % wrong.  The kink itself is the business
+    of FCOS_NEG and of the activation kernels' own test."""
+    gen = _gen(seed)
+    out = dict(cls=[], raw=[])
+    for (h, w) in level_shapes(PLAIN_PAD):
+        out['cls'].append(
+            _normal((num_imgs, PLAIN_CLASSES, h, w), gen) * 1.2 - 3.0)
+        out['raw'].append(_normal((num_imgs, 4, h, w), gen) * 0.5)
+    if relu:
+        out['raw'] = [r + 0.125 * torch.sign(r) for r in out['raw']]
+        n, l, y, x = FCOS_NEG['all']
+        out['raw'][l][n, :, y, x] = -out['raw'][l][n, :, y, x].abs() - 0.125
+        n, l, y, x = FCOS_NEG['one']
+        out['raw'][l][n, :, y, x] = out['raw'][l][n, :, y, x].abs() + 0.125
+        out['raw'][l][n, FCOS_NEG_CH, y, x] *= -1.0
+    out['ctr'] = synthetic_centerness(num_imgs, level_shapes(PLAIN_PAD),
+                                      seed=seed)
+    return {k: [t.to(device) for t in v] for k, v in out.items()}
+
+
+def fcos_activate(raw, scales=FCOS_SCALES, norm_on_bbox=False, training=True):
+    """fcos_head.py:145-153 on per-level raw maps with torch ops (any dtype,
+    differentiable): what the head's forward returns for them."""
+    out = []
+    for r, s, stride in zip(raw, scales, FCOS_STRIDES):
+        u = r * s
+        if not norm_on_bbox:
+            out.append(u.exp())
+        else:
+            u = torch.relu(u)
+            out.append(u if training else u * stride)
+    return out
+
+
+def fcos_infer_inputs(device='cpu'):
+    """get_bboxes inputs of the plain FCOS head: lifted class logits and the
+    metas of plain_infer_inputs, ``reg`` = distances in pixels (exp of the raw
+    maps times the stride, what an eval-mode forward returns)."""
+    cfg = PLAIN_INFER
+    hi = fcos_head_inputs(cfg['seed'], len(cfg['img_shapes']), device)
+    hi['cls'] = [c * 1.25 + 1.0 for c in hi['cls']]
+    hi['reg'] = [r.exp() * s for r, s in zip(hi.pop('raw'), FCOS_STRIDES)]
+    metas = [dict(img_shape=s, pad_shape=PLAIN_PAD + (3, ), ori_shape=s,
+                  scale_factor=np.array(f, dtype=np.float32), flip=False)
+             for s, f in zip(cfg['img_shapes'], cfg['scale_factors'])]
+    return hi, metas
+
+
+def fcos_feats(seed=5, num_imgs=2, device='cpu'):
+    """Neck outputs (N, PLAIN_FEAT, h, w) for the forward tests of the small
+    head."""
+    gen = _gen(seed)
+    return [_normal((num_imgs, PLAIN_FEAT, h, w), gen).to(device)
+            for (h, w) in level_shapes(PLAIN_PAD)]
+
+
 DELTA_ROWS = 257  # two 128-thread blocks and one row
 # hand-written coder rows: (anchor, gt box, deltas to decode)
 DELTA_HAND = [

@@ -1150,7 +1150,7 @@ class GraphedStep:
         head = getattr(trainer.model, 'bbox_head', None)
         self.dynamic_gt = type(head).__name__ in (
             'GFLHead', 'LDHead', 'GFocalHead', 'LDv2Head', 'ATSSGFLHead',
-            'LDATSSHead', 'ATSSHead')
+            'LDATSSHead', 'ATSSHead', 'FCOSHead')
         metas = [dict(m) for m in data['img_metas']]
         if self.dynamic_gt:
             metas[0]['ld_static_targets'] = self.static
