@@ -139,7 +139,7 @@ typedef struct {
  * the reg maps carry the 4 DeltaXYWH deltas of an anchor instead of 68
  * distribution logits.  Combined with LD_LOSS_ATSS or LD_LOSS_RETINA (which keep
  * their class, centerness and normaliser rules); the block is then run as
- * ld_loss_delta_prepass -> ld_loss_delta_pos -> ld_loss_main_parts(
+ * ld_loss_plain_prepass -> ld_loss_plain_pos -> ld_loss_main_parts(
  * LD_LOSS_PART_CLS) [-> ld_loss_centerness] -> ld_loss_finalize: no REG / IM
  * launch, no teacher maps, the DFL, LD, VLR-LD, KD and IM rows of the table are
  * zero (set lw_kd = 0).  The coder travels beside hp in an ld_delta_t. */
@@ -149,7 +149,7 @@ typedef struct {
  * targets of ld_fcos_targets), never with LD_LOSS_DELTA, LD_LOSS_RETINA or
  * LD_LOSS_PROB_CLS.  The reg maps carry 4 ACTIVATED distances per point
  * (ld_scale_act_levels_forward: exp or relu of the scaled conv output).  The
- * block runs as ld_loss_dist_prepass -> ld_loss_dist_pos -> ld_loss_main_parts(
+ * block runs as ld_loss_plain_prepass -> ld_loss_plain_pos -> ld_loss_main_parts(
  * LD_LOSS_PART_CLS) -> ld_loss_centerness -> ld_loss_finalize; the DFL, LD,
  * VLR-LD, KD and IM rows are zero.  loss_cls and loss_centerness are divided by
  * max(num_pos, 1), loss_bbox by max(sum of the centerness targets, 1e-6).
@@ -376,57 +376,47 @@ int ld_loss_main_parts(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                        void* workspace, size_t workspace_bytes, int parts,
                        ld_stream_t stream);
 
-/* The two launches an LD_LOSS_DELTA block has of its own (hp->flags must carry
- * LD_LOSS_DELTA and exactly one of LD_LOSS_ATSS / LD_LOSS_RETINA).
- * reg / grad_reg: (N, 4, H_l, W_l) maps (LD_LOSS_RETINA: the (N * B, 4, ...)
- * pseudo-image views).  anchors: the explicit (num_anchors * num_base, 4) list,
- * row (cell * num_base + b), when delta->num_base > 0 (pseudo-image n uses base
- * anchor n % num_base); NULL for the implicit square anchor.  bbox_targets hold
- * the matched GT boxes in pixels, as the target launches write them.
+/* The two launches a plain block (LD_LOSS_DELTA or LD_LOSS_DIST, never both)
+ * has of its own.  `delta` selects the form: non-NULL exactly with
+ * LD_LOSS_DELTA, NULL exactly with LD_LOSS_DIST; any other pairing, and any flag
+ * combination but the ones those two flags name, is LD_EINVAL.
+ * reg / grad_reg: (N, 4, H_l, W_l) maps.  Same workspace as the other parts.
  *
- * prepass: score = the ATSS centerness target of the positives from the anchor
- * centre and the encoded-then-decoded GT (atss_head.py:298-313; zero with
- * LD_LOSS_RETINA), weight_targets = 0, norm as ld_loss_prepass leaves it.
- * pos: the box term, forward and gradient through the decode -- the gradient
- * of a clamped dw / dh is zero -- written dense into grad_reg (zeros away from
- * the positives), and the class-softmax statistics ld_loss_main_parts(CLS)
- * reads.  Same workspace as the other parts. */
-int ld_loss_delta_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+ * LD_LOSS_DELTA (with exactly one of LD_LOSS_ATSS / LD_LOSS_RETINA): reg holds
+ * DeltaXYWH deltas (LD_LOSS_RETINA: the (N * B, 4, ...) pseudo-image views).
+ * anchors: the explicit (num_anchors * num_base, 4) list, row (cell * num_base +
+ * b), when delta->num_base > 0 (pseudo-image n uses base anchor n % num_base, so
+ * num_imgs is a multiple of num_base); NULL for the implicit square anchor.
+ * bbox_targets hold the matched GT boxes in pixels, as the target launches write
+ * them.
+ * LD_LOSS_DIST: reg holds activated distances, anchors is NULL; bbox_targets:
+ * ld_fcos_targets' (l, t, r, b) in pixels.
+ *
+ * prepass: score = the centerness target sqrt(min(l, r) / max(l, r) * min(t, b) /
+ * max(t, b)) of the positives -- delta: from the anchor centre and the
+ * encoded-then-decoded GT (atss_head.py:298-313; zero with LD_LOSS_RETINA);
+ * dist: of the targets themselves --, weight_targets = 0, norm as
+ * ld_loss_prepass leaves it (num_pos, sum of the centerness targets).
+ * pos: the box term, forward and gradient, written dense into grad_reg (zeros
+ * away from the positives), and the class-softmax statistics
+ * ld_loss_main_parts(CLS) reads.  delta: through the decode -- the gradient of a
+ * clamped dw / dh is zero.  dist: hp's LD_LOSS_BBOX_* loss on (px - d0, py - d1,
+ * px + d2, py + d3) against the same form of the targets, (px, py) = (x, y) *
+ * stride + stride / 2, weighted by the centerness target; d(loss)/d(d) =
+ * (-g.x1, -g.y1, +g.x2, +g.y2). */
+int ld_loss_plain_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                           const ld_delta_t* delta, const float* anchors,
                           const int64_t* labels, const float* bbox_targets,
                           const int32_t* counts, float* weight_targets, float* score,
                           float* norm, void* workspace, size_t workspace_bytes,
                           ld_stream_t stream);
-int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+int ld_loss_plain_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                       const ld_delta_t* delta, const float* anchors,
                       const ld_maps_t* cls, const ld_maps_t* reg,
                       const int64_t* labels, const float* bbox_targets,
                       const float* score, const float* norm, const float* upstream,
                       const ld_maps_t* grad_reg, void* workspace,
                       size_t workspace_bytes, ld_stream_t stream);
-
-/* The two launches an LD_LOSS_DIST block has of its own.  reg / grad_reg:
- * (N, 4, H_l, W_l) maps of activated distances; bbox_targets: ld_fcos_targets'
- * (l, t, r, b) in pixels.
- * prepass: score = the centerness target sqrt(min(l, r) / max(l, r) * min(t, b) /
- * max(t, b)) of the positives, weight_targets = 0, norm as ld_loss_prepass
- * leaves it (num_pos, sum of the centerness targets).
- * pos: hp's LD_LOSS_BBOX_* loss on (px - d0, py - d1, px + d2, py + d3) against
- * the same form of the targets, (px, py) = (x, y) * stride + stride / 2, weighted
- * by the centerness target; d(loss)/d(d) = (-g.x1, -g.y1, +g.x2, +g.y2), written
- * dense into grad_reg (zeros away from the positives), and the class-softmax
- * statistics ld_loss_main_parts(CLS) reads.  Any other flag combination than the
- * one LD_LOSS_DIST names: LD_EINVAL.  Same workspace as the other parts. */
-int ld_loss_dist_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
-                         const int64_t* labels, const float* bbox_targets,
-                         const int32_t* counts, float* weight_targets, float* score,
-                         float* norm, void* workspace, size_t workspace_bytes,
-                         ld_stream_t stream);
-int ld_loss_dist_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
-                     const ld_maps_t* cls, const ld_maps_t* reg, const int64_t* labels,
-                     const float* bbox_targets, const float* score, const float* norm,
-                     const float* upstream, const ld_maps_t* grad_reg, void* workspace,
-                     size_t workspace_bytes, ld_stream_t stream);
 
 /* The 'gibox' imitation region (LDHead.get_gi_region, ld_head.py:613-637;
  * LDv2Head: ld_gflv2.py:619-644 with hp->flags & LD_LOSS_PROB_CLS): per level,

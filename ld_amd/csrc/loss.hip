@@ -98,12 +98,14 @@ struct Cell {  // where this thread sits
   size_t o;  // n * A + a
 };
 
+// PER = cells per block: kWave (prepass) or kBlk (the 256-thread kernels)
+template <int PER>
 __device__ __forceinline__ Cell locate(const ld_geom_t& g, const BlockMap& bm) {
   Cell c;
   c.n = blockIdx.y;
   c.l = block_level(bm, g.num_levels, blockIdx.x);
   const ld_level_t lv = g.lv[c.l];
-  c.r = (blockIdx.x - bm.blk_start[c.l]) * kWave + threadIdx.x;
+  c.r = (blockIdx.x - bm.blk_start[c.l]) * PER + threadIdx.x;
   c.active = c.r < lv.H * lv.W;
   c.a = lv.offset + c.r;
   c.y = c.r / lv.W;
@@ -139,12 +141,24 @@ __device__ __forceinline__ Box target_box(bool fcos, float cx, float cy, const f
   return Box{t.x / stride, t.y / stride, t.z / stride, t.w / stride};
 }
 
+// centerness target of a cell from its distances to the four sides of its box
+// (atss_head.py:298-313, fcos_head.py:590-608)
+__device__ __forceinline__ float centerness_ltrb(float l, float t, float r, float b) {
+  return sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(t, b) / fmaxf(t, b)));
+}
+
+// where a prepass block leaves its wave sum: partial[S_WSUM][n][b]
+__device__ __forceinline__ size_t prepass_part_idx(const BlockMap& bm, int n) {
+  return (size_t)S_WSUM * gridDim.y * bm.blocks_per_img + (size_t)n * bm.blocks_per_img +
+         blockIdx.x;
+}
+
 __global__ __launch_bounds__(kWave) void loss_prepass_kernel(
     ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t reg,
     const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
     const float* __restrict__ vlr, float* __restrict__ weight_targets, float* __restrict__ score,
     float* __restrict__ partial) {
-  const Cell c = locate(geom, bm);
+  const Cell c = locate<kWave>(geom, bm);
   const bool fcos = (hp.flags & LD_LOSS_FCOS) != 0;
   float wt = 0.0f, sc = 0.0f;
   if (c.active) {
@@ -178,23 +192,20 @@ __global__ __launch_bounds__(kWave) void loss_prepass_kernel(
       sc = ld::iou_pair(box, tgt);
       if (fcos) {
         // fcos_gfl_head.py:705-721 on the (l, t, r, b) targets
-        sc = sqrtf((fminf(t.x, t.z) / fmaxf(t.x, t.z)) *
-                   (fminf(t.y, t.w) / fmaxf(t.y, t.w)));
+        sc = centerness_ltrb(t.x, t.y, t.z, t.w);
       } else if (hp.flags & LD_LOSS_ATSS) {
         // centerness target (atss_gfl_head.py:312-331), image pixels; the
         // anchor centre is (x, y) * stride exactly
         const float ax = cx * stride, ay = cy * stride;
         const float l_ = ax - t.x, t_ = ay - t.y, r_ = t.z - ax, b_ = t.w - ay;
-        sc = sqrtf((fminf(l_, r_) / fmaxf(l_, r_)) * (fminf(t_, b_) / fmaxf(t_, b_)));
+        sc = centerness_ltrb(l_, t_, r_, b_);
       }
     }
     weight_targets[c.o] = wt;
     score[c.o] = sc;
   }
   const float s = wave_sum((hp.flags & LD_LOSS_ATSS) ? sc : wt);
-  if (threadIdx.x == 0)
-    partial[(size_t)S_WSUM * gridDim.y * bm.blocks_per_img +
-            (size_t)c.n * bm.blocks_per_img + blockIdx.x] = s;
+  if (threadIdx.x == 0) partial[prepass_part_idx(bm, c.n)] = s;
 }
 
 __global__ __launch_bounds__(256) void loss_norm_kernel(
@@ -237,20 +248,6 @@ constexpr int kBlk = 256;
 constexpr int kZMax = 8;     // channel groups per anchor (sides, class/feature chunks)
 constexpr int kClsChunk = 16;
 constexpr int kPosRec = 8;   // floats per anchor in the positives record
-
-__device__ __forceinline__ Cell locate256(const ld_geom_t& g, const BlockMap& bm) {
-  Cell c;
-  c.n = blockIdx.y;
-  c.l = block_level(bm, g.num_levels, blockIdx.x);
-  const ld_level_t lv = g.lv[c.l];
-  c.r = (blockIdx.x - bm.blk_start[c.l]) * kBlk + threadIdx.x;
-  c.active = c.r < lv.H * lv.W;
-  c.a = lv.offset + c.r;
-  c.y = c.r / lv.W;
-  c.x = c.r - c.y * lv.W;
-  c.o = (size_t)c.n * g.num_anchors + c.a;
-  return c;
-}
 
 // fixed-order sum over the 256 threads of a block; result valid in thread 0
 __device__ __forceinline__ float block_sum(float v, float* lds4) {
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(kBlk) void loss_pos_kernel(
   // cls / t_cls here are the maps of the KD term (LDHead: the class logits;
   // LDv2Head: the raw cls_feat of student and teacher)
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   float s_bbox = 0.0f;
   if (c.active) {
     const int64_t lab = labels[c.o];
@@ -359,7 +356,7 @@ __global__ __launch_bounds__(kBlk) void loss_reg_dense_kernel(
     const float* __restrict__ norm, const float* __restrict__ upstream,
     const float* __restrict__ posrec, ld_maps_t grad_reg, float* __restrict__ partial) {
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   const int side = blockIdx.z;
   float s_dfl = 0.0f, s_ld = 0.0f, s_vlr = 0.0f;
   if (c.active) {
@@ -793,7 +790,7 @@ __global__ __launch_bounds__(kBlk) void loss_cls_dense_kernel(
     const float* __restrict__ upstream, const float* __restrict__ posrec,
     ld_maps_t grad_cls, ld_maps_t grad_kd, float* __restrict__ partial) {
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   const int NC = hp.num_classes;  // foreground classes: labels in [0, NC)
   const int C = hp.cls_channels > 0 ? hp.cls_channels : NC;
   const bool prob = (hp.flags & LD_LOSS_PROB_CLS) != 0;
@@ -887,7 +884,7 @@ __global__ __launch_bounds__(kBlk) void loss_im_dense_kernel(
     const float* __restrict__ upstream, ld_maps_t grad_x, int chunk,
     float* __restrict__ partial) {
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   const int CH = hp.feat_channels;
   const int ch0 = blockIdx.z * chunk, ch1 = min(CH, ch0 + chunk);
   float s_im = 0.0f;
@@ -929,7 +926,7 @@ __global__ __launch_bounds__(kBlk) void gi_score_kernel(
     ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t t_cls,
     ld_maps_t reg, ld_maps_t t_reg, float* __restrict__ giscore,
     float* __restrict__ gibox) {
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   if (!c.active) return;
   const int C = hp.cls_channels > 0 ? hp.cls_channels : hp.num_classes;
   const bool prob = (hp.flags & LD_LOSS_PROB_CLS) != 0;
@@ -1038,7 +1035,7 @@ __global__ __launch_bounds__(kBlk) void loss_ctr_dense_kernel(
     const float* __restrict__ norm, const float* __restrict__ upstream,
     ld_maps_t grad_ctr, float* __restrict__ partial) {
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   float s_ctr = 0.0f;
   if (c.active) {
     const int64_t lab = labels[c.o];
@@ -1102,88 +1099,67 @@ __device__ __forceinline__ void plain_cls_stats(const ld_loss_hp_t& hp, const ld
   rec[1] = make_float4(ms, zs, ms, zs);
 }
 
-__global__ __launch_bounds__(kWave) void loss_delta_prepass_kernel(
-    ld_geom_t geom, ld_loss_hp_t hp, ld_delta_t dc, BlockMap bm,
-    const float* __restrict__ anchors, const int64_t* __restrict__ labels,
-    const float* __restrict__ bbox_targets, float* __restrict__ weight_targets,
-    float* __restrict__ score, float* __restrict__ partial) {
-  const Cell c = locate(geom, bm);
-  float sc = 0.0f;
-  if (c.active) {
-    const int64_t lab = labels[c.o];
-    if ((hp.flags & LD_LOSS_ATSS) && lab >= 0 && lab < hp.num_classes) {
-      // centerness_target, atss_head.py:298-313
-      const Box an = delta_anchor(geom, dc, anchors, c);
-      const Box gt =
-          delta_target(hp, dc, an, reinterpret_cast<const float4*>(bbox_targets)[c.o]);
-      const float ax = (an.x2 + an.x1) / 2.0f, ay = (an.y2 + an.y1) / 2.0f;
-      const float l_ = ax - gt.x1, t_ = ay - gt.y1, r_ = gt.x2 - ax, b_ = gt.y2 - ay;
-      sc = sqrtf((fminf(l_, r_) / fmaxf(l_, r_)) * (fminf(t_, b_) / fmaxf(t_, b_)));
-    }
-    weight_targets[c.o] = 0.0f;
-    score[c.o] = sc;
-  }
-  const float s = wave_sum(sc);
-  if (threadIdx.x == 0)
-    partial[(size_t)S_WSUM * gridDim.y * bm.blocks_per_img +
-            (size_t)c.n * bm.blocks_per_img + blockIdx.x] = s;
-}
+// The DeltaXYWH form of a plain block.  What differs between ATSSHead and
+// RetinaHead (LD_LOSS_ATSS, box_term, num_base) is decided in here, not in the
+// kernels templated on the form.
+struct DeltaForm {
+  ld_delta_t dc;
+  const float* __restrict__ anchors;
 
-__global__ __launch_bounds__(kBlk) void loss_delta_pos_kernel(
-    ld_geom_t geom, ld_loss_hp_t hp, ld_delta_t dc, BlockMap bm,
-    const float* __restrict__ anchors, ld_maps_t cls, ld_maps_t reg,
-    const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
-    const float* __restrict__ score, const float* __restrict__ norm,
-    const float* __restrict__ upstream, ld_maps_t grad_reg, float* __restrict__ posrec,
-    float* __restrict__ partial) {
-  __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
-  float s_bbox = 0.0f;
-  if (c.active) {
-    const int64_t lab = labels[c.o];
-    float gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (lab >= 0 && lab < hp.num_classes) {
-      const float up_bbox = upstream ? upstream[1 * geom.num_levels + c.l] : 1.0f;
-      const float inv_avg = 1.0f / avg_divisor(hp, norm);
-      const Box an = delta_anchor(geom, dc, anchors, c);
-      const float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
-      float d[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) d[k] = *chan_ptr(reg, c, k);
-      if (dc.box_term == LD_DELTA_DECODED) {
-        // centerness target (ATSS) / bbox_weights = 1 (Retina)
-        const float wt = (hp.flags & LD_LOSS_ATSS) ? score[c.o] : 1.0f;
-        const float c_bbox = up_bbox * hp.lw_bbox * wt * inv_avg;
-        float jac[4], iou, g[4];
-        const Box box = ld::delta2bbox(an, d, dc.means, dc.stds, dc.max_ratio, jac);
-        const Box tgt = delta_target(hp, dc, an, t);
-        const float gl = bbox_loss_grad(hp, box, tgt, &iou, g);
-        s_bbox = wt * gl;
-        ld::delta2bbox_grad(g, jac, gd);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) gd[k] *= c_bbox;
-      } else {
-        // L1Loss / SmoothL1Loss on the deltas (anchor_head.py:414-424)
-        const float c_bbox = up_bbox * hp.lw_bbox * inv_avg;
-        float td[4];
-        ld::bbox2delta(an, Box{t.x, t.y, t.z, t.w}, dc.means, dc.stds, td);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          float dl;
-          s_bbox += dc.box_term == LD_DELTA_L1
-                        ? ld::l1_elem(d[k] - td[k], &dl)
-                        : ld::smooth_l1_elem(d[k] - td[k], dc.beta, &dl);
-          gd[k] = c_bbox * dl;
-        }
-      }
-      plain_cls_stats(hp, cls, c, posrec);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) *chan_ptr_w(grad_reg, c, k) = gd[k];
+  // (l, t, r, b) of the centerness target (atss_head.py:298-313); RetinaHead
+  // has none: false, its score stays 0
+  __device__ __forceinline__ bool ltrb(const ld_geom_t& g, const ld_loss_hp_t& hp,
+                                       const float* __restrict__ bbox_targets,
+                                       const Cell& c, float d[4]) const {
+    if (!(hp.flags & LD_LOSS_ATSS)) return false;
+    const Box an = delta_anchor(g, dc, anchors, c);
+    const Box gt =
+        delta_target(hp, dc, an, reinterpret_cast<const float4*>(bbox_targets)[c.o]);
+    const float ax = (an.x2 + an.x1) / 2.0f, ay = (an.y2 + an.y1) / 2.0f;
+    d[0] = ax - gt.x1, d[1] = ay - gt.y1, d[2] = gt.x2 - ax, d[3] = gt.y2 - ay;
+    return true;
   }
-  s_bbox = block_sum(s_bbox, lds4);
-  if (threadIdx.x == 0) partial[part_idx(S_BBOX, 0, bm, c.n)] = s_bbox;
-}
+
+  // box term of one positive: the weighted loss, gd = d total / d the 4 deltas
+  __device__ __forceinline__ float box_term(const ld_geom_t& g, const ld_loss_hp_t& hp,
+                                            const ld_maps_t& reg,
+                                            const float* __restrict__ bbox_targets,
+                                            const float* __restrict__ score, const Cell& c,
+                                            float up_bbox, float avg, float gd[4]) const {
+    const float inv_avg = 1.0f / avg;
+    const Box an = delta_anchor(g, dc, anchors, c);
+    const float4 t = reinterpret_cast<const float4*>(bbox_targets)[c.o];
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = *chan_ptr(reg, c, k);
+    if (dc.box_term == LD_DELTA_DECODED) {
+      // centerness target (ATSS) / bbox_weights = 1 (Retina)
+      const float wt = (hp.flags & LD_LOSS_ATSS) ? score[c.o] : 1.0f;
+      const float c_bbox = up_bbox * hp.lw_bbox * wt * inv_avg;
+      float jac[4], iou, gb[4];
+      const Box box = ld::delta2bbox(an, d, dc.means, dc.stds, dc.max_ratio, jac);
+      const Box tgt = delta_target(hp, dc, an, t);
+      const float gl = bbox_loss_grad(hp, box, tgt, &iou, gb);
+      ld::delta2bbox_grad(gb, jac, gd);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) gd[k] *= c_bbox;
+      return wt * gl;
+    }
+    // L1Loss / SmoothL1Loss on the deltas (anchor_head.py:414-424)
+    const float c_bbox = up_bbox * hp.lw_bbox * inv_avg;
+    float td[4], s_bbox = 0.0f;
+    ld::bbox2delta(an, Box{t.x, t.y, t.z, t.w}, dc.means, dc.stds, td);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float dl;
+      s_bbox += dc.box_term == LD_DELTA_L1
+                    ? ld::l1_elem(d[k] - td[k], &dl)
+                    : ld::smooth_l1_elem(d[k] - td[k], dc.beta, &dl);
+      gd[k] = c_bbox * dl;
+    }
+    return s_bbox;
+  }
+};
 
 // --------------------- plain FCOS: 4 activated distances (LD_LOSS_DIST) -------
 // FCOSHead.loss (fcos_head.py:157-254) on (N, 4, H, W) maps of exp / relu
@@ -1202,60 +1178,85 @@ __device__ __forceinline__ float4 dist_target(const ld_geom_t& g, const ld_loss_
   return t;
 }
 
-__global__ __launch_bounds__(kWave) void loss_dist_prepass_kernel(
-    ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, const int64_t* __restrict__ labels,
-    const float* __restrict__ bbox_targets, float* __restrict__ weight_targets,
-    float* __restrict__ score, float* __restrict__ partial) {
-  const Cell c = locate(geom, bm);
+struct DistForm {
+  // centerness_target, fcos_head.py:590-608: the distance targets themselves
+  __device__ __forceinline__ bool ltrb(const ld_geom_t& g, const ld_loss_hp_t& hp,
+                                       const float* __restrict__ bbox_targets,
+                                       const Cell& c, float d[4]) const {
+    const float4 t = dist_target(g, hp, bbox_targets, c);
+    d[0] = t.x, d[1] = t.y, d[2] = t.z, d[3] = t.w;
+    return true;
+  }
+
+  __device__ __forceinline__ float box_term(const ld_geom_t& g, const ld_loss_hp_t& hp,
+                                            const ld_maps_t& reg,
+                                            const float* __restrict__ bbox_targets,
+                                            const float* __restrict__ score, const Cell& c,
+                                            float up_bbox, float avg, float gd[4]) const {
+    const float wt = score[c.o];  // the centerness target
+    const float c_bbox = up_bbox * hp.lw_bbox * wt / avg;
+    // the point (x, y) * stride + stride // 2, in pixels
+    const int stride = g.lv[c.l].stride;
+    const float px = (float)(c.x * stride + stride / 2);
+    const float py = (float)(c.y * stride + stride / 2);
+    const float4 t = dist_target(g, hp, bbox_targets, c);
+    // distance2bbox of prediction and target about the same point
+    const Box box{px - *chan_ptr(reg, c, 0), py - *chan_ptr(reg, c, 1),
+                  px + *chan_ptr(reg, c, 2), py + *chan_ptr(reg, c, 3)};
+    const Box tgt{px - t.x, py - t.y, px + t.z, py + t.w};
+    float iou, gb[4];
+    const float gl = bbox_loss_grad(hp, box, tgt, &iou, gb);
+    gd[0] = -c_bbox * gb[0];
+    gd[1] = -c_bbox * gb[1];
+    gd[2] = c_bbox * gb[2];
+    gd[3] = c_bbox * gb[3];
+    return wt * gl;
+  }
+};
+
+// ---- the two launches of a plain block before its class part, once for both
+// forms (traces show loss_plain_{prepass,pos}_kernel<DeltaForm | DistForm>) ----
+// prepass: score = the centerness target of the positives, weight_targets = 0
+// (no plain head reads them), the normaliser partial = sum(score)
+template <class Form>
+__global__ __launch_bounds__(kWave) void loss_plain_prepass_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, Form form, BlockMap bm,
+    const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
+    float* __restrict__ weight_targets, float* __restrict__ score,
+    float* __restrict__ partial) {
+  const Cell c = locate<kWave>(geom, bm);
   float sc = 0.0f;
   if (c.active) {
     const int64_t lab = labels[c.o];
-    if (lab >= 0 && lab < hp.num_classes) {
-      // centerness_target, fcos_head.py:590-608
-      const float4 t = dist_target(geom, hp, bbox_targets, c);
-      sc = sqrtf((fminf(t.x, t.z) / fmaxf(t.x, t.z)) *
-                 (fminf(t.y, t.w) / fmaxf(t.y, t.w)));
-    }
+    float d[4];
+    if (lab >= 0 && lab < hp.num_classes && form.ltrb(geom, hp, bbox_targets, c, d))
+      sc = centerness_ltrb(d[0], d[1], d[2], d[3]);
     weight_targets[c.o] = 0.0f;
     score[c.o] = sc;
   }
   const float s = wave_sum(sc);
-  if (threadIdx.x == 0)
-    partial[(size_t)S_WSUM * gridDim.y * bm.blocks_per_img +
-            (size_t)c.n * bm.blocks_per_img + blockIdx.x] = s;
+  if (threadIdx.x == 0) partial[prepass_part_idx(bm, c.n)] = s;
 }
 
-__global__ __launch_bounds__(kBlk) void loss_dist_pos_kernel(
-    ld_geom_t geom, ld_loss_hp_t hp, BlockMap bm, ld_maps_t cls, ld_maps_t reg,
+// positives: the box term and its gradient on the 4 reg channels (zero away
+// from the positives), the class statistics the CLS part reads
+template <class Form>
+__global__ __launch_bounds__(kBlk) void loss_plain_pos_kernel(
+    ld_geom_t geom, ld_loss_hp_t hp, Form form, BlockMap bm, ld_maps_t cls, ld_maps_t reg,
     const int64_t* __restrict__ labels, const float* __restrict__ bbox_targets,
     const float* __restrict__ score, const float* __restrict__ norm,
     const float* __restrict__ upstream, ld_maps_t grad_reg, float* __restrict__ posrec,
     float* __restrict__ partial) {
   __shared__ float lds4[4];
-  const Cell c = locate256(geom, bm);
+  const Cell c = locate<kBlk>(geom, bm);
   float s_bbox = 0.0f;
   if (c.active) {
     const int64_t lab = labels[c.o];
     float gd[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (lab >= 0 && lab < hp.num_classes) {
       const float up_bbox = upstream ? upstream[1 * geom.num_levels + c.l] : 1.0f;
-      const float wt = score[c.o];  // the centerness target
-      const float c_bbox = up_bbox * hp.lw_bbox * wt / avg_divisor(hp, norm);
-      // the point (x, y) * stride + stride // 2, in pixels
-      const int stride = geom.lv[c.l].stride;
-      const float px = (float)(c.x * stride + stride / 2);
-      const float py = (float)(c.y * stride + stride / 2);
-      const float4 t = dist_target(geom, hp, bbox_targets, c);
-      // distance2bbox of prediction and target about the same point
-      const Box box{px - *chan_ptr(reg, c, 0), py - *chan_ptr(reg, c, 1),
-                    px + *chan_ptr(reg, c, 2), py + *chan_ptr(reg, c, 3)};
-      const Box tgt{px - t.x, py - t.y, px + t.z, py + t.w};
-      float iou, g[4];
-      s_bbox = wt * bbox_loss_grad(hp, box, tgt, &iou, g);
-      gd[0] = -c_bbox * g[0];
-      gd[1] = -c_bbox * g[1];
-      gd[2] = c_bbox * g[2];
-      gd[3] = c_bbox * g[3];
+      s_bbox = form.box_term(geom, hp, reg, bbox_targets, score, c, up_bbox,
+                             avg_divisor(hp, norm), gd);
       plain_cls_stats(hp, cls, c, posrec);
     }
 #pragma unroll
@@ -1449,6 +1450,15 @@ LossWs loss_ws(const ld_geom_t& g) {
 }
 inline int im_chunk(int ch) { return max(32, (ch + kZMax - 1) / kZMax); }
 
+// norm <- (total positives, fixed-order sum of a prepass' S_WSUM partials)
+void launch_norm(const ld_geom_t& geom, const BlockMap& bm64, const float* partial,
+                 const int32_t* counts, float* norm, hipStream_t stream) {
+  const int nparts = geom.num_imgs * bm64.blocks_per_img;
+  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
+            partial + (size_t)S_WSUM * nparts, counts, geom.num_imgs + 2 * geom.num_levels,
+            norm);
+}
+
 // ---- which reg-side kernel ld_loss_main_parts launches ----------------------
 // variant word: bits 0-1 log2(VEC) | bit 2 NT loads | bit 3 NT stores | bit 4
 // FAST (v_exp_f32 / v_rcp_f32) | bit 5 side_fast | bit 6 "NT bits also apply
@@ -1582,7 +1592,7 @@ extern "C" int ld_loss_prepass_ex(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   if (int e = check_hp(hp)) return e;
   if ((hp->flags & LD_LOSS_FCOS) && (!vlr || !(hp->flags & LD_LOSS_ATSS)))
     return LD_EINVAL;
-  // 4 distance channels are not what this prepass reads: ld_loss_dist_prepass
+  // 4 distance channels are not what this prepass reads: ld_loss_plain_prepass
   if (hp->flags & LD_LOSS_DIST) return LD_EINVAL;
   if (!cls || !reg || !labels || !bbox_targets || !counts || !weight_targets ||
       !score || !norm)
@@ -1596,10 +1606,7 @@ extern "C" int ld_loss_prepass_ex(const ld_geom_t* geom, const ld_loss_hp_t* hp,
   LD_LAUNCH(loss_prepass_kernel, grid, dim3(kWave), 0, stream, *geom,
                      *hp, bm, *cls, *reg, labels, bbox_targets, vlr, weight_targets,
                      score, partial);
-  const int nparts = geom->num_imgs * bm.blocks_per_img;
-  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
-                     partial + (size_t)S_WSUM * nparts, counts,
-                     geom->num_imgs + 2 * geom->num_levels, norm);
+  launch_norm(*geom, bm, partial, counts, norm, stream);
   return (int)hipGetLastError();
 }
 
@@ -1736,9 +1743,22 @@ int check_delta(const ld_loss_hp_t* hp, const ld_delta_t* dc, const float* ancho
     if (!(dc->stds[k] > 0.0f)) return LD_EINVAL;
   return 0;
 }
+
+// a plain block has exactly one of the two forms, and `delta` says which
+int check_plain(const ld_geom_t* geom, const ld_loss_hp_t* hp, const ld_delta_t* dc,
+                const float* anchors) {
+  const bool delta = (hp->flags & LD_LOSS_DELTA) != 0;
+  if (delta == ((hp->flags & LD_LOSS_DIST) != 0) || delta != (dc != nullptr))
+    return LD_EINVAL;
+  if (!delta) return anchors ? LD_EINVAL : check_dist(hp);
+  if (int e = check_delta(hp, dc, anchors)) return e;
+  // pseudo-image n reads base anchor n % num_base: whole images only
+  if (dc->num_base > 0 && geom->num_imgs % dc->num_base != 0) return LD_EINVAL;
+  return 0;
+}
 }  // namespace
 
-extern "C" int ld_loss_delta_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+extern "C" int ld_loss_plain_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                                      const ld_delta_t* delta, const float* anchors,
                                      const int64_t* labels, const float* bbox_targets,
                                      const int32_t* counts, float* weight_targets,
@@ -1746,26 +1766,27 @@ extern "C" int ld_loss_delta_prepass(const ld_geom_t* geom, const ld_loss_hp_t* 
                                      size_t workspace_bytes, ld_stream_t stream_) {
   if (int e = check_geom(geom)) return e;
   if (int e = check_hp(hp)) return e;
-  if (int e = check_delta(hp, delta, anchors)) return e;
+  if (int e = check_plain(geom, hp, delta, anchors)) return e;
   if (!labels || !bbox_targets || !counts || !weight_targets || !score || !norm)
     return LD_EINVAL;
-  if (delta->num_base > 0 && geom->num_imgs % delta->num_base != 0) return LD_EINVAL;
   if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
     return LD_ENOSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const BlockMap bm = make_block_map(*geom, kWave);
   float* partial = (float*)workspace;
-  LD_LAUNCH(loss_delta_prepass_kernel, dim3(bm.blocks_per_img, geom->num_imgs),
-                     dim3(kWave), 0, stream, *geom, *hp, *delta, bm, anchors, labels,
-                     bbox_targets, weight_targets, score, partial);
-  const int nparts = geom->num_imgs * bm.blocks_per_img;
-  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
-                     partial + (size_t)S_WSUM * nparts, counts,
-                     geom->num_imgs + 2 * geom->num_levels, norm);
+  const dim3 grid(bm.blocks_per_img, geom->num_imgs);
+  if (delta)
+    LD_LAUNCH(loss_plain_prepass_kernel<DeltaForm>, grid, dim3(kWave), 0, stream, *geom,
+              *hp, DeltaForm{*delta, anchors}, bm, labels, bbox_targets, weight_targets,
+              score, partial);
+  else
+    LD_LAUNCH(loss_plain_prepass_kernel<DistForm>, grid, dim3(kWave), 0, stream, *geom,
+              *hp, DistForm{}, bm, labels, bbox_targets, weight_targets, score, partial);
+  launch_norm(*geom, bm, partial, counts, norm, stream);
   return (int)hipGetLastError();
 }
 
-extern "C" int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
+extern "C" int ld_loss_plain_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                                  const ld_delta_t* delta, const float* anchors,
                                  const ld_maps_t* cls, const ld_maps_t* reg,
                                  const int64_t* labels, const float* bbox_targets,
@@ -1775,68 +1796,24 @@ extern "C" int ld_loss_delta_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
                                  ld_stream_t stream_) {
   if (int e = check_geom(geom)) return e;
   if (int e = check_hp(hp)) return e;
-  if (int e = check_delta(hp, delta, anchors)) return e;
+  if (int e = check_plain(geom, hp, delta, anchors)) return e;
   if (!cls || !reg || !labels || !bbox_targets || !score || !norm || !grad_reg)
-    return LD_EINVAL;
-  if (delta->num_base > 0 && geom->num_imgs % delta->num_base != 0) return LD_EINVAL;
-  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
-    return LD_ENOSPACE;
-  const LossWs w = loss_ws(*geom);
-  float* partial = (float*)workspace + w.pre_floats;
-  float* posrec = partial + w.main_floats;
-  LD_LAUNCH(loss_delta_pos_kernel, dim3(w.bm256.blocks_per_img, geom->num_imgs),
-                     dim3(kBlk), 0, (hipStream_t)stream_, *geom, *hp, *delta, w.bm256,
-                     anchors, *cls, *reg, labels, bbox_targets, score, norm, upstream,
-                     *grad_reg, posrec, partial);
-  return (int)hipGetLastError();
-}
-
-extern "C" int ld_loss_dist_prepass(const ld_geom_t* geom, const ld_loss_hp_t* hp,
-                                    const int64_t* labels, const float* bbox_targets,
-                                    const int32_t* counts, float* weight_targets,
-                                    float* score, float* norm, void* workspace,
-                                    size_t workspace_bytes, ld_stream_t stream_) {
-  if (int e = check_geom(geom)) return e;
-  if (int e = check_hp(hp)) return e;
-  if (int e = check_dist(hp)) return e;
-  if (!labels || !bbox_targets || !counts || !weight_targets || !score || !norm)
     return LD_EINVAL;
   if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
     return LD_ENOSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  const BlockMap bm = make_block_map(*geom, kWave);
-  float* partial = (float*)workspace;
-  LD_LAUNCH(loss_dist_prepass_kernel, dim3(bm.blocks_per_img, geom->num_imgs),
-                     dim3(kWave), 0, stream, *geom, *hp, bm, labels, bbox_targets,
-                     weight_targets, score, partial);
-  const int nparts = geom->num_imgs * bm.blocks_per_img;
-  LD_LAUNCH(loss_norm_kernel, dim3(1), dim3(256), 0, stream, nparts,
-                     partial + (size_t)S_WSUM * nparts, counts,
-                     geom->num_imgs + 2 * geom->num_levels, norm);
-  return (int)hipGetLastError();
-}
-
-extern "C" int ld_loss_dist_pos(const ld_geom_t* geom, const ld_loss_hp_t* hp,
-                                const ld_maps_t* cls, const ld_maps_t* reg,
-                                const int64_t* labels, const float* bbox_targets,
-                                const float* score, const float* norm,
-                                const float* upstream, const ld_maps_t* grad_reg,
-                                void* workspace, size_t workspace_bytes,
-                                ld_stream_t stream_) {
-  if (int e = check_geom(geom)) return e;
-  if (int e = check_hp(hp)) return e;
-  if (int e = check_dist(hp)) return e;
-  if (!cls || !reg || !labels || !bbox_targets || !score || !norm || !grad_reg)
-    return LD_EINVAL;
-  if (!workspace || workspace_bytes < ld_loss_workspace_bytes(geom))
-    return LD_ENOSPACE;
   const LossWs w = loss_ws(*geom);
   float* partial = (float*)workspace + w.pre_floats;
   float* posrec = partial + w.main_floats;
-  LD_LAUNCH(loss_dist_pos_kernel, dim3(w.bm256.blocks_per_img, geom->num_imgs),
-                     dim3(kBlk), 0, (hipStream_t)stream_, *geom, *hp, w.bm256, *cls, *reg,
-                     labels, bbox_targets, score, norm, upstream, *grad_reg, posrec,
-                     partial);
+  const dim3 grid(w.bm256.blocks_per_img, geom->num_imgs);
+  if (delta)
+    LD_LAUNCH(loss_plain_pos_kernel<DeltaForm>, grid, dim3(kBlk), 0, stream, *geom, *hp,
+              DeltaForm{*delta, anchors}, w.bm256, *cls, *reg, labels, bbox_targets, score,
+              norm, upstream, *grad_reg, posrec, partial);
+  else
+    LD_LAUNCH(loss_plain_pos_kernel<DistForm>, grid, dim3(kBlk), 0, stream, *geom, *hp,
+              DistForm{}, w.bm256, *cls, *reg, labels, bbox_targets, score, norm, upstream,
+              *grad_reg, posrec, partial);
   return (int)hipGetLastError();
 }
 

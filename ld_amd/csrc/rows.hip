@@ -455,5 +455,5 @@ extern "C" int ld_sum(const float* x, int64_t n, float* out, void* workspace,
   return (int)hipGetLastError();
 }
 
-extern "C" int ld_abi_version(void) { return 25; }
+extern "C" int ld_abi_version(void) { return 26; }
 extern "C" const char* ld_target_arch(void) { return "gfx950"; }

@@ -306,7 +306,7 @@ def save_tune_table(path):
     return get_lib().ld_conv_tune_save(str(path).encode())
 
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 _vp, _i64, _i32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_size_t
 _G, _H, _M = C.POINTER(GeomT), C.POINTER(LossHpT), C.POINTER(MapsT)
 _CV, _EP, _LV = C.POINTER(ConvT), C.POINTER(ConvEpilogueT), C.POINTER(LevelsT)
@@ -386,14 +386,10 @@ SIGNATURES = {
     'ld_loss_centerness': (C.c_int, [_G, _H, _M, _vp, _vp, _vp, _vp, _M, _vp,
                                      _sz, _vp]),
     'ld_loss_set_reg_variant': (C.c_int, [_i32]),
-    'ld_loss_delta_prepass': (C.c_int, [_G, _H, _D, _vp, _vp, _vp, _vp, _vp,
+    'ld_loss_plain_prepass': (C.c_int, [_G, _H, _D, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _sz, _vp]),
-    'ld_loss_delta_pos': (C.c_int, [_G, _H, _D, _vp, _M, _M, _vp, _vp, _vp,
+    'ld_loss_plain_pos': (C.c_int, [_G, _H, _D, _vp, _M, _M, _vp, _vp, _vp,
                                     _vp, _vp, _M, _vp, _sz, _vp]),
-    'ld_loss_dist_prepass': (C.c_int, [_G, _H, _vp, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _sz, _vp]),
-    'ld_loss_dist_pos': (C.c_int, [_G, _H, _M, _M, _vp, _vp, _vp, _vp, _vp, _M,
-                                   _vp, _sz, _vp]),
     'ld_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
     'ld_smooth_l1_rows': (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp,
                                     _vp]),

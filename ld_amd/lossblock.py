@@ -241,6 +241,56 @@ def _static_targets(img_metas):
     return img_metas[0].get('ld_static_targets') if img_metas else None
 
 
+def _pack_gt(gt_bboxes, gt_labels, N, device, static=None):
+    """The ground truth of a batch as the target launches read it: boxes
+    (N, max_gt, 4), labels (N, max_gt), per-image counts ``ng`` on the device.
+    -> (gtb, gtl, ng, max_gt, num_gt).  ``static``: a captured step's
+    ``StaticTargets``, whose fixed-address buffers are taken as they are."""
+    if static is not None:
+        # captured step: padded boxes + device-side counts at fixed addresses
+        return (static.gtb, static.gtl, static.ng, static.max_gt,
+                list(static.num_gt))
+    num_gt = [int(b.shape[0]) for b in gt_bboxes]
+    max_gt = max(num_gt) if num_gt else 0
+    gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
+                      device=device)
+    gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64, device=device)
+    for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
+        if num_gt[i]:
+            L.require_device(b, torch.float32, 'gt_bboxes')
+            gtb[i, :num_gt[i]] = b
+            gtl[i, :num_gt[i]] = l
+    return gtb, gtl, _small_int_tensor(tuple(num_gt), device), max_gt, num_gt
+
+
+def _valid_hw(static, featmap_sizes, strides, img_metas, device):
+    """Per image and level (valid_h, valid_w), a device int32 buffer."""
+    if static is not None:
+        return static.valid_hw(featmap_sizes, strides)
+    return _small_int_tensor(
+        tuple(tuple(r) for r in valid_hw_from_metas(featmap_sizes, strides,
+                                                    img_metas)), device)
+
+
+def _alloc_targets(rows, A, num_levels, device, gt_inds=False):
+    """The arrays every target launch fills, for ``rows`` (pseudo-)images."""
+    out = dict(
+        labels=torch.empty((rows, A), dtype=torch.int64, device=device),
+        label_weights=torch.empty((rows, A), dtype=torch.float32,
+                                  device=device),
+        bbox_targets=torch.empty((rows, A, 4), dtype=torch.float32,
+                                 device=device),
+        vlr=torch.empty((rows, A), dtype=torch.float32, device=device),
+        im=torch.empty((rows, A), dtype=torch.float32, device=device),
+        counts=torch.empty(rows + 2 * num_levels + 1, dtype=torch.int32,
+                           device=device),
+    )
+    if gt_inds:
+        out['gt_inds'] = torch.empty((rows, A), dtype=torch.int64,
+                                     device=device)
+    return out
+
+
 def atss_targets(featmap_sizes, strides, img_metas, gt_bboxes, gt_labels, hp,
                  device, anchor_scale=8):
     """Dense ATSS / VLR / IM targets for a batch (see ld_atss_targets in
@@ -248,38 +298,11 @@ def atss_targets(featmap_sizes, strides, img_metas, gt_bboxes, gt_labels, hp,
     lib = L.get_lib()
     N = len(img_metas)
     geom = L.make_geom(featmap_sizes, strides, N, anchor_scale)
-    A, nl = geom.num_anchors, geom.num_levels
     st = _static_targets(img_metas)
-    if st is not None:
-        # captured step: padded boxes + device-side counts at fixed addresses
-        gtb, gtl, ng, max_gt = st.gtb, st.gtl, st.ng, st.max_gt
-        num_gt = list(st.num_gt)
-        vhw = st.valid_hw(featmap_sizes, strides)
-    else:
-        num_gt = [int(b.shape[0]) for b in gt_bboxes]
-        max_gt = max(num_gt) if num_gt else 0
-        gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
-                          device=device)
-        gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64,
-                          device=device)
-        for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
-            if num_gt[i]:
-                L.require_device(b, torch.float32, 'gt_bboxes')
-                gtb[i, :num_gt[i]] = b
-                gtl[i, :num_gt[i]] = l
-        ng = _small_int_tensor(tuple(num_gt), device)
-        vhw = _small_int_tensor(
-            tuple(tuple(r) for r in valid_hw_from_metas(featmap_sizes, strides,
-                                                        img_metas)), device)
-    out = dict(
-        labels=torch.empty((N, A), dtype=torch.int64, device=device),
-        label_weights=torch.empty((N, A), dtype=torch.float32, device=device),
-        bbox_targets=torch.empty((N, A, 4), dtype=torch.float32,
-                                 device=device),
-        vlr=torch.empty((N, A), dtype=torch.float32, device=device),
-        im=torch.empty((N, A), dtype=torch.float32, device=device),
-        counts=torch.empty(N + 2 * nl + 1, dtype=torch.int32, device=device),
-    )
+    gtb, gtl, ng, max_gt, num_gt = _pack_gt(gt_bboxes, gt_labels, N, device,
+                                            st)
+    vhw = _valid_hw(st, featmap_sizes, strides, img_metas, device)
+    out = _alloc_targets(N, geom.num_anchors, geom.num_levels, device)
     need = lib.ld_atss_targets_workspace_bytes(C.byref(geom), max_gt)
     ws = workspace(device, need, 'targets')
     rc = lib.ld_atss_targets(
@@ -303,34 +326,10 @@ def fcos_targets(featmap_sizes, strides, gt_bboxes, gt_labels, num_classes,
     lib = L.get_lib()
     N = len(gt_bboxes)
     geom = L.make_geom(featmap_sizes, strides, N, 8)
-    A, nl = geom.num_anchors, geom.num_levels
-    st = _static_targets(img_metas)
-    if st is not None:
-        # captured step: padded boxes + device-side counts at fixed addresses
-        gtb, gtl, ng, max_gt = st.gtb, st.gtl, st.ng, st.max_gt
-        num_gt = list(st.num_gt)
-    else:
-        num_gt = [int(b.shape[0]) for b in gt_bboxes]
-        max_gt = max(num_gt) if num_gt else 0
-        gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
-                          device=device)
-        gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64,
-                          device=device)
-        for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
-            if num_gt[i]:
-                L.require_device(b, torch.float32, 'gt_bboxes')
-                gtb[i, :num_gt[i]] = b
-                gtl[i, :num_gt[i]] = l
-        ng = _small_int_tensor(tuple(num_gt), device)
-    out = dict(
-        labels=torch.empty((N, A), dtype=torch.int64, device=device),
-        label_weights=torch.empty((N, A), dtype=torch.float32, device=device),
-        bbox_targets=torch.empty((N, A, 4), dtype=torch.float32,
-                                 device=device),
-        vlr=torch.empty((N, A), dtype=torch.float32, device=device),
-        im=torch.empty((N, A), dtype=torch.float32, device=device),
-        counts=torch.empty(N + 2 * nl + 1, dtype=torch.int32, device=device),
-    )
+    nl = geom.num_levels
+    gtb, gtl, ng, max_gt, num_gt = _pack_gt(gt_bboxes, gt_labels, N, device,
+                                            _static_targets(img_metas))
+    out = _alloc_targets(N, geom.num_anchors, nl, device)
     flat = [float(min(v, 1e8)) for r in regress_ranges for v in r]
     assert len(flat) == 2 * nl
     rr = (C.c_float * len(flat))(*flat)
@@ -352,43 +351,22 @@ def retina_targets(featmap_sizes, strides, img_metas, gt_bboxes, gt_labels,
     (ld_retina_targets).  ``anchors``: the per-level explicit lists of
     AnchorGenerator.grid_anchors.  Arrays come back in the pseudo-image layout
     (N * num_base, A) the loss block sweeps (include/ld_hip.h LD_LOSS_RETINA);
-    ``geom`` in the result is that pseudo-image geometry."""
+    ``geom`` in the result is that pseudo-image geometry.
+
+    Open item: a ``StaticTargets`` in ``img_metas`` is ignored -- this wrapper
+    always packs the batch itself, so a Retina step cannot be captured yet."""
     lib = L.get_lib()
     N, B = len(img_metas), int(num_base)
     geom = L.make_geom(featmap_sizes, strides, N, 8)
-    A, nl = geom.num_anchors, geom.num_levels
+    A = geom.num_anchors
     flat = anchors[0] if len(anchors) == 1 else torch.cat(list(anchors))
     flat = L.require_device(flat.contiguous(), torch.float32, 'anchors')
     if flat.shape != (A * B, 4):
         raise L.LdError(f'retina_targets: {tuple(flat.shape)} anchors for '
                         f'{A} cells x {B}')
-    num_gt = [int(b.shape[0]) for b in gt_bboxes]
-    max_gt = max(num_gt) if num_gt else 0
-    gtb = torch.zeros((N, max(max_gt, 1), 4), dtype=torch.float32,
-                      device=device)
-    gtl = torch.zeros((N, max(max_gt, 1)), dtype=torch.int64, device=device)
-    for i, (b, l) in enumerate(zip(gt_bboxes, gt_labels)):
-        if num_gt[i]:
-            L.require_device(b, torch.float32, 'gt_bboxes')
-            gtb[i, :num_gt[i]] = b
-            gtl[i, :num_gt[i]] = l
-    ng = _small_int_tensor(tuple(num_gt), device)
-    vhw = _small_int_tensor(
-        tuple(tuple(r) for r in valid_hw_from_metas(featmap_sizes, strides,
-                                                    img_metas)), device)
-    NB = N * B
-    out = dict(
-        labels=torch.empty((NB, A), dtype=torch.int64, device=device),
-        label_weights=torch.empty((NB, A), dtype=torch.float32, device=device),
-        bbox_targets=torch.empty((NB, A, 4), dtype=torch.float32,
-                                 device=device),
-        vlr=torch.empty((NB, A), dtype=torch.float32, device=device),
-        im=torch.empty((NB, A), dtype=torch.float32, device=device),
-        counts=torch.empty(NB + 2 * nl + 1, dtype=torch.int32, device=device),
-    )
-    if want_gt_inds:
-        out['gt_inds'] = torch.empty((NB, A), dtype=torch.int64,
-                                     device=device)
+    gtb, gtl, ng, max_gt, num_gt = _pack_gt(gt_bboxes, gt_labels, N, device)
+    vhw = _valid_hw(None, featmap_sizes, strides, img_metas, device)
+    out = _alloc_targets(N * B, A, geom.num_levels, device, want_gt_inds)
     need = lib.ld_retina_targets_workspace_bytes(C.byref(geom), B, max_gt)
     ws = workspace(device, need, 'targets')
     L.check(lib.ld_retina_targets(
@@ -399,7 +377,7 @@ def retina_targets(featmap_sizes, strides, img_metas, gt_bboxes, gt_labels,
         L.ptr(out['bbox_targets']), L.ptr(out['vlr']), L.ptr(out['im']),
         L.ptr(out['counts']), L.ptr(out.get('gt_inds')), L.ptr(ws),
         ws.numel(), L.stream_ptr(device)), 'ld_retina_targets')
-    out['geom'] = L.make_geom(featmap_sizes, strides, NB, 8)
+    out['geom'] = L.make_geom(featmap_sizes, strides, N * B, 8)
     out['num_gt'] = num_gt
     out['num_base'] = B
     return out
@@ -436,10 +414,6 @@ def gi_region(hp, targets, cls, reg, t_cls, t_reg, topn=10, iou_thr=0.3):
     out = dict(targets)
     out['im'], out['counts'] = im, counts
     return out
-
-
-class _LossState:
-    pass
 
 
 class DeferredNorm:
@@ -552,28 +526,32 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     their gradient comes back as grads['ctr'] and the centerness loss in row 6.
     reduce_norm: optional callable(norm_tensor[2]) doing the cross-rank MEAN
     in place (core/utils/dist_utils.py:63-69) -- device side, no host sync.
-    hp.flags & LD_LOSS_DELTA (ATSSHead / RetinaHead): ``reg`` are 4-channel
-    DeltaXYWH maps and ``targets['delta']`` = (ld_delta_t, explicit anchors or
-    None); the block runs its delta prepass / positives launches and the class
-    part only, the teacher arguments are not read.
-    hp.flags & LD_LOSS_DIST (FCOSHead): ``reg`` are 4-channel maps of activated
-    distances (layers.scale_act_levels) and ``targets`` those of
-    :func:`fcos_targets`; the block runs its dist prepass / positives launches,
-    the class part and the centerness term.
+    hp.flags & (LD_LOSS_DELTA | LD_LOSS_DIST), the plain heads: ``reg`` are
+    4-channel maps and the block runs its plain prepass / positives launches,
+    the class part and (LD_LOSS_ATSS) the centerness term; the teacher
+    arguments are not read.  LD_LOSS_DELTA (ATSSHead / RetinaHead): DeltaXYWH
+    maps, ``targets['delta']`` = (ld_delta_t, explicit anchors or None).
+    LD_LOSS_DIST (FCOSHead): activated distances (layers.scale_act_levels),
+    ``targets`` those of :func:`fcos_targets`.
     Returns (losses (8, L) tensor, grads dict of lists, norm tensor).
     """
     lib = L.get_lib()
     geom = targets['geom']
-    delta = None
-    if hp.flags & L.LD_LOSS_DELTA:
-        delta = targets['delta']
+    # the plain forms as one value: (ld_delta_t or None, anchors or None)
+    plain = None
+    if hp.flags & (L.LD_LOSS_DELTA | L.LD_LOSS_DIST):
+        delta = bool(hp.flags & L.LD_LOSS_DELTA)
+        plain = targets['delta'] if delta else (None, None)
         if any(r.shape[1] != 4 for r in reg):
-            raise L.LdError('LD_LOSS_DELTA: the reg maps carry 4 channels per '
-                            'anchor')
-    dist = bool(hp.flags & L.LD_LOSS_DIST)
-    if dist and any(r.shape[1] != 4 for r in reg):
-        raise L.LdError('LD_LOSS_DIST: the reg maps carry 4 distances per '
-                        'point')
+            raise L.LdError(
+                'LD_LOSS_DELTA: the reg maps carry 4 channels per anchor'
+                if delta else
+                'LD_LOSS_DIST: the reg maps carry 4 distances per point')
+
+    def plain_args():
+        return (None if plain[0] is None else C.byref(plain[0]),
+                L.ptr(plain[1]))
+
     device = cls[0].device
     N, A = geom.num_imgs, geom.num_anchors
     m_cls, m_reg = L.make_maps(cls), L.make_maps(reg)
@@ -603,23 +581,17 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     need = lib.ld_loss_workspace_bytes(C.byref(geom))
     ws = workspace(device, need, 'loss')
     st = L.stream_ptr(device)
-    if delta is not None:
-        L.check(lib.ld_loss_delta_prepass(
-            C.byref(geom), C.byref(hp), C.byref(delta[0]), L.ptr(delta[1]),
-            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
-            L.ptr(targets['counts']), L.ptr(wt), L.ptr(score), L.ptr(norm),
-            L.ptr(ws), ws.numel(), st), 'ld_loss_delta_prepass')
-    elif dist:
-        L.check(lib.ld_loss_dist_prepass(
-            C.byref(geom), C.byref(hp), L.ptr(targets['labels']),
-            L.ptr(targets['bbox_targets']), L.ptr(targets['counts']),
-            L.ptr(wt), L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
-            'ld_loss_dist_prepass')
+    labels, bbox_targets, counts = (L.ptr(targets[k]) for k in
+                                    ('labels', 'bbox_targets', 'counts'))
+    if plain is not None:
+        L.check(lib.ld_loss_plain_prepass(
+            C.byref(geom), C.byref(hp), *plain_args(), labels, bbox_targets,
+            counts, L.ptr(wt), L.ptr(score), L.ptr(norm), L.ptr(ws),
+            ws.numel(), st), 'ld_loss_plain_prepass')
     else:
         L.check(lib.ld_loss_prepass_ex(
             C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
-            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
-            L.ptr(targets['vlr']), L.ptr(targets['counts']), L.ptr(wt),
+            labels, bbox_targets, L.ptr(targets['vlr']), counts, L.ptr(wt),
             L.ptr(score), L.ptr(norm), L.ptr(ws), ws.numel(), st),
             'ld_loss_prepass')
     up = None
@@ -639,9 +611,36 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     keep = (cls, reg, t_cls, t_reg, x, t_x, kd_s, kd_t, grads, aux)
 
     def _main(norm, keep=keep):
-        _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg,
-                         m_x, m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x,
-                         m_kds, m_kdt, mg_kd, ctr, g_ctr, ws, losses, st, delta)
+        """main -> (centerness) -> finalise with the normalisers in ``norm``."""
+        parts = 15
+        if plain is not None:
+            # the positives' box term on the 4 channels, then the class part
+            L.check(lib.ld_loss_plain_pos(
+                C.byref(geom), C.byref(hp), *plain_args(), C.byref(m_cls),
+                C.byref(m_reg), labels, bbox_targets, L.ptr(score),
+                L.ptr(norm), L.ptr(up), C.byref(mg_reg), L.ptr(ws), ws.numel(),
+                st), 'ld_loss_plain_pos')
+            parts = L.LD_LOSS_PART_CLS
+        L.check(lib.ld_loss_main_parts(
+            C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
+            C.byref(m_tcls), C.byref(m_treg), C.byref(m_x), C.byref(m_tx),
+            labels, L.ptr(targets['label_weights']), bbox_targets,
+            L.ptr(targets['vlr']), L.ptr(targets['im']), counts, L.ptr(wt),
+            L.ptr(score), L.ptr(norm), L.ptr(up), C.byref(mg_cls),
+            C.byref(mg_reg), C.byref(mg_x),
+            C.byref(m_kds) if split else None,
+            C.byref(m_kdt) if split else None,
+            C.byref(mg_kd) if split else None, L.ptr(ws), ws.numel(), parts,
+            st), 'ld_loss_main')
+        if g_ctr is not None:
+            L.check(lib.ld_loss_centerness(
+                C.byref(geom), C.byref(hp), C.byref(L.make_maps(ctr)), labels,
+                L.ptr(score), L.ptr(norm), L.ptr(up),
+                C.byref(L.make_maps(g_ctr)), L.ptr(ws), ws.numel(), st),
+                'ld_loss_centerness')
+        L.check(lib.ld_loss_finalize(
+            C.byref(geom), C.byref(hp), counts, L.ptr(norm), L.ptr(ws),
+            L.ptr(losses), st), 'ld_loss_finalize')
 
     if deferred:
         # virtual ranks: the main part waits for the other ranks' prepasses
@@ -653,50 +652,14 @@ def loss_block_forward(hp, targets, cls, reg, t_cls, t_reg, x, t_x,
     return losses, grads, norm, aux
 
 
-def _loss_block_main(lib, geom, hp, targets, m_cls, m_reg, m_tcls, m_treg, m_x,
-                     m_tx, wt, score, norm, up, mg_cls, mg_reg, mg_x, m_kds,
-                     m_kdt, mg_kd, ctr, g_ctr, ws, losses, st, delta=None):
-    """main -> (centerness) -> finalise of ``loss_block_forward`` with the
-    normalisers in ``norm``."""
-    split = m_kds is not None
-    parts = 15
-    if delta is not None:
-        # the positives' box term on the 4 deltas, then the class part alone
-        L.check(lib.ld_loss_delta_pos(
-            C.byref(geom), C.byref(hp), C.byref(delta[0]), L.ptr(delta[1]),
-            C.byref(m_cls), C.byref(m_reg), L.ptr(targets['labels']),
-            L.ptr(targets['bbox_targets']), L.ptr(score), L.ptr(norm),
-            L.ptr(up), C.byref(mg_reg), L.ptr(ws), ws.numel(), st),
-            'ld_loss_delta_pos')
-        parts = L.LD_LOSS_PART_CLS
-    elif hp.flags & L.LD_LOSS_DIST:
-        # the positives' box term on the 4 distances, then the class part
-        L.check(lib.ld_loss_dist_pos(
-            C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
-            L.ptr(targets['labels']), L.ptr(targets['bbox_targets']),
-            L.ptr(score), L.ptr(norm), L.ptr(up), C.byref(mg_reg), L.ptr(ws),
-            ws.numel(), st), 'ld_loss_dist_pos')
-        parts = L.LD_LOSS_PART_CLS
-    L.check(lib.ld_loss_main_parts(
-        C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
-        C.byref(m_tcls), C.byref(m_treg), C.byref(m_x), C.byref(m_tx),
-        L.ptr(targets['labels']), L.ptr(targets['label_weights']),
-        L.ptr(targets['bbox_targets']), L.ptr(targets['vlr']),
-        L.ptr(targets['im']), L.ptr(targets['counts']), L.ptr(wt),
-        L.ptr(score), L.ptr(norm), L.ptr(up), C.byref(mg_cls),
-        C.byref(mg_reg), C.byref(mg_x),
-        C.byref(m_kds) if split else None, C.byref(m_kdt) if split else None,
-        C.byref(mg_kd) if split else None, L.ptr(ws), ws.numel(), parts, st),
-        'ld_loss_main')
-    if g_ctr is not None:
-        L.check(lib.ld_loss_centerness(
-            C.byref(geom), C.byref(hp), C.byref(L.make_maps(ctr)),
-            L.ptr(targets['labels']), L.ptr(score), L.ptr(norm), L.ptr(up),
-            C.byref(L.make_maps(g_ctr)), L.ptr(ws), ws.numel(), st),
-            'ld_loss_centerness')
-    L.check(lib.ld_loss_finalize(
-        C.byref(geom), C.byref(hp), L.ptr(targets['counts']), L.ptr(norm),
-        L.ptr(ws), L.ptr(losses), st), 'ld_loss_finalize')
+def _split_student(hp, nl, student):
+    """The flat student maps of ``LDLossBlock`` -> (cls, reg, x, kd_s, ctr).
+    The 4th group is LDv2's raw cls_feat or, with LD_LOSS_ATSS, the centerness
+    maps."""
+    cls, reg, x = student[:nl], student[nl:2 * nl], student[2 * nl:3 * nl]
+    extra = student[3 * nl:] or None
+    kd_s, ctr = (None, extra) if hp.flags & L.LD_LOSS_ATSS else (extra, None)
+    return cls, reg, x, kd_s, ctr
 
 
 class LDLossBlock(torch.autograd.Function):
@@ -709,12 +672,7 @@ class LDLossBlock(torch.autograd.Function):
     def forward(ctx, hp, targets, teacher, reduce_norm, unit_upstream,
                 *student):
         nl = targets['geom'].num_levels
-        cls, reg, x = (student[:nl], student[nl:2 * nl],
-                       student[2 * nl:3 * nl])
-        # 4th student group: LDv2 = raw cls_feat, LDATSS = centerness maps
-        extra = student[3 * nl:] or None
-        atss = bool(hp.flags & L.LD_LOSS_ATSS)
-        kd_s, ctr = (None, extra) if atss else (extra, None)
+        cls, reg, x, kd_s, ctr = _split_student(hp, nl, student)
         t_cls, t_reg, t_x = teacher[:3]
         kd_t = teacher[3] if len(teacher) > 3 else None
         losses, grads, norm, aux = loss_block_forward(
@@ -733,13 +691,8 @@ class LDLossBlock(torch.autograd.Function):
         grads = ctx.grads
         if not ctx.unit_upstream:
             hp, targets, teacher, norm = ctx.pack
-            student = ctx.saved_tensors
-            nl = ctx.nl
-            cls, reg, x = (student[:nl], student[nl:2 * nl],
-                           student[2 * nl:3 * nl])
-            extra = student[3 * nl:] or None
-            atss = bool(hp.flags & L.LD_LOSS_ATSS)
-            kd_s, ctr = (None, extra) if atss else (extra, None)
+            cls, reg, x, kd_s, ctr = _split_student(hp, ctx.nl,
+                                                    ctx.saved_tensors)
             # the normalisers are constants of the graph (the reference takes
             # them through .item(), ld_head.py:340-341,363): reuse them
             _, grads, _, _ = _rerun_with_upstream(hp, targets, teacher, norm,

@@ -874,23 +874,39 @@ PLAIN_INFER = dict(seed=81, nms_pre=100,
                                   [1.25, 1.25, 1.25, 1.25]])
 
 
+# The pyramid whose levels end in partly filled blocks AFTER a full one: pad
+# (8, 2056) gives one-row levels of 257, 129, 65, 33 and 17 cells, so the last
+# cell of level 0 is the first of a second 256-wide block and the last cells of
+# levels 0 to 2 sit in the second (third, fifth) 64-wide block.  Image 0: a
+# 62 px and a 250 px box around x = 2048, the far end of every level (positives
+# in cell 256 of level 0 and cell 64 of level 2 for the ATSS, MaxIoU and FCOS
+# assigners alike), and a 60 px box near x = 500; image 1 has no GT.
+RAGGED_PAD = (8, 2056)
+RAGGED_GT = [[(2018., -30., 2080., 32., 1), (1925., -125., 2175., 125., 3),
+              (470., -28., 530., 30., 0)], []]
+RAGGED_SEED = 74
+
+
 def plain_batch(case, device='cpu'):
-    """gt_bboxes / gt_labels / img_metas of a PLAIN_CASES entry."""
+    """gt_bboxes / gt_labels / img_metas of a PLAIN_CASES entry, or of the
+    RAGGED_PAD pyramid (``case`` 'ragged')."""
+    ragged = case == 'ragged'
     gtb, gtl = [], []
-    for rows in PLAIN_CASES[case]:
+    for rows in (RAGGED_GT if ragged else PLAIN_CASES[case]):
         a = torch.tensor([r[:4] for r in rows], dtype=torch.float32)
         gtb.append(a.reshape(-1, 4).to(device))
         gtl.append(torch.tensor([int(r[4]) for r in rows],
                                 dtype=torch.long).to(device))
-    h, w = PLAIN_PAD
+    h, w = RAGGED_PAD if ragged else PLAIN_PAD
     metas = [dict(img_shape=(h, w, 3), pad_shape=(h, w, 3),
                   ori_shape=(h, w, 3), scale_factor=1.0, flip=False)
              for _ in gtb]
     return dict(gt_bboxes=gtb, gt_labels=gtl, img_metas=metas)
 
 
-def plain_head_inputs(kind, seed, num_imgs=2, device='cpu', clamp=True):
-    """Head outputs of a plain head on the PLAIN_PAD pyramid: ``kind`` 'atss'
+def plain_head_inputs(kind, seed, num_imgs=2, device='cpu', clamp=True,
+                      pad=PLAIN_PAD):
+    """Head outputs of a plain head on the ``pad`` pyramid: ``kind`` 'atss'
     -> cls (N, 4, h, w), reg (N, 4, h, w) ~ 4 * randn (in units of the coder's
     stds 0.1 / 0.2), ctr; 'retina' -> cls (N, 36, h, w), reg (N, 36, h, w) ~
     0.5 * randn.  ``clamp``: the PLAIN_CLAMP positive's dw is set beyond
@@ -899,7 +915,7 @@ def plain_head_inputs(kind, seed, num_imgs=2, device='cpu', clamp=True):
     B = 1 if kind == 'atss' else 9
     amp = 4.0 if kind == 'atss' else 0.5
     out = dict(cls=[], reg=[])
-    for (h, w) in level_shapes(PLAIN_PAD):
+    for (h, w) in level_shapes(pad):
         out['cls'].append(
             _normal((num_imgs, B * PLAIN_CLASSES, h, w), gen) * 1.2 - 3.0)
         out['reg'].append(_normal((num_imgs, B * 4, h, w), gen) * amp)
@@ -907,7 +923,7 @@ def plain_head_inputs(kind, seed, num_imgs=2, device='cpu', clamp=True):
         n, l, y, x, b, v = PLAIN_CLAMP[kind]
         out['reg'][l][n, b * 4 + 2, y, x] = v
     if kind == 'atss':
-        out['ctr'] = synthetic_centerness(num_imgs, level_shapes(PLAIN_PAD),
+        out['ctr'] = synthetic_centerness(num_imgs, level_shapes(pad),
                                           seed=seed)
     return {k: [t.to(device) for t in v] for k, v in out.items()}
 
@@ -952,8 +968,9 @@ FCOS_NEG = dict(all=(0, 0, 5, 5), one=(0, 0, 6, 6))
 FCOS_NEG_CH = 2
 
 
-def fcos_head_inputs(seed, num_imgs=2, device='cpu', relu=False):
-    """Outputs of the plain FCOS head's convs on the PLAIN_PAD pyramid: cls
+def fcos_head_inputs(seed, num_imgs=2, device='cpu', relu=False,
+                     pad=PLAIN_PAD):
+    """Outputs of the plain FCOS head's convs on the ``pad`` pyramid: cls
     (N, 4, h, w) and ctr as for plain_head_inputs('atss'), ``raw`` (N, 4, h, w)
     ~ 0.5 * randn -- the box maps BEFORE Scale and exp / relu, so exp stays in
     range.  ``relu`` (the norm_on_bbox variants): every pre-activation is moved
@@ -965,7 +982,7 @@ def fcos_head_inputs(seed, num_imgs=2, device='cpu', relu=False):
     of FCOS_NEG and of the activation kernels' own test."""
     gen = _gen(seed)
     out = dict(cls=[], raw=[])
-    for (h, w) in level_shapes(PLAIN_PAD):
+    for (h, w) in level_shapes(pad):
         out['cls'].append(
             _normal((num_imgs, PLAIN_CLASSES, h, w), gen) * 1.2 - 3.0)
         out['raw'].append(_normal((num_imgs, 4, h, w), gen) * 0.5)
@@ -976,7 +993,7 @@ def fcos_head_inputs(seed, num_imgs=2, device='cpu', relu=False):
         n, l, y, x = FCOS_NEG['one']
         out['raw'][l][n, :, y, x] = out['raw'][l][n, :, y, x].abs() + 0.125
         out['raw'][l][n, FCOS_NEG_CH, y, x] *= -1.0
-    out['ctr'] = synthetic_centerness(num_imgs, level_shapes(PLAIN_PAD),
+    out['ctr'] = synthetic_centerness(num_imgs, level_shapes(pad),
                                       seed=seed)
     return {k: [t.to(device) for t in v] for k, v in out.items()}
 

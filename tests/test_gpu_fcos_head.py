@@ -87,8 +87,12 @@ def _run_loss(head, case, dev):
     cls / raw / ctr, grads of the scales (L,), inputs)."""
     from ld_amd import layers as Y
     batch = S.plain_batch(case, dev)
-    hi = S.fcos_head_inputs(S.PLAIN_SEEDS[case], device=dev,
-                            relu=head.norm_on_bbox)
+    if case == 'ragged':
+        hi = S.fcos_head_inputs(S.RAGGED_SEED, device=dev,
+                                relu=head.norm_on_bbox, pad=S.RAGGED_PAD)
+    else:
+        hi = S.fcos_head_inputs(S.PLAIN_SEEDS[case], device=dev,
+                                relu=head.norm_on_bbox)
     for v in hi.values():
         for t in v:
             t.requires_grad_(True)
@@ -123,14 +127,19 @@ def _ref64(head, hi, bbox_loss=None):
     return ref.detach(), maps, scales
 
 
-def _pos_per_level(head):
+def _pos_levels(head, pad=S.PLAIN_PAD):
+    """Per level the (N, cells) mask of the positives."""
     lab = head.last_targets['labels'].cpu()
     off, pos = 0, []
-    for h, w in S.level_shapes(S.PLAIN_PAD):
+    for h, w in S.level_shapes(pad):
         part = lab[:, off:off + h * w]
-        pos.append(int(((part >= 0) & (part < head.num_classes)).sum()))
+        pos.append((part >= 0) & (part < head.num_classes))
         off += h * w
     return pos
+
+
+def _pos_per_level(head):
+    return [int(p.sum()) for p in _pos_levels(head)]
 
 
 def _check_grads(grads, gs, want, want_gs, what):
@@ -483,6 +492,34 @@ def test_aug_test_equals_hand_merge():
     assert float((dets[:, 2] - dets[:, 0]).max()) > 8.0
 
 
+def test_ragged_block_tails_vs_float64():
+    """The dist form of tests/test_gpu_plain_heads.py::
+    test_ragged_block_tails_vs_float64: synthetic.RAGGED_PAD's levels of 257,
+    129, 65, 33 and 17 points end in a partly filled block after a full one.
+    Positives in the second 256-block of level 0 and the second 64-block of
+    level 2; image 1 has no GT.  Against float64 at this file's bars."""
+    dev = torch.device('cuda:0')
+    head = _head(dev)
+    _, table, grads, gs, hi = _run_loss(head, 'ragged', dev)
+    pos = _pos_levels(head, S.RAGGED_PAD)
+    assert [p.shape[1] for p in pos] == [257, 129, 65, 33, 17]
+    assert bool(pos[0][0, 256]) and bool(pos[0][0, :256].any())
+    assert bool(pos[2][0, 64]) and bool(pos[2][0, :64].any())
+    assert not any(bool(p[1].any()) for p in pos)
+    ref, maps, scales = _ref64(head, hi)
+    np.testing.assert_allclose(table.cpu().numpy().astype(np.float64),
+                               ref.numpy(), **LOSS_TOL)
+    _check_grads(grads, gs, lambda k, l: maps[k][l].grad.numpy(),
+                 scales.grad.numpy(), 'float64')
+    assert all(float(g[1].abs().sum()) == 0.0 for g in grads['raw'])
+    # a second run of the same step: the same bits
+    _, table2, grads2, gs2, _ = _run_loss(head, 'ragged', dev)
+    assert torch.equal(table, table2) and torch.equal(gs, gs2)
+    for k in grads:
+        for a, b_ in zip(grads[k], grads2[k]):
+            assert torch.equal(a, b_)
+
+
 # ---------------------------------------------------- C entry points: EINVAL --
 def test_entry_points_refuse_illegal_flag_combinations():
     from ld_amd import lib as L
@@ -508,21 +545,24 @@ def test_entry_points_refuse_illegal_flag_combinations():
                       'loss')
     ok = L.LD_LOSS_DIST | L.LD_LOSS_ATSS | L.LD_LOSS_FCOS
 
-    def pre(flags):
+    def pre(flags, delta=None, anchors=None, geom=geom):
         hp = LB.make_hp(num_classes=S.PLAIN_CLASSES, flags=flags,
                         bbox_loss='iou', lw_ctr=1.0)
-        return lib.ld_loss_dist_prepass(
-            C.byref(geom), C.byref(hp), L.ptr(labels), L.ptr(tg),
-            L.ptr(counts), L.ptr(wt), L.ptr(score), L.ptr(norm), L.ptr(ws),
-            ws.numel(), L.stream_ptr(dev))
+        return lib.ld_loss_plain_prepass(
+            C.byref(geom), C.byref(hp),
+            None if delta is None else C.byref(delta), L.ptr(anchors),
+            L.ptr(labels), L.ptr(tg), L.ptr(counts), L.ptr(wt), L.ptr(score),
+            L.ptr(norm), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
 
-    def pos(flags):
+    def pos(flags, delta=None, anchors=None, geom=geom):
         hp = LB.make_hp(num_classes=S.PLAIN_CLASSES, flags=flags,
                         bbox_loss='iou', lw_ctr=1.0)
-        return lib.ld_loss_dist_pos(
-            C.byref(geom), C.byref(hp), C.byref(m_cls), C.byref(m_reg),
-            L.ptr(labels), L.ptr(tg), L.ptr(score), L.ptr(norm), None,
-            C.byref(mg_reg), L.ptr(ws), ws.numel(), L.stream_ptr(dev))
+        return lib.ld_loss_plain_pos(
+            C.byref(geom), C.byref(hp),
+            None if delta is None else C.byref(delta), L.ptr(anchors),
+            C.byref(m_cls), C.byref(m_reg), L.ptr(labels), L.ptr(tg),
+            L.ptr(score), L.ptr(norm), None, C.byref(mg_reg), L.ptr(ws),
+            ws.numel(), L.stream_ptr(dev))
     assert pre(ok) == 0 and pos(ok) == 0
     assert pre(ok | L.LD_LOSS_DIST_NORM) == 0
     bad = [L.LD_LOSS_DIST, L.LD_LOSS_DIST | L.LD_LOSS_ATSS,
@@ -533,6 +573,25 @@ def test_entry_points_refuse_illegal_flag_combinations():
     for flags in bad:
         assert pre(flags) == -1, flags   # LD_EINVAL
         assert pos(flags) == -1, flags
+    # the delta side: `delta` is non-null exactly with LD_LOSS_DELTA
+    atss = L.LD_LOSS_ATSS | L.LD_LOSS_DELTA
+    from ld_amd.core import DeltaXYWHBBoxCoder
+    coder = DeltaXYWHBBoxCoder(*S.PLAIN_CODERS['atss'])
+    dc = coder.delta_t()
+    assert pre(atss, dc) == 0 and pos(atss, dc) == 0
+    assert pre(atss) == -1 and pos(atss) == -1
+    assert pre(ok, dc) == -1 and pos(ok, dc) == -1
+    # L1 on the deltas is RetinaHead's alone
+    l1 = coder.delta_t(box_term='l1')
+    assert pre(atss, l1) == -1 and pos(atss, l1) == -1
+    # explicit anchors: whole images of num_base pseudo-images each
+    b3 = DeltaXYWHBBoxCoder(*S.PLAIN_CODERS['retina']).delta_t(num_base=3)
+    anchors = torch.zeros((A * 3, 4), device=dev)
+    retina = L.LD_LOSS_RETINA | L.LD_LOSS_DELTA
+    assert geom.num_imgs == 2
+    assert pre(retina, b3, anchors) == -1 and pos(retina, b3, anchors) == -1
+    b2 = DeltaXYWHBBoxCoder(*S.PLAIN_CODERS['retina']).delta_t(num_base=2)
+    assert pre(retina, b2, anchors) == 0 and pos(retina, b2, anchors) == 0
     # the distribution prepass does not read 4-channel maps
     hp = LB.make_hp(num_classes=S.PLAIN_CLASSES, flags=ok, bbox_loss='iou')
     assert lib.ld_loss_prepass_ex(

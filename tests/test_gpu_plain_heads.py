@@ -77,7 +77,11 @@ def _outs(kind, hi):
 
 def _run_loss(kind, head, case, dev):
     batch = S.plain_batch(case, dev)
-    hi = S.plain_head_inputs(kind, S.PLAIN_SEEDS[case], device=dev)
+    if case == 'ragged':
+        hi = S.plain_head_inputs(kind, S.RAGGED_SEED, device=dev, clamp=False,
+                                 pad=S.RAGGED_PAD)
+    else:
+        hi = S.plain_head_inputs(kind, S.PLAIN_SEEDS[case], device=dev)
     for v in hi.values():
         for t in v:
             t.requires_grad_(True)
@@ -89,7 +93,7 @@ def _run_loss(kind, head, case, dev):
     return list(losses.keys()), table.detach(), grads, hi
 
 
-def _ref_targets(head, kind, C):
+def _ref_targets(head, kind, C, pad=S.PLAIN_PAD):
     """head.last_targets (the kernels' (N * B, A) arrays) in the row order of
     the reference: per level (image, cell, base anchor)."""
     t = head.last_targets
@@ -100,7 +104,7 @@ def _ref_targets(head, kind, C):
     wts = t['label_weights'].view(N, B, A).cpu().double()
     gts = t['bbox_targets'].view(N, B, A, 4).cpu().double()
     levels, off = [], 0
-    for (h, w) in S.level_shapes(S.PLAIN_PAD):
+    for (h, w) in S.level_shapes(pad):
         n = h * w
         levels.append(dict(
             labels=lab[:, :, off:off + n].permute(0, 2, 1).reshape(-1),
@@ -109,6 +113,26 @@ def _ref_targets(head, kind, C):
         off += n
     pos = ((lab >= 0) & (lab < C)).reshape(N, -1).sum(1).tolist()
     return dict(levels=levels, num_pos_img=pos)
+
+
+def _check_float64(tag, head, hi, t, got, grads, pad):
+    """Loss table and every gradient map against tests/_plain_ref64.py on the
+    kernels' own targets ``t``; -> the float64 maps with their gradients."""
+    kind, _, box_term, lw_bbox, beta = VARIANTS[tag]
+    anchors = [a.cpu().double() for a in head.anchor_generator.grid_anchors(
+        S.level_shapes(pad), hi['cls'][0].device)]
+    maps = {k: [x.detach().cpu().double().requires_grad_(True) for x in v]
+            for k, v in hi.items()}
+    ref = R.plain_loss(kind, maps, t, anchors, S.PLAIN_CLASSES,
+                       S.PLAIN_CODERS[kind], box_term, lw_bbox, beta)
+    ref.sum().backward()
+    np.testing.assert_allclose(got, ref.detach().numpy(), **LOSS_TOL)
+    for k, gs in grads.items():
+        for l, g in enumerate(gs):
+            np.testing.assert_allclose(g.cpu().numpy(),
+                                       maps[k][l].grad.numpy(), **GRAD_TOL,
+                                       err_msg=f'{k}[{l}] vs float64')
+    return maps
 
 
 @pytest.mark.parametrize('tag,case', LOSS_CASES,
@@ -140,20 +164,7 @@ def test_loss_block_vs_reference_and_float64(tag, case, gold):
                                        gold[f'{key}_g{k}_{l}'], **GRAD_TOL,
                                        err_msg=f'{k}[{l}] vs golden')
     # ... and against float64 autograd on the same targets
-    sizes = S.level_shapes(S.PLAIN_PAD)
-    anchors = [a.cpu().double()
-               for a in head.anchor_generator.grid_anchors(sizes, dev)]
-    maps = {k: [x.detach().cpu().double().requires_grad_(True) for x in v]
-            for k, v in hi.items()}
-    ref = R.plain_loss(kind, maps, t, anchors, C, S.PLAIN_CODERS[kind],
-                       box_term, lw_bbox, beta)
-    ref.sum().backward()
-    np.testing.assert_allclose(got, ref.detach().numpy(), **LOSS_TOL)
-    for k, gs in grads.items():
-        for l, g in enumerate(gs):
-            np.testing.assert_allclose(g.cpu().numpy(),
-                                       maps[k][l].grad.numpy(), **GRAD_TOL,
-                                       err_msg=f'{k}[{l}] vs float64')
+    maps = _check_float64(tag, head, hi, t, got, grads, S.PLAIN_PAD)
     if case == 'multi':
         # the positive whose dw sits beyond the clamp: exactly zero gradient
         # there, as in the reference (decoded box losses).  The clamped box
@@ -175,6 +186,41 @@ def test_loss_block_vs_reference_and_float64(tag, case, gold):
         assert all(float(g.abs().sum()) == 0.0 for g in grads['reg'])
     # a second run of the same step: the same bits
     _, table2, grads2, _ = _run_loss(kind, head, case, dev)
+    assert torch.equal(table, table2)
+    for k in grads:
+        for a, b_ in zip(grads[k], grads2[k]):
+            assert torch.equal(a, b_)
+
+
+@pytest.mark.parametrize('tag', ['atss', 'retina_l1'])
+def test_ragged_block_tails_vs_float64(tag):
+    """The plain prepass (64 cells per block) and positives kernel (256) on
+    synthetic.RAGGED_PAD, whose levels of 257, 129, 65, 33 and 17 cells end in
+    a partly filled block after a full one -- the PLAIN_PAD levels (256, 64,
+    16, 4, 1 cells) never do.  Positives sit in the second 256-block of level
+    0 and the second 64-block of level 2; image 1 has no GT.  Against float64
+    at this file's bars.  (FCOSHead: tests/test_gpu_fcos_head.py.)"""
+    kind = VARIANTS[tag][0]
+    dev = torch.device('cuda:0')
+    head = _head(kind, dev, **VARIANTS[tag][1])
+    _, table, grads, hi = _run_loss(kind, head, 'ragged', dev)
+    C = S.PLAIN_CLASSES
+    t = _ref_targets(head, kind, C, S.RAGGED_PAD)
+    sizes = S.level_shapes(S.RAGGED_PAD)
+    assert [h * w for h, w in sizes] == [257, 129, 65, 33, 17]
+
+    def pos_cells(l):  # rows of a level: (image, cell, base anchor)
+        lab = t['levels'][l]['labels']
+        rows = ((lab >= 0) & (lab < C)).nonzero()[:, 0]
+        return (rows // head.num_anchors) % (sizes[l][0] * sizes[l][1])
+    assert int(pos_cells(0).max()) >= 256 and int(pos_cells(0).min()) < 256
+    assert int(pos_cells(2).max()) >= 64 and int(pos_cells(2).min()) < 64
+    assert t['num_pos_img'][0] > 0 and t['num_pos_img'][1] == 0
+    got = table.cpu().numpy().astype(np.float64)
+    _check_float64(tag, head, hi, t, got, grads, S.RAGGED_PAD)
+    assert all(float(g[1].abs().sum()) == 0.0 for g in grads['reg'])
+    # a second run of the same step: the same bits
+    _, table2, grads2, _ = _run_loss(kind, head, 'ragged', dev)
     assert torch.equal(table, table2)
     for k in grads:
         for a, b_ in zip(grads[k], grads2[k]):
